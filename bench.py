@@ -22,8 +22,19 @@ N > 1 (torch.distributed.run, one process per GPU): BASELINE config 3 at a
   vs in one group), and config 3 on comms bounded to rings x 2..64 channels
   — skip with --no-extras.  Every timed path is checked afterwards.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--bytes S]
-       [--workload reduce_copy|allreduce|rs_ag] [--sweep] [--no-extras]
+A plain run (no --full) does only what the headline needs: set up, warm up,
+time the K steps, write the outputs if asked, print the line.  Everything
+named above beside `value` — the correctness checks, `cpu_baseline`, the
+per-launch and PMC passes of `roofline`, the peer-copy microbench, `extras`,
+the single-process init check — runs with --full only (and there the --no-*
+options still drop single legs).  --dump-outputs DIR writes what the last
+timed step computed as DIR/<name>.npy (float32; a fixed sample of 48 MiB in
+all when the output is larger); the inputs are seeded, so two builds can be
+compared output for output.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--bytes S] [--full]
+       [--dump-outputs DIR] [--workload reduce_copy|allreduce|rs_ag] [--sweep]
+       [--no-extras]
 """
 import argparse
 import ctypes
@@ -144,6 +155,31 @@ def _evt():
     return torch.cuda.Event(enable_timing=True)
 
 
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs: every file of one run together
+
+
+def dump_outputs(dirname, tensors):
+    """--dump-outputs: write each 1-D device tensor of `tensors` ({name:
+    tensor}) as dirname/<name>.npy in float32 (float64 stays float64).  The
+    files of one call share DUMP_MAX_BYTES; a tensor larger than its share is
+    cut to a fixed sample of it: its first and last 2^16 elements, then
+    indices drawn once by a generator seeded with the tensor's length (sorted,
+    without the ends) — the same elements in every run of the same shape."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(tensors)) - 4096  # the .npy headers
+    for name, t in tensors.items():
+        t = t.reshape(-1)
+        odt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        keep = share // (8 if odt == torch.float64 else 4)
+        if t.numel() > keep:
+            edge = 1 << 16
+            g = torch.Generator().manual_seed(t.numel())
+            mid = torch.randint(edge, t.numel() - edge, (keep - 2 * edge,), generator=g).sort().values
+            idx = torch.cat([torch.arange(edge), mid, torch.arange(t.numel() - edge, t.numel())])
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.to(odt).cpu().numpy())
+
+
 def bench_reduce_copy(args):
     n = (args.bytes or (256 << 20)) // 4
     stream = torch.cuda.current_stream()
@@ -204,19 +240,22 @@ def bench_reduce_copy(args):
     wall = time.perf_counter() - t0
     gpu_s = e0.elapsed_time(e1) / 1e3
     ev_launches = args.steps - lead
-    # correctness of the measured buffers (bit-exact f32 add), after the timed
-    # region so no idle gap separates warmup and timing
-    assert torch.equal(d.view(torch.int32), (a + b).view(torch.int32)), "reduce-copy mismatch"
-    # per-launch kernel durations, separately (an event pair per launch
-    # serialises the queue, so it stays out of the timed region)
+    if args.dump_outputs:  # what the last timed step left in the destination
+        dump_outputs(args.dump_outputs, {"reduce_copy_dst": d})
     kern_ms = []
-    for _ in range(min(args.steps, 20)):
-        s0, s1 = _evt(), _evt()
-        s0.record(stream)
-        step()
-        s1.record(stream)
-        torch.cuda.synchronize()
-        kern_ms.append(s0.elapsed_time(s1))
+    if args.full:
+        # correctness of the measured buffers (bit-exact f32 add), after the timed
+        # region so no idle gap separates warmup and timing
+        assert torch.equal(d.view(torch.int32), (a + b).view(torch.int32)), "reduce-copy mismatch"
+        # per-launch kernel durations, separately (an event pair per launch
+        # serialises the queue, so it stays out of the timed region)
+        for _ in range(min(args.steps, 20)):
+            s0, s1 = _evt(), _evt()
+            s0.record(stream)
+            step()
+            s1.record(stream)
+            torch.cuda.synchronize()
+            kern_ms.append(s0.elapsed_time(s1))
     bytes_per = 3 * n * 4
     avg_kern_s = gpu_s / ev_launches  # HIP events inside the timed region, launch stream
     achieved = bytes_per / avg_kern_s / 1e9
@@ -225,7 +264,7 @@ def bench_reduce_copy(args):
             "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
             "kernel": "k_reduce_copy<FnSum<float>,2,1>", "algorithmic_bytes_per_launch": bytes_per,
             "avg_launch_us": round(avg_kern_s * 1e6, 2), "event_span_launches": ev_launches,
-            "single_launch_us_median": round(float(np.median(kern_ms)) * 1e3, 2)}
+            "single_launch_us_median": round(float(np.median(kern_ms)) * 1e3, 2) if kern_ms else None}
     out = {"metric": "device reduce-copy GB/s vs HBM peak; all-reduce busbw at 1/2/4/8 GPUs",
            "value": round(value, 1), "unit": "GB/s", "n_gpus": 1, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": round(wall / args.steps * 1e3, 4),
@@ -237,7 +276,7 @@ def bench_reduce_copy(args):
            "roofline": roof, "preroll": preroll}
     # HBM traffic of the same kernel measured live on this box (PMC passes in
     # child processes); the committed summary only when that is impossible
-    if not args.no_pmc_live:
+    if args.full and not args.no_pmc_live:
         live, why = _pmc_live(bytes_per)
         if live is not None:
             roof["traffic"] = live["hbm_bytes_per_launch"]
@@ -246,13 +285,13 @@ def bench_reduce_copy(args):
             roof["traffic"] = _pmc_traffic("reduce_copy", bytes_per)
             roof["traffic_detail"] = {"source": "committed profiles/pmc_traffic.json",
                                       "live_error": why}
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(n)
         try:
             out["cpu_baseline"]["staging"] = staging_rates(a, b)
         except Exception as e:  # noqa: BLE001 - reported, not fatal to the headline
             out["cpu_baseline"]["staging_error"] = repr(e)
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         out["extras"] = {"config1_allreduce_1KiB_world1": bench_one_rank_latency()}
         del a, b, d
         try:
@@ -1168,13 +1207,13 @@ def bench_allreduce(args):
     # compare per dtype on 4 Ki elements: their first launches load code
     # objects for ~0.1-0.2 s); reported as check_warmup_s, outside check_s.
     t_w = time.perf_counter()
-    for tdt in _TDT.values():
+    for tdt in _TDT.values() if args.full else ():
         w = torch.empty(4096, dtype=tdt, device="cuda")
         pattern_fill(w, rank, world)
         pattern_ok(w, world)
     torch.cuda.synchronize()
     check_warmup_s = time.perf_counter() - t_w
-    xgmi = peer_copy_bench(dist, rank, world) if not args.no_peer else None
+    xgmi = peer_copy_bench(dist, rank, world) if args.full and not args.no_peer else None
     sizes = [1 << p for p in range(3, 31)] if args.sweep else [args.bytes or (1 << 30)]
     rows = []
     call_errs = []
@@ -1183,7 +1222,9 @@ def bench_allreduce(args):
         g = torch.Generator(device="cuda").manual_seed(1000 + rank)
         x = torch.rand(n, device="cuda", generator=g) * 2 - 1
         y = torch.empty_like(x)
-        steps = args.steps if S >= (64 << 20) else max(args.steps, 20)
+        # --steps is the number of timed steps; only the sweep's small rows
+        # (latency-regime sizes) take at least 20
+        steps = max(args.steps, 20) if args.sweep and S < (64 << 20) else args.steps
 
         def fn():
             # a call refused after an async error (ncclInternalError /
@@ -1198,6 +1239,8 @@ def bench_allreduce(args):
         busbw = algbw * 2 * (world - 1) / world
         rows.append({"bytes": n * 4, "us": dt / steps * 1e6, "algbw": algbw, "busbw": busbw,
                      "algo": comm.coll_algo(0, n, nccl.ncclFloat32)})
+        if args.dump_outputs and rank == 0 and S == sizes[-1]:  # every rank holds the same sum
+            dump_outputs(args.dump_outputs, {"allreduce_out": y})
         del x, y
         if rank == 0 and args.sweep:
             print(f"# allreduce {n*4:>12d} B  {dt/steps*1e6:10.1f} us  algbw {algbw:8.2f}  "
@@ -1209,7 +1252,7 @@ def bench_allreduce(args):
     e = torch.tensor([comm.async_error() or max(call_errs, default=0)], dtype=torch.int64)
     dist.all_reduce(e, op=dist.ReduceOp.MAX)
     head_err = int(e.item())
-    full = not args.sweep and not args.no_extras and head_err == 0
+    full = args.full and not args.sweep and not args.no_extras and head_err == 0
     tcomm = _Tolerant(comm)
     extras = bench_extras(dist, tcomm, rank, world, args) if full else None
     # Correctness of everything timed above, on this topology (fences off and on).
@@ -1245,23 +1288,26 @@ def bench_allreduce(args):
     # after a headline error (the same verdict on every rank) nothing more is
     # run on the comm: its calls are refused, and a rank that raised would
     # skip the gloo collectives of a check that its peers still enter
-    checks = (run_checks(dist, tcomm, rank, world, plan) if head_err == 0
+    checks = (run_checks(dist, tcomm, rank, world, plan) if args.full and head_err == 0
               else {"check_ms": {}, "fences_off": {}, "fences_on": {}})
     err = comm.async_error()
     n_channels, ring_orders = comm.n_channels(), nccl.ring_orders(world)
     comm.destroy()
     initall = None
-    if not args.no_initall and world > 1 and torch.cuda.device_count() > 1 and head_err == 0:
+    if args.full and not args.no_initall and world > 1 and torch.cuda.device_count() > 1 and head_err == 0:
         # one process drives every GPU while the other ranks wait at the barrier
         initall = initall_check(torch.cuda.device_count()) if rank == 0 else None
         dist.barrier()
     t_chk = time.perf_counter() - t_chk
     last = rows[-1]
     rpd, roof, cpu_base = line_roofline_and_baseline(dist, rank, world, last, torch.cuda.device_count(),
-                                                     ring_orders, n_channels, xgmi, cpu=not args.no_cpu)
+                                                     ring_orders, n_channels, xgmi,
+                                                     cpu=args.full and not args.no_cpu)
     line_s = time.perf_counter() - _T_START
     correct_all = (_flatten_ok(checks) and (initall is None or initall.get("ok") is True)
                    and head_err == 0)
+    if not args.full and head_err == 0:
+        correct_all = None  # no check ran: the checks belong to --full
     out = {"metric": "device reduce-copy GB/s vs HBM peak; all-reduce busbw at 1/2/4/8 GPUs",
            "value": round(last["busbw"], 2), "unit": "GB/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(last["us"] / 1e3, 4),
@@ -1283,7 +1329,7 @@ def bench_allreduce(args):
            "correct": {"all": correct_all, **checks, "initall_single_process": initall,
                        "headline_async_error": head_err,
                        **({"extras_skipped": "async error during the headline timing"}
-                          if head_err and not args.sweep and not args.no_extras else {}),
+                          if head_err and args.full and not args.sweep and not args.no_extras else {}),
                        "check_s": round(t_chk, 2), "check_warmup_s": round(check_warmup_s, 3),
                        "line_s": round(line_s, 2),  # bench.py start (imports included) -> here
                        "check_frac": round(t_chk / line_s, 3),
@@ -1829,9 +1875,10 @@ def _reduce_row(dist, comm, rank, world, S, root=None):
             "correct": ok, "algo": comm.coll_algo(4, n, nccl.ncclFloat32)}
 
 
-def _rs_ag(dist, comm, rank, world, S, steps, warmup, dtype="bf16"):
+def _rs_ag(dist, comm, rank, world, S, steps, warmup, dtype="bf16", dump=None):
     """Reduce-scatter of an S-byte bucket (n blocks) then all-gather of the
-    shards back: busbw = (S / t) (n-1)/n each, and us per call."""
+    shards back: busbw = (S / t) (n-1)/n each, and us per call.  `dump`: the
+    --dump-outputs directory for this rank's shard and gathered bucket."""
     sp = torch.cuda.current_stream().cuda_stream
     tdt, code = _TDT[dtype], _CODE[dtype]
     n = S // torch.tensor([], dtype=tdt).element_size()
@@ -1849,6 +1896,8 @@ def _rs_ag(dist, comm, rank, world, S, steps, warmup, dtype="bf16"):
     t_rs = _time_coll(dist, rs, steps, warmup)
     t_ag = _time_coll(dist, ag, steps, warmup)
     frac = (world - 1) / world
+    if dump:
+        dump_outputs(dump, {"reduce_scatter_shard": shard, "all_gather_out": y})
     del x, y, shard
     torch.cuda.empty_cache()
     return {"bytes": S, "dtype": dtype, "steps": steps,
@@ -1862,8 +1911,10 @@ def _rs_ag(dist, comm, rank, world, S, steps, warmup, dtype="bf16"):
 def bench_rs_ag(args):
     """BASELINE config 4: reduce-scatter + all-gather bf16 bucket."""
     dist, rank, world, comm = _dist_setup()
-    r = _rs_ag(dist, comm, rank, world, args.bytes or (4 << 30), args.steps, args.warmup)
-    rs_ok, ag_ok = check_rs_ag(dist, comm, rank, world, args.bytes or (4 << 30))
+    r = _rs_ag(dist, comm, rank, world, args.bytes or (4 << 30), args.steps, args.warmup,
+               dump=args.dump_outputs if rank == 0 else None)
+    rs_ok, ag_ok = (check_rs_ag(dist, comm, rank, world, args.bytes or (4 << 30)) if args.full
+                    else (None, None))
     comm.destroy()
     dist.destroy_process_group()
     if rank:
@@ -1885,6 +1936,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--bytes", type=int, default=0)
     ap.add_argument("--workload", default="")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: checks, CPU baselines, roofline passes, extras")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-peer", action="store_true")

@@ -10,6 +10,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -25,7 +26,7 @@ def test_two_rank_line_roofline_and_cpu_baseline():
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.pop("VCCL_ALLOW_SHARED_DEVICE", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3",
                         "--warmup", "1", "--bytes", str(64 << 20), "--no-extras", "--no-initall"],
                        env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -55,7 +56,7 @@ def test_broken_path_line_fails_fast():
     env.pop("WORLD_SIZE", None)
     env.update({"VCCL_NET_FORCE": "1", "VCCL_DEBUG_NET_SHORT_SLOT": str(64 << 10),
                 "VCCL_SPIN_TIMEOUT_S": "6"})
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "2",
                         "--warmup", "1", "--bytes", str(64 << 20), "--no-initall", "--no-cpu"],
                        env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -77,7 +78,7 @@ def test_error_mid_extras_still_prints_line():
     env.pop("WORLD_SIZE", None)
     env.update({"VCCL_NET_FORCE": "1", "VCCL_DEBUG_NET_SHORT_SLOT": str(512 << 10),
                 "VCCL_SPIN_TIMEOUT_S": "6"})
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "2",
                         "--warmup", "1", "--bytes", str(64 << 10), "--no-initall", "--no-cpu",
                         "--rs-ag-bytes", str(8 << 20)],
                        env=env, capture_output=True, text=True, timeout=400, cwd=ROOT)
@@ -87,6 +88,31 @@ def test_error_mid_extras_still_prints_line():
     assert c["headline_async_error"] == 0 and c["all"] is False, c
     assert "stopped" in line["extras"], sorted(line["extras"])
     assert line["config"]["async_error"] != 0
+
+
+def test_plain_line_is_lean_and_dumps_its_output(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline
+    fields only (no CPU baseline, no extras, no PMC or per-launch passes), K
+    timed steps, and --dump-outputs writes the destination of the last timed
+    step — at 4 MiB the whole buffer, bitwise the sum of the seeded inputs."""
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    n = 1 << 20
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
+                        "--warmup", "1", "--bytes", str(4 * n), "--preroll-s", "0",
+                        "--dump-outputs", str(tmp_path / "out")],
+                       env=env, capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "GB/s" and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert "cpu_baseline" not in line and "extras" not in line, sorted(line)
+    assert line["roofline"]["traffic"] is None and line["roofline"]["single_launch_us_median"] is None
+    got = np.load(tmp_path / "out" / "reduce_copy_dst.npy")
+    assert got.dtype == np.float32 and got.shape == (n,)
+    a = torch.rand(n, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1)) * 2 - 1
+    b = torch.rand(n, device="cuda", generator=torch.Generator(device="cuda").manual_seed(2)) * 2 - 1
+    assert np.array_equal(got.view(np.int32), (a + b).cpu().numpy().view(np.int32))
 
 
 def test_staging_row_checked():

@@ -3,7 +3,7 @@
 #   tools/gpu_run.sh <label> <step> [<step> ...]
 # steps: test      pytest -m gpu (one process, per-test timeout)
 #        test:<k>  pytest -m gpu -k <k>
-#        bench     bench.py at N=1 (the driver's default invocation)
+#        bench     bench.py --full at N=1 (headline, checks, CPU baseline, extras)
 #        prof      rocprofv3 --kernel-trace --stats of bench.py (no CPU leg)
 #        n2        bench.py N>1 rehearsal: 2 ranks sharing the one GPU
 #        nr:<n>    the same with n ranks
@@ -38,18 +38,18 @@ for s in "$@"; do
   case $s in
     test) timeout -k 10 1100 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > $O/pytest_gpu.log 2>&1 ;;
     test:*) lg=$(printf %s "${s#test:}" | tr -c 'A-Za-z0-9_' '_'); timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -k "${s#test:}" > "$O/pytest_$lg.log" 2>&1 ;;
-    bench) timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err ;;
+    bench) timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err ;;
     prof) (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu --no-extras > $O/bench_prof.json 2> $O/bench_prof.err) ;;
-    n2) timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 > $O/bench_n2.json 2> $O/bench_n2.err ;;
-    nr:*) timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node ${s#nr:} --master-addr 127.0.0.1 --master-port 29535 bench.py --gpus ${s#nr:} --steps 5 --warmup 2 > $O/bench_n${s#nr:}.json 2> $O/bench_n${s#nr:}.err ;;
-    spawn:*) timeout -k 10 900 python bench.py --gpus ${s#spawn:} --steps 5 --warmup 2 > $O/bench_spawn_n${s#spawn:}.json 2> $O/bench_spawn_n${s#spawn:}.err ;;
+    n2) timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --full --steps 5 --warmup 2 > $O/bench_n2.json 2> $O/bench_n2.err ;;
+    nr:*) timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node ${s#nr:} --master-addr 127.0.0.1 --master-port 29535 bench.py --gpus ${s#nr:} --full --steps 5 --warmup 2 > $O/bench_n${s#nr:}.json 2> $O/bench_n${s#nr:}.err ;;
+    spawn:*) timeout -k 10 900 python bench.py --gpus ${s#spawn:} --full --steps 5 --warmup 2 > $O/bench_spawn_n${s#spawn:}.json 2> $O/bench_spawn_n${s#spawn:}.err ;;
     smoke) timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 ;;
     py:*) timeout -k 10 600 python -u ${s#py:} > $O/$(basename ${s#py:} .py).log 2>&1 ;;
     sweep:*) SWEEP_MODE=${s#sweep:} SWEEP_ROUNDS=${SWEEP_ROUNDS:-6} timeout -k 10 300 python -u tools/sweep_rc.py > $O/sweep_${s#sweep:}.log 2>&1 ;;
     pmcshapes) timeout -k 10 200 python -u tools/rc_shape_driver.py > $O/rc_shape_driver.log 2>&1 && timeout -k 10 500 python -u tools/pmc_shapes.py > $O/pmc_shapes.log 2>&1 && cp gpurun_out/pmc_shapes.json $O/ ;;
     pmc) timeout -k 10 400 python -u tools/pmc_traffic.py > $O/pmc_traffic.log 2>&1 && cp gpurun_out/pmc_traffic.json $O/ ;;
     lat:*) timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node ${s#lat:} --master-addr 127.0.0.1 --master-port 29534 tools/coll_latency.py > $O/lat_n${s#lat:}.log 2> $O/lat_n${s#lat:}.err ;;
-    mprof:*) timeout -k 10 600 python -u tools/mp_prof.py ${s#mprof:} $O/mprof_n${s#mprof:} --steps 5 --warmup 2 > $O/mprof_n${s#mprof:}.log 2>&1 ;;
+    mprof:*) timeout -k 10 600 python -u tools/mp_prof.py ${s#mprof:} $O/mprof_n${s#mprof:} --full --steps 5 --warmup 2 > $O/mprof_n${s#mprof:}.log 2>&1 ;;
     fence:*) timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node ${s#fence:} --master-addr 127.0.0.1 --master-port 29536 tools/fence_cost.py > $O/fence_n${s#fence:}.json 2> $O/fence_n${s#fence:}.err ;;
     lll:*) n=${s#lll:}; q=${n#*q}; n=${n%q*}; [ "$q" = "$n" ] && q=4; GPU_MAX_HW_QUEUES=$q timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 29537 tools/ll_latency.py > $O/lll_n${n}_q${q}.json 2> $O/lll_n${n}_q${q}.err ;;
     lltrace:*) n=${s#lltrace:}; MP_PROF_SCRIPT=tools/ll_latency.py MP_PROF_FLAGS=--hip-runtime-trace timeout -k 10 600 python -u tools/mp_prof.py $n $O/lltrace_n$n > $O/lltrace_n$n.log 2>&1 && python tools/ll_trace.py $O/lltrace_n$n > $O/lltrace_n$n.json ;;

@@ -15,6 +15,6 @@ for algo in auto Ring Direct; do
   if [ "$algo" = auto ]; then unset NCCL_ALGO; else export NCCL_ALGO=$algo; fi
   if [ "$algo" = Direct ]; then export VCCL_DIRECT_THRESHOLD=$((1 << 30)); else unset VCCL_DIRECT_THRESHOLD; fi
   timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" \
-    --master-addr 127.0.0.1 --master-port $port bench.py --gpus "$N" --sweep --no-peer \
+    --master-addr 127.0.0.1 --master-port $port bench.py --gpus "$N" --full --sweep --no-peer \
     --steps 5 --warmup 2 > "$OUT/sweep_${N}rank_$algo.json" 2> "$OUT/sweep_${N}rank_$algo.log"
 done
