@@ -2,7 +2,7 @@
 expected result of a ring collective with the CPU oracle.
 
 The ring's element -> (channel, chunk) partition is VCCL's own (the device
-follows it, host/enqueue.cc cbd_schedule; the tests take it from the oracle's
+follows it, host/plan.cc cbd_schedule; the tests take it from the oracle's
 independent restatement, oracle/vccl_sched.py); the ring set per channel and
 the channel count mirror vccl_amd/csrc/host/init.cc.  The oracle's ring_fold
 then reproduces the fold order element by element, so ring results are
@@ -139,7 +139,7 @@ def group_algos(calls, n, coll_algo):
 
 
 def select_algo(policy, coll, esz, count, n):
-    """The library's path of one bucket (host/enqueue.cc select_algo) on an
+    """The library's path of one bucket (host/plan.cc select_algo) on an
     explicit policy dict (vcclGroupPlanEx's policy fields); coll "ar" | "rs" |
     "ag", count in elements of esz."""
     if n < 2 or policy["force"] == 1:
@@ -256,7 +256,7 @@ def direct_shard_elts(count, n, elt_size):
 
 
 def direct_chunk_elts(count, n, elt_size, chunk_bytes=16 << 20):
-    """Elements per chunk (host/init.cc inbox region, host/enqueue.cc launch_direct)."""
+    """Elements per chunk (host/init.cc inbox region, host/launch.cc launch_direct)."""
     region = (chunk_bytes + n - 1) // n // 256 * 256 + 256
     unit = n * max(1, 16 // elt_size)
     return min(count, (region - 16) // elt_size * n // unit * unit)

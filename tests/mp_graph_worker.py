@@ -152,7 +152,7 @@ def captures_on_destroyed_streams(comm, rank, n):
     """The capture-ordering pool after 16 captures whose streams were
     destroyed: each entry's capture has ended and its stream is gone, so a
     new capture must find a free entry (the liveness query on a destroyed
-    stream handle reads as ended, host/enqueue.cc capture_live) — no crash, no
+    stream handle reads as ended, host/launch.cc capture_live) — no crash, no
     refusal — and replay exactly."""
     import ctypes
     hip = ctypes.CDLL("libamdhip64.so")
@@ -274,7 +274,7 @@ def main():
     g = torch.cuda.CUDAGraph()
     # An eager call on ANOTHER stream right before the capture: the capture
     # must not wait on (or overwrite) the comm's eager ordering event, which
-    # was recorded outside it (enqueue.cc stream_order / stream_mark).
+    # was recorded outside it (launch.cc stream_order / stream_mark).
     eager_x = torch.arange(4099, device="cuda", dtype=torch.float32) + rank
     eager_y = torch.empty_like(eager_x)
     comm.all_reduce(eager_x.data_ptr(), eager_y.data_ptr(), 4099, nccl.ncclFloat32, nccl.ncclSum,

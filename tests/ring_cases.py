@@ -185,7 +185,7 @@ def group_algos(coll_algo, n_ranks):
 
 def group_plan_works(n_ranks, nch, slot_bytes, nthreads=512, algos=None):
     """[CbdWork per GROUP_CASES call]: the group's VCCL plan
-    (host/enqueue.cc launch_planned) with every call on its aggregate's path
+    (host/launch.cc launch_planned) with every call on its aggregate's path
     (`algos`, group_algos; None = every call RING / SIMPLE)."""
     return _ring.group_works(GROUP_CALLS, n_ranks, nch, slot_bytes, nthreads, algos=algos)
 

@@ -1,5 +1,5 @@
 """CPU simulation of the two-shot direct all-reduce's data movement
-(vccl_amd/csrc/device/direct.hpp, host/enqueue.cc launch_direct).
+(vccl_amd/csrc/device/direct.hpp, host/launch.cc launch_direct).
 
 Replays phases 1-3 with numpy over the same shard / block partition and inbox
 region layout the kernel uses, and checks that (a) every write stays inside
@@ -20,7 +20,7 @@ MIN_BLK_BYTES = 16 << 10
 
 
 def _geometry(count, n, esz, max_blocks, chunk_bytes):
-    """host/enqueue.cc launch_direct: chunk, block length (fixed per launch),
+    """host/launch.cc launch_direct: chunk, block length (fixed per launch),
     block count, inbox region bytes."""
     align = max(1, 16 // esz)
     region = (chunk_bytes + n - 1) // n // 256 * 256 + 256

@@ -1,6 +1,6 @@
 """VCCL's multi-task plan for a group of ring calls — CPU checks.
 
-* the library's group planner (vcclGroupPlan, host/enqueue.cc group_plan)
+* the library's group planner (vcclGroupPlan, host/plan.cc group_plan)
   equals the oracle's independent restatement (oracle/vccl_sched.py
   plan_schedule) over random groups of mixed collectives, types, ops and
   sizes, and a group of one call equals the one-call partition;

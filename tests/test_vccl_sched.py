@@ -1,6 +1,6 @@
 """VCCL's ring channel partition (cbd split + chunking) — CPU checks.
 
-* the library's host planner (vcclRingPartition, host/enqueue.cc
+* the library's host planner (vcclRingPartition, host/plan.cc
   cbd_schedule) equals the oracle's independent restatement
   (oracle/vccl_sched.py) over a sweep of collectives, sizes, types, rank and
   channel counts and slot sizes;

@@ -77,7 +77,7 @@ struct DirectWork {
   int64_t chunkElts;     // elements per chunk (last one shorter)
   int64_t blkElts;       // elements per block, the same for every chunk
   int64_t regionBytes;   // bytes per (phase, rank) inbox region
-  // VCCL's cbd channel partition (host/enqueue.cc cbd_schedule, the ring's
+  // VCCL's cbd channel partition (host/plan.cc cbd_schedule, the ring's
   // own) of the recvcount block (reduce-scatter) or of the whole bucket
   // (all-reduce, with the ring chunk arChunk): channel c of [channelLo,
   // channelHi] folds on ring c mod nRings (DevComm::rsOrder / ringAt), so

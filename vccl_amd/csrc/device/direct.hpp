@@ -36,7 +36,7 @@
 // only ever touches the inbox bytes [b * blkElts, (b + 1) * blkElts) of a
 // region, so the per-block flags order all reuse of those bytes.  A fused
 // batch (DirectBatch) keeps that true across its parts by giving every part
-// ONE block length (host/enqueue.cc launch_direct).
+// ONE block length (host/launch.cc launch_direct).
 //  * the all-reduce double-buffers its chunks by parity (regions and flags,
 //    direct_allreduce_part): parity p is rewritten for chunk c+2 only after
 //    the readers' flags of chunk c were awaited;

@@ -210,6 +210,25 @@ struct ncclComm {
 };
 
 namespace vccl {
+// Makes `device` current for a scope: hipSetDevice only when it differs from
+// the current one, the previous device restored on scope exit (that result
+// ignored).  status: the failure of the query or of the switch, for HIPCHECK
+// where either is an error.  A failed query leaves the device alone unless
+// `ignoreQuery` (the teardown paths, which switch regardless).
+struct __attribute__((visibility("hidden"))) DeviceGuard {
+  const int device;
+  int old = -1;
+  hipError_t status;
+  explicit DeviceGuard(int dev, bool ignoreQuery = false) : device(dev), status(hipGetDevice(&old)) {
+    if (status != hipSuccess) old = -1;
+    if (status == hipSuccess || ignoreQuery) status = old != device ? hipSetDevice(device) : hipSuccess;
+  }
+  ~DeviceGuard() {
+    if (old >= 0 && old != device) (void)hipSetDevice(old);
+  }
+  DeviceGuard(const DeviceGuard&) = delete;
+};
+
 constexpr uint64_t kCommMagic = 0x76636363'6c6d6933ull;  // "vccclmi3"
 // A valid, live comm whose initialisation has ended (a non-blocking one is
 // waited for); its result unless allowFailedInit (destroy / abort).

@@ -61,7 +61,7 @@ static uint64_t debug_subsys_mask(const char* spec) {
 }
 
 static uint64_t subsys_of(const char* base) {
-  if (!strncmp(base, "enqueue", 7)) return kSubColl;
+  if (!strncmp(base, "enqueue", 7) || !strncmp(base, "launch", 6)) return kSubColl;
   if (!strncmp(base, "proxy", 5)) return kSubNet | kSubProxy;
   if (!strncmp(base, "bootstrap", 9)) return kSubBootstrap;
   if (!strncmp(base, "debug", 5)) return kSubEnv;

@@ -593,7 +593,7 @@ static ncclResult_t init_rank(ncclComm* c, const ncclUniqueId* id) {
     }
     if (share > 1) {
       const int cap = std::max(1, cus * 7 / 8 / share);
-      c->shareBlockCap = cap;  // the LL and direct grids too (enqueue.cc)
+      c->shareBlockCap = cap;  // the LL and direct grids too (launch.cc)
       c->directMaxBlocks = std::min(c->directMaxBlocks, cap);
       if (c->nChannels > cap) {
         VINFO("rank %d: %d ranks share a GPU of %d CUs: %d -> %d ring channels", c->rank, share, cus,
@@ -876,7 +876,7 @@ ncclResult_t comm_init_rank(ncclComm_t* out, int nranks, const ncclUniqueId* id,
 
 // Wait for THIS comm's launches only — its ordering event, which every eager
 // launch of the comm records (bound to the kernel's completion, or a marker
-// behind it; enqueue.cc stream_mark), and the launches of one comm are
+// behind it; launch.cc stream_mark), and the launches of one comm are
 // serialised through it, so the last one done means all done.  The
 // reference's commReclaim likewise waits on the comm's own strong stream
 // (src/init.cc:2079-2111), never the whole device: a hipDeviceSynchronize
@@ -901,9 +901,7 @@ static bool wait_own_launches(ncclComm* c, double timeoutS) {
 ncclResult_t comm_wait_own_launches(ncclComm* c) { return wait_own_launches(c, -1) ? ncclSuccess : ncclInternalError; }
 
 ncclResult_t comm_destroy(ncclComm* c, bool abort) {
-  int old = -1;
-  (void)hipGetDevice(&old);
-  (void)hipSetDevice(c->device);
+  DeviceGuard dev(c->device, /*ignoreQuery=*/true);
   // ncclCommAbort (init.cc:2079-2111): raise the abort word every spin of the
   // comm's kernels polls (ring.hpp / ll.hpp / direct.hpp, as checkAbort,
   // primitives.h:142-152), then wait for the comm's own work only.
@@ -936,7 +934,6 @@ ncclResult_t comm_destroy(ncclComm* c, bool abort) {
   c->bootstrap = nullptr;
   c->destroyed = true;
   c->magic = 0;
-  if (old >= 0) (void)hipSetDevice(old);
   delete c;
   return ncclSuccess;
 }
@@ -1067,18 +1064,15 @@ VCCL_EXPORT ncclResult_t ncclCommSplit(ncclComm_t comm, int color, int key, nccl
         members.size());
   if (members.empty()) return ncclSuccess;
   const int newRank = (int)(std::find(members.begin(), members.end(), me) - members.begin());
-  int old = -1;
-  HIPCHECK(hipGetDevice(&old));
-  if (old != comm->device) HIPCHECK(hipSetDevice(comm->device));
+  DeviceGuard dev(comm->device);
+  HIPCHECK(dev.status);
   // config NULL: the parent's (copyCommConfig, src/init.cc:2160-2161) — its
   // CTA bounds, so the child gets the parent's channel count
   ncclConfig_t inherit = NCCL_CONFIG_INITIALIZER;
   inherit.minCTAs = comm->minCTAs;
   inherit.maxCTAs = comm->maxCTAs;
-  const ncclResult_t r = comm_init_rank(newcomm, (int)members.size(), &ids[members[0]], newRank, comm->device,
-                                        config ? config : &inherit);
-  if (old != comm->device) (void)hipSetDevice(old);
-  return r;
+  return comm_init_rank(newcomm, (int)members.size(), &ids[members[0]], newRank, comm->device,
+                        config ? config : &inherit);
 }
 
 VCCL_EXPORT ncclResult_t ncclCommInitAll(ncclComm_t* comms, int ndev, const int* devlist) {
@@ -1127,12 +1121,8 @@ VCCL_EXPORT ncclResult_t ncclCommInitAll(ncclComm_t* comms, int ndev, const int*
 // completed when it returns — its own launches, not the whole device.
 VCCL_EXPORT ncclResult_t ncclCommFinalize(ncclComm_t comm) {
   NCCLCHECK(comm_check(comm, "ncclCommFinalize"));
-  int old = -1;
-  (void)hipGetDevice(&old);
-  (void)hipSetDevice(comm->device);
-  const ncclResult_t r = comm_wait_own_launches(comm);
-  if (old >= 0) (void)hipSetDevice(old);
-  return r;
+  DeviceGuard dev(comm->device, /*ignoreQuery=*/true);
+  return comm_wait_own_launches(comm);
 }
 
 VCCL_EXPORT ncclResult_t ncclCommDestroy(ncclComm_t comm) {
@@ -1231,13 +1221,11 @@ VCCL_EXPORT ncclResult_t vcclCommSetFences(ncclComm_t comm, int useFences) {
   NCCLCHECK(comm_check(comm, "vcclCommSetFences"));
   if (useFences != 0 && useFences != 1) return ncclInvalidArgument;
   if (comm->nRanks < 2 || !comm->devComm) return ncclSuccess;
-  int old = -1;
-  (void)hipGetDevice(&old);
-  HIPCHECK(hipSetDevice(comm->device));
+  DeviceGuard dev(comm->device, /*ignoreQuery=*/true);
+  HIPCHECK(dev.status);
   NCCLCHECK(comm_wait_own_launches(comm));
   HIPCHECK(hipMemcpy((char*)comm->devComm + offsetof(DevComm, useFences), &useFences, sizeof(int),
                      hipMemcpyHostToDevice));
-  if (old >= 0) (void)hipSetDevice(old);
   return ncclSuccess;
 }
 
@@ -1256,15 +1244,13 @@ VCCL_EXPORT ncclResult_t vcclCommDebugSetEpochs(ncclComm_t comm, uint32_t llEpoc
                                                 uint32_t directEpoch) {
   NCCLCHECK(comm_check(comm, "vcclCommDebugSetEpochs"));
   if (comm->nRanks < 2 || !comm->devComm) return ncclSuccess;
-  int old = -1;
-  (void)hipGetDevice(&old);
-  HIPCHECK(hipSetDevice(comm->device));
+  DeviceGuard dev(comm->device, /*ignoreQuery=*/true);
+  HIPCHECK(dev.status);
   NCCLCHECK(comm_wait_own_launches(comm));
   HIPCHECK(hipMemcpy((char*)comm->devComm + offsetof(DevComm, llEpoch), &llEpoch, sizeof(uint32_t),
                      hipMemcpyHostToDevice));
   HIPCHECK(hipMemcpy((char*)comm->devComm + offsetof(DevComm, dEpoch), &directEpoch,
                      sizeof(uint32_t), hipMemcpyHostToDevice));
-  if (old >= 0) (void)hipSetDevice(old);
   return ncclSuccess;
 }
 

@@ -1,0 +1,41 @@
+// What launch.cc offers the API file (enqueue.cc): a checked call as a Task,
+// its launch alone or as part of a group, and the path queries.
+#pragma once
+#include <vector>
+
+#include "core.h"
+#include "plan.h"
+
+#pragma GCC visibility push(hidden)  // internal, as plan.h
+namespace vccl {
+
+struct Task {
+  int coll;
+  const void* sendbuff;
+  void* recvbuff;
+  size_t count;
+  ncclDataType_t datatype;
+  int devOp;
+  uint64_t arg;
+  const void* argPtr;  // ncclScalarDevice PreMulSum scalar
+  int root;            // broadcast / reduce
+  ncclComm* comm;
+  hipStream_t stream;
+  // Set by the group planner (launch_planned): this call's partition inside
+  // its group's VCCL plan, under the protocol of the path its aggregate took;
+  // otherwise the call is planned alone (cbd_schedule).
+  bool planned;
+  CbdPlan plan;
+};
+
+// The one place that reads a comm into the planner's thresholds.
+AlgoPolicy policy_of(const ncclComm* c);
+// The kernel element type of a call (K_U8 for the byte copies), -1: no kernel.
+int kernel_type_of_call(int coll, int devOp, ncclDataType_t datatype);
+// One call outside a group.
+ncclResult_t launch_task(const Task& t);
+// A group's calls, at the outermost ncclGroupEnd.
+ncclResult_t launch_group(std::vector<Task>& tasks);
+
+}  // namespace vccl
+#pragma GCC visibility pop

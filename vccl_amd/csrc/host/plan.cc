@@ -1,0 +1,432 @@
+// VCCL's planner restated for one node (plan.h): the op encoding, the cbd
+// channel partition, the path selection and the multi-task group plan.
+#include "plan.h"
+
+#include <algorithm>
+#include <cstring>
+
+#include "../../../include/vccl_device.h"
+#include "../device/coll_types.hpp"
+
+namespace vccl {
+
+// The device op codes (vcclDevRedOp_t = ncclDevRedOp_t, device.h:34-38; the
+// kernels' OP_* of dispatch.hpp are the same values, tied in launch.cc).
+enum : int { OP_SUM = vcclDevSum, OP_PROD = vcclDevProd, OP_MINMAX = vcclDevMinMax, OP_PREMULSUM = vcclDevPreMulSum,
+             OP_SUMPOSTDIV = vcclDevSumPostDiv };
+
+int type_size(ncclDataType_t t) {
+  switch (t) {
+    case ncclInt8: case ncclUint8: case ncclFloat8e4m3: case ncclFloat8e5m2: return 1;
+    case ncclFloat16: case ncclBfloat16: return 2;
+    case ncclInt32: case ncclUint32: case ncclFloat32: return 4;
+    case ncclInt64: case ncclUint64: case ncclFloat64: return 8;
+    default: return -1;
+  }
+}
+
+// __nv_cvt_float_to_fp8(f, __NV_SATFINITE, fmt) for the avg scalar
+// (enqueue.cc:2265-2272): RN-even to `mbits` mantissa bits with exponent bias
+// `bias`, magnitudes past max finite saturate, NaN -> 0x7f.
+static uint8_t f32_to_fp8_satfinite(float f, int mbits, int bias, uint32_t maxCode) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  const uint32_t s = (u >> 24) & 0x80u, a = u & 0x7fffffffu;
+  if (a > 0x7f800000u) return 0x7fu;
+  const int e = (int)(a >> 23) - 127, emin = 1 - bias;
+  if (a == 0) return (uint8_t)s;
+  const uint64_t m = (a & 0x7fffffu) | 0x800000u;
+  const int shift = (e >= emin ? e : emin) - mbits - e + 23;  // >= 23 - mbits
+  uint64_t q = 0;
+  if (shift < 40) {
+    q = m >> shift;
+    const uint64_t rem = m & ((1ull << shift) - 1), half = 1ull << (shift - 1);
+    if (rem > half || (rem == half && (q & 1))) q++;
+  }
+  uint64_t code = e >= emin ? ((uint64_t)(e + bias) << mbits) + (q - (1ull << mbits)) : q;
+  if (e > 15 + bias || code > maxCode) code = maxCode;
+  return (uint8_t)(s | code);
+}
+
+// hostToDevRedOp (enqueue.cc:2217-2310) for built-in ops.
+ncclResult_t host_to_dev_redop(ncclRedOp_t op, ncclDataType_t dt, int nRanks, int* devOp, uint64_t* arg) {
+  const int nbits = 8 * type_size(dt);
+  if (nbits <= 0) return ncclInvalidArgument;
+  const uint64_t allBits = ~0ull >> (64 - nbits);
+  const uint64_t signBit = allBits ^ (allBits >> 1);
+  const bool isSigned = dt == ncclInt8 || dt == ncclInt32 || dt == ncclInt64;
+  *arg = 0;
+  switch ((int)op) {
+    case ncclSum: *devOp = OP_SUM; return ncclSuccess;
+    case ncclProd: *devOp = OP_PROD; return ncclSuccess;
+    case ncclMin:
+    case ncclMax:
+      *devOp = OP_MINMAX;
+      if (isSigned) *arg ^= signBit;
+      if (op == ncclMax) *arg ^= allBits;
+      return ncclSuccess;
+    case ncclAvg:
+      switch ((int)dt) {
+        case ncclInt8: case ncclInt32: case ncclInt64:
+        case ncclUint8: case ncclUint32: case ncclUint64:
+          *devOp = OP_SUMPOSTDIV;
+          *arg = ((uint64_t)nRanks << 1) | (isSigned ? 1 : 0);
+          return ncclSuccess;
+        case ncclFloat16: {
+          *devOp = OP_PREMULSUM;
+          _Float16 h = (_Float16)(float)(1.0 / nRanks);
+          uint16_t b;
+          memcpy(&b, &h, 2);
+          *arg = b;
+          return ncclSuccess;
+        }
+        case ncclBfloat16: {
+          *devOp = OP_PREMULSUM;
+          __bf16 h = (__bf16)(float)(1.0 / nRanks);
+          uint16_t b;
+          memcpy(&b, &h, 2);
+          *arg = b;
+          return ncclSuccess;
+        }
+        case ncclFloat32: {
+          *devOp = OP_PREMULSUM;
+          float f = (float)(1.0 / nRanks);
+          uint32_t b;
+          memcpy(&b, &f, 4);
+          *arg = b;
+          return ncclSuccess;
+        }
+        case ncclFloat64: {
+          *devOp = OP_PREMULSUM;
+          double d = 1.0 / nRanks;
+          memcpy(arg, &d, 8);
+          return ncclSuccess;
+        }
+        case ncclFloat8e4m3:
+          *devOp = OP_PREMULSUM;
+          *arg = f32_to_fp8_satfinite((float)(1.0 / nRanks), 3, 7, 0x7eu);
+          return ncclSuccess;
+        case ncclFloat8e5m2:
+          *devOp = OP_PREMULSUM;
+          *arg = f32_to_fp8_satfinite((float)(1.0 / nRanks), 2, 15, 0x7bu);
+          return ncclSuccess;
+      }
+      return ncclInvalidArgument;
+  }
+  return ncclInvalidArgument;
+}
+
+// VCCL's channel partition of ring collectives: the host side of
+// scheduleCollTasksToPlan (enqueue.cc:518-769) with the ring channel tuning
+// of topoGetAlgoInfo (:1902-1925) and calcCollChunking's RING chunk
+// (:2027-2032, 2093), so every element lands on the same channel and the same
+// chunk of the same loop as in VCCL — hence the same ring and fold order.
+// `count` / `eltSize` are already AG-rewritten to bytes.  Restated for the
+// tests in oracle/vccl_sched.py.
+//
+// proto: kProtoSimple or kProtoLL128.  stepBytes: that protocol's FIFO step
+// (buffSize / NCCL_STEPS).  nThreads: maxThreads[RING][proto] — NCCL_NTHREADS
+// for SIMPLE (the ring kernel's own block size here, comm->nThreads),
+// NCCL_LL128_NTHREADS (640) for LL128 (tuning.cc:198-211).
+static int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
+int64_t traffic_per_byte(int coll, int nRanks) {  // ncclFuncTrafficPerByte (enqueue.cc:67-74)
+  return coll == kAllReduce ? 2 : coll == kBroadcast || coll == kReduce ? 1 : nRanks;
+}
+
+// nMaxChannels of a task (or of an aggregate of tasks, ncclPrepareTasks):
+// the ring / tree channel tuning on nBytes = eltSize * ncclFuncMaxSendRecvCount
+// (enqueue.cc:1955, 1921-1924); thread thresholds (comm.h:38-40,
+// tuning.cc:489-493) SIMPLE 64, LL128 8, LL 8 — times nRanks for the ring's
+// LL (reduce-scatter / all-gather), not for the all-reduce's LL, which VCCL
+// runs on its tree.  nThreads: maxThreads of the protocol (tuning.cc:198-211:
+// NCCL_NTHREADS for SIMPLE and LL, NCCL_LL128_NTHREADS for LL128).
+int ring_nmax_channels(int coll, int64_t count, int64_t eltSize, int nRanks, int commChannels,
+                       int proto, int64_t nThreads) {
+  const int64_t threshold = proto == kProtoSimple ? 64
+                            : proto == kProtoLL128 || coll == kAllReduce ? 8 : 8 * (int64_t)nRanks;
+  // ncclFuncMaxSendRecvCount (enqueue.h:36-38): RS / AG move n blocks
+  const int64_t nBytes =
+      eltSize * (coll == kReduceScatter || coll == kAllGather ? (int64_t)nRanks * count : count);
+  int64_t nc = commChannels;
+  while (nBytes < nc * nThreads * threshold && nc >= 2) nc--;
+  return (int)nc;
+}
+
+// The cbd cell split of one task at the cursor (enqueue.cc:597-644; LL
+// counts its traffic 4x, :599), then the cursor advanced past it (:667-681).
+CbdPlan cbd_place(PlanCursor& pc, int coll, int64_t count, int64_t eltSize, int nRanks, int proto, int64_t stepBytes) {
+  const bool ll128 = proto == kProtoLL128, ll = proto == kProtoLL;
+  const uint64_t tpb = (uint64_t)traffic_per_byte(coll, nRanks) * (ll ? 4 : 1);
+  const uint64_t cellSize = (uint64_t)div_up(div_up(kMinTraffic, tpb), 16) * 16;
+  const uint64_t eltsPerCell = cellSize / (uint64_t)eltSize;
+  const uint64_t cells = (uint64_t)div_up(count * eltSize, (int64_t)cellSize);
+  const uint64_t trafficPerElement = (uint64_t)eltSize * tpb;
+  const uint64_t trafficPerCell = cellSize * tpb;
+  const uint64_t tpc = pc.trafficPerChannel;
+  uint64_t cellsPerChannel = std::min(cells, (tpc + trafficPerCell - 1) / trafficPerCell);
+  uint64_t cellsLo;
+  if (pc.channelId + 1 == pc.nMax) cellsLo = cells;  // on the last channel everything goes to "lo"
+  else cellsLo = std::min(cells, (tpc - pc.currentTraffic + trafficPerCell - 1) / trafficPerCell);
+  int nMid = (int)((cells - cellsLo) / cellsPerChannel);
+  uint64_t cellsHi = (cells - cellsLo) % cellsPerChannel;
+  int nCh = (cellsLo != 0 ? 1 : 0) + nMid + (cellsHi != 0 ? 1 : 0);
+  if (pc.nMax < pc.channelId + nCh) {  // overflowed the available channels
+    nMid = pc.nMax - pc.channelId - 2;
+    cellsPerChannel = (cells - cellsLo) / (uint64_t)(nMid + 1);
+    cellsHi = cellsPerChannel + (cells - cellsLo) % (uint64_t)(nMid + 1);
+  }
+  if (cellsHi == 0 && nMid != 0) {
+    cellsHi = cellsPerChannel;
+    nMid -= 1;
+  }
+  if (cellsLo == 0) {  // least channel skipped: the next one becomes the least
+    pc.channelId += 1;
+    if (nMid == 0) {
+      cellsLo = cellsHi;
+      cellsHi = 0;
+    } else {
+      cellsLo = cellsPerChannel;
+      nMid -= 1;
+    }
+  }
+  CbdPlan p{};
+  p.countMid = nMid != 0 ? (int64_t)(cellsPerChannel * eltsPerCell) : 0;
+  p.countLo = (int64_t)(cellsLo * eltsPerCell);
+  p.countHi = (int64_t)(cellsHi * eltsPerCell);
+  (p.countHi != 0 ? p.countHi : p.countLo) -= (int64_t)(cells * eltsPerCell) - count;
+  nCh = (p.countLo != 0 ? 1 : 0) + nMid + (cellsHi != 0 ? 1 : 0);
+  p.channelLo = pc.channelId;
+  p.channelHi = pc.channelId + nCh - 1;
+  // RING chunk (calcCollChunking, enqueue.cc:2027-2032, 2093): SIMPLE =
+  // chunkSteps (4) FIFO steps of buffSize / NCCL_STEPS (= one slot here);
+  // LL128 = one step, 15/16 of it data; LL = half a step; rounded down to
+  // the protocol grain (device.h:290-295: SIMPLE 512, LL128 1920, LL 16);
+  // independent of size.
+  // (broadcast / reduce: BROADCAST_CHUNKSTEPS / REDUCE_CHUNKSTEPS 1,
+  // collectives.h:23-26)
+  const int64_t grain = ll128 ? 1920 : ll ? 16 : 512;
+  const int64_t chunkBytes =
+      ll128 ? stepBytes / 16 * 15 : ll ? stepBytes / 2 : (coll == kBroadcast || coll == kReduce ? 1 : 4) * stepBytes;
+  const int64_t chunkElts = chunkBytes / grain * grain / eltSize;
+  p.chunkLo = p.chunkMid = p.chunkHi = chunkElts;
+  // advance the cursor (enqueue.cc:667-681)
+  if (p.countHi != 0) {
+    pc.channelId += nCh - 1;
+    pc.currentTraffic = cellsHi * eltsPerCell * trafficPerElement;
+  } else if (nMid != 0) {
+    pc.channelId += nCh;
+    pc.currentTraffic = 0;
+  } else {
+    pc.currentTraffic += cellsLo * eltsPerCell * trafficPerElement;
+  }
+  if (pc.currentTraffic >= tpc && pc.channelId + 1 != pc.nMax) {
+    pc.channelId += 1;
+    pc.currentTraffic = 0;
+  }
+  return p;
+}
+
+// A plan holding one ring collective (a call outside a group).
+CbdPlan cbd_schedule(int coll, int64_t count, int64_t eltSize, int nRanks, int commChannels,
+                     int proto, int64_t stepBytes, int64_t nThreads) {
+  const int nc = ring_nmax_channels(coll, count, eltSize, nRanks, commChannels, proto, nThreads);
+  const uint64_t traffic = std::max<uint64_t>(
+      kMinTraffic, (uint64_t)(count * eltSize) * traffic_per_byte(coll, nRanks) * (proto == kProtoLL ? 4 : 1));
+  PlanCursor pc{std::max<uint64_t>(kMinTraffic, traffic / (uint64_t)std::min(nc, commChannels)), 0, 0,
+                commChannels};
+  return cbd_place(pc, coll, count, eltSize, nRanks, proto, stepBytes);
+}
+
+// ---------------------------------------------------------------- paths
+// The path of a bucket (VCCL's topoGetAlgoInfo, enqueue.cc:1805-1945, reduced
+// to one node over a full xGMI mesh): buckets up to the LL threshold take the
+// one-hop LL path, the LL128 window (when enabled) the LL128 ring, up to the
+// direct threshold the direct path (all-reduce two-shot, reduce-scatter /
+// all-gather one-hop), larger ones the SIMPLE ring.  NCCL_ALGO / NCCL_PROTO
+// force one: Ring/SIMPLE -> ring; Tree/LL -> LL where it fits; Direct -> direct
+// where the mesh has it; LL128 -> the LL128 ring where its FIFOs exist;
+// anything that does not fit falls through to the ring.  A pure function of
+// the comm's thresholds (AlgoPolicy), so the group planner can ask it for an
+// aggregate of calls as ncclPrepareTasks asks getAlgoInfo (enqueue.cc:398).
+// count in elements of eltSize (all-gather: any element type, or bytes)
+int select_algo(const AlgoPolicy& p, int coll, int64_t eltSize, int64_t count) {
+  if (p.nRanks < 2 || p.algoForce == 1) return kAlgoRing;
+  // NCCL_PROTO=LL128 (or vcclCommSetAlgo): the LL128 ring for every size
+  if (p.algoForce == 4) return p.ll128 ? kAlgoRingLL128 : kAlgoRing;
+  if (coll == kBroadcast || coll == kReduce) {  // the rings of broadcast.h / reduce.h: SIMPLE or the LL128 window
+    const uint64_t bytes = (uint64_t)(count * eltSize);
+    return p.ll128 && p.ll128Max && bytes >= p.ll128Min && bytes <= p.ll128Max ? kAlgoRingLL128 : kAlgoRing;
+  }
+  const uint64_t block = (uint64_t)(count * eltSize);
+  // Reduce-scatter / all-gather: one rank's block must fit an LL slot; the
+  // thresholds are on the whole bucket (n blocks), as the reference's tuner
+  // sizes RS / AG (enqueue.cc:1955, ncclFuncMaxSendRecvCount).
+  const uint64_t bytes = coll == kAllReduce ? block : block * (uint64_t)p.nRanks;
+  const bool llFits = coll == kAllReduce
+                          ? p.llSlotBytes > 0 && bytes <= p.llMax
+                          : p.llSlotBytes > 0 && p.nRanks <= kOrderMaxRanks &&
+                                block <= (uint64_t)p.llSlotBytes && bytes <= p.llRsAgMax;
+  const bool directFits = p.direct && bytes <= (coll == kAllReduce ? p.directMax : p.directRsAgMax);
+  if (p.algoForce == 2) return llFits ? kAlgoLL : kAlgoRing;
+  // Forced direct: any bucket the inbox can stream (the size threshold only
+  // steers the automatic choice); needs every peer's inbox mapped (no net
+  // peers)
+  if (p.algoForce == 3) return p.direct && p.nRanks <= kDirectMaxRanks ? kAlgoDirect : kAlgoRing;
+  if (llFits) return kAlgoLL;
+  // the LL128 ring over its window (the bucket, as the tuner sizes it), ahead
+  // of the direct path
+  if (p.ll128 && p.ll128Max && bytes >= p.ll128Min && bytes <= p.ll128Max) return kAlgoRingLL128;
+  if (directFits) return kAlgoDirect;
+  return kAlgoRing;
+}
+// The protocol VCCL runs a path's calls with: the one-hop LL stands in for
+// VCCL's LL (tree for the all-reduce, ring otherwise), the direct path for a
+// SIMPLE ring call.
+int proto_of_algo(int algo) {
+  return algo == kAlgoLL ? kProtoLL : algo == kAlgoRingLL128 ? kProtoLL128 : kProtoSimple;
+}
+
+// ---------------------------------------------------------------- group plan
+// VCCL's plan for a group's collectives of one comm:
+//  * taskAppend: trafficBytes = count * eltSize * trafficPerByte, inserted
+//    into the size sorter (enqueue.cc:2405-2413; comm.h:294-343: 81 bins of
+//    u32fpEncode(min(bytes, 1 GiB) >> 10, 2 bits) in descending size, LIFO
+//    within a bin, bitops.h:252-262);
+//  * ncclPrepareTasks (enqueue.cc:352-437): the sorted list binned by
+//    (func, devOp, type) in LIFO order — each bin size-ascending, bins in
+//    order of first appearance; runs within 4x of the run's first
+//    trafficBytes aggregated; the path (select_algo, standing in for
+//    getAlgoInfo's tuner) and nMaxChannels chosen on the aggregate's count
+//    and given to every member; an LL member's trafficBytes x4 (:418);
+//  * scheduleCollTasksToPlan (enqueue.cc:518-769): trafficPerChannel = the
+//    plan's traffic / min(sum nMaxChannels, comm channels), each task placed
+//    at the running channelId / currentTraffic under its protocol; a task
+//    that would overflow the kernel-argument budget (testBudget :278-286:
+//    16-byte work batches within 4 KiB - 32 B of kernel arguments, 96-byte
+//    works within half the 1 MiB work FIFO; batches counted as
+//    addWorkBatchToPlan :91-156 does, per device function and protocol)
+//    starts the next plan.
+// No policy: every call RING / SIMPLE.  Restated for the tests in
+// oracle/vccl_sched.py (plan_schedule).
+// group_task_of: all-gather / broadcast are int8 copies (enqueue.cc:2400-2404), keyed as such.
+GroupTask group_task_of(int coll, size_t count, ncclDataType_t datatype, int devOp, int kernelType) {
+  const bool ag = is_copy_coll(coll);
+  const CallSize sz = call_size(coll, count, datatype);
+  const int key = (coll * 16 + (ag ? (int)OP_SUM : devOp)) * 32;
+  return GroupTask{coll, sz.count, sz.eltSize, key + (ag ? (int)ncclInt8 : (int)datatype), key + kernelType};
+}
+uint32_t u32fp_encode(uint32_t x, int bitsPerPow2) {  // bitops.h:252-262
+  const int log2x = 31 - __builtin_clz(x | 1);
+  const uint32_t mantissa = x >> (log2x >= bitsPerPow2 ? log2x - bitsPerPow2 : 0) & ((1u << bitsPerPow2) - 1);
+  const uint32_t exponent = log2x >= bitsPerPow2 ? log2x - (bitsPerPow2 - 1) : 0;
+  return exponent << bitsPerPow2 | mantissa;
+}
+void group_plan(const std::vector<GroupTask>& ts, int nRanks, int commChannels, const PlanGeometry& geo,
+                const AlgoPolicy* pol, GroupPlanOut* out) {
+  const int n = (int)ts.size();
+  std::vector<uint64_t> traffic(n);
+  for (int i = 0; i < n; i++)
+    traffic[i] = (uint64_t)(ts[i].count * ts[i].eltSize) * traffic_per_byte(ts[i].coll, nRanks);
+  // the size sorter: bins in descending size, LIFO within a bin
+  constexpr int kBinCount = 1 + (30 - 10) * 4;
+  std::vector<std::vector<int>> bins(kBinCount);
+  for (int i = 0; i < n; i++) {
+    const uint32_t x = (uint32_t)(std::min<uint64_t>(traffic[i], 1ull << 30) >> 10);
+    bins[kBinCount - 1 - (int)u32fp_encode(x, 2)].push_back(i);
+  }
+  std::vector<int> sorted;
+  for (auto& b : bins) sorted.insert(sorted.end(), b.rbegin(), b.rend());
+  // (func, op, type) bins, LIFO, in order of first appearance
+  std::vector<int> keys;
+  std::vector<std::vector<int>> byKey;
+  for (int i : sorted) {
+    const size_t k = std::find(keys.begin(), keys.end(), ts[i].binKey) - keys.begin();
+    if (k == keys.size()) {
+      keys.push_back(ts[i].binKey);
+      byKey.emplace_back();
+    }
+    byKey[k].insert(byKey[k].begin(), i);
+  }
+  auto step_of = [&](int proto) {
+    return proto == kProtoLL ? kLLStepBytes : proto == kProtoLL128 ? geo.ll128StepBytes : geo.stepBytes;
+  };
+  std::vector<int> nMax(n), proto(n), queue;
+  out->algo.assign(n, kAlgoRing);
+  for (auto& lst : byKey) {
+    for (size_t a = 0; a < lst.size();) {
+      size_t e = a + 1;
+      int64_t aggCount = ts[lst[a]].count;
+      while (e < lst.size() && traffic[lst[e]] < 4 * traffic[lst[a]]) aggCount += ts[lst[e++]].count;
+      const GroupTask& h = ts[lst[a]];
+      const int algo = pol ? select_algo(*pol, h.coll, h.eltSize, aggCount) : kAlgoRing;
+      const int pr = proto_of_algo(algo);
+      const int nc = ring_nmax_channels(h.coll, aggCount, h.eltSize, nRanks, commChannels, pr,
+                                        pr == kProtoLL128 ? geo.ll128Threads : geo.nThreads);
+      for (size_t j = a; j < e; j++) {
+        nMax[lst[j]] = nc;
+        proto[lst[j]] = pr;
+        out->algo[lst[j]] = algo;
+        if (pr == kProtoLL) traffic[lst[j]] *= 4;
+      }
+      a = e;
+    }
+    queue.insert(queue.end(), lst.begin(), lst.end());
+  }
+  out->order = queue;
+  out->planOf.assign(n, -1);
+  out->cbd.assign(n, CbdPlan{});
+  constexpr int64_t kWorkBytes = 96, kBatchBytes = 16;   // sizeof ncclDevWorkColl / ncclDevWorkBatch
+  constexpr int64_t kInArgs = (4 << 10) - 32;            // workArgsBytes - sizeof(ncclDevKernelArgs)
+  constexpr int64_t kOutArgs = (1 << 20) / 2;            // workFifoBytes / 2
+  auto budget_ok = [&](int64_t nBatches, int64_t workBytes) {
+    const int64_t bb = nBatches * kBatchBytes;
+    return bb + workBytes <= kInArgs || (bb <= kInArgs && workBytes <= kOutArgs);
+  };
+  size_t head = 0;
+  for (int plan = 0; head < queue.size(); plan++) {
+    int nPlanColls = 0;
+    uint64_t tb = 0;
+    int nch = 0;
+    for (size_t q = head, wb = 0; q < queue.size(); q++) {
+      if (!budget_ok(div_up(nPlanColls, 4), (int64_t)wb + kWorkBytes)) break;
+      nPlanColls++;
+      wb += kWorkBytes;
+      tb += std::max<uint64_t>(kMinTraffic, traffic[queue[q]]);
+      nch = std::min(nch + nMax[queue[q]], commChannels);
+    }
+    PlanCursor pc{std::max<uint64_t>(kMinTraffic, tb / (uint64_t)std::max(nch, 1)), 0, 0, commChannels};
+    // per channel: the work batch being filled (addWorkBatchToPlan)
+    std::vector<int> lastFunc(commChannels, -1);
+    std::vector<int64_t> offsetBase(commChannels, 0), wipBytes(commChannels, 0);
+    int64_t nWorkBatches = 0, workBytes = 0;
+    while (nPlanColls != 0 && head < queue.size()) {
+      const int i = queue[head];
+      PlanCursor trial = pc;
+      const CbdPlan p = cbd_place(trial, ts[i].coll, ts[i].count, ts[i].eltSize, nRanks, proto[i],
+                                  step_of(proto[i]));
+      const int nChTask = p.channelHi - p.channelLo + 1;
+      if (!budget_ok(nWorkBatches + nChTask, workBytes + kWorkBytes)) break;  // the next plan
+      pc = trial;
+      const int func = ts[i].funcKey * 4 + proto[i];  // devFuncId: (func, op, type, algo, proto)
+      for (int c = p.channelLo; c <= p.channelHi && c < commChannels; c++) {
+        const bool fresh = lastFunc[c] < 0 || lastFunc[c] != func ||
+                           wipBytes[c] + kWorkBytes > 1024;  // NCCL_MAX_DEV_WORK_BATCH_BYTES
+        const int64_t off = fresh ? 0 : workBytes - offsetBase[c];
+        if (fresh || 63 * kWorkBytes < off) {
+          offsetBase[c] = workBytes;
+          if (fresh) wipBytes[c] = 0;
+          nWorkBatches++;
+        }
+        lastFunc[c] = func;
+        wipBytes[c] += kWorkBytes;
+      }
+      workBytes += kWorkBytes;
+      out->planOf[i] = plan;
+      out->cbd[i] = p;
+      head++;
+      nPlanColls--;
+    }
+  }
+}
+
+}  // namespace vccl

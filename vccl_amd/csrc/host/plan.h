@@ -1,0 +1,120 @@
+// The restatement of VCCL's planner (plan.cc): pure integer arithmetic on
+// plain structs — no runtime call, no communicator, no stream.  launch.cc
+// reads a comm into these inputs; the plan exports (enqueue.cc) and through
+// them the CPU parity tests (oracle/vccl_sched.py) pass explicit ones.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "../../../include/nccl.h"
+#include "../device/ring_types.hpp"
+
+#pragma GCC visibility push(hidden)  // internal: the library's exported symbols stay the C ABI's
+namespace vccl {
+
+// The values of vcclColl_t (vccl_ext.h) and of the launchers' kColl* codes
+// (ring_launch.hpp; tied in launch.cc).
+enum Coll { kAllReduce = 0, kReduceScatter = 1, kAllGather = 2, kBroadcast = 3, kReduce = 4 };
+// Byte-copy collectives: the host rewrites them as int8 (enqueue.cc:2400-2404).
+inline bool is_copy_coll(int coll) { return coll == kAllGather || coll == kBroadcast; }
+
+int type_size(ncclDataType_t t);
+
+// A call's (count, eltSize) as the planner takes them: the byte copies have
+// eltSize 1 and count in bytes.
+struct CallSize {
+  int64_t count, eltSize;
+};
+inline CallSize call_size(int coll, size_t count, ncclDataType_t datatype) {
+  const int64_t tsz = type_size(datatype);
+  return is_copy_coll(coll) ? CallSize{(int64_t)count * tsz, 1} : CallSize{(int64_t)count, tsz};
+}
+
+// One call's part of VCCL's channel partition (ncclDevWorkColl channelLo /
+// channelHi + cbd, device.h:258-287): channels [channelLo, channelHi] carry
+// parts of countLo / countMid... / countHi elements, moved in chunks of
+// chunkLo / chunkMid / chunkHi elements.
+struct CbdPlan {
+  int channelLo, channelHi;
+  int64_t countLo, countMid, countHi;
+  int64_t chunkLo, chunkMid, chunkHi;  // elements
+};
+// The eight words vcclRingPartition / vcclGroupPlan report a partition as.
+inline void cbd_words(const CbdPlan& p, int64_t* out) {
+  const int64_t v[8] = {p.channelLo, p.channelHi, p.countLo, p.countMid, p.countHi, p.chunkLo, p.chunkMid, p.chunkHi};
+  for (int i = 0; i < 8; i++) out[i] = v[i];
+}
+
+// The paths a call can take (select_algo).
+enum { kAlgoRing = 0, kAlgoLL = 1, kAlgoDirect = 2, kAlgoRingLL128 = 3 };
+
+ncclResult_t host_to_dev_redop(ncclRedOp_t op, ncclDataType_t dt, int nRanks, int* devOp, uint64_t* arg);
+
+constexpr uint64_t kMinTraffic = 16 << 10;  // MinTrafficPerChannel, enqueue.cc:528
+int64_t traffic_per_byte(int coll, int nRanks);
+int ring_nmax_channels(int coll, int64_t count, int64_t eltSize, int nRanks, int commChannels, int proto,
+                       int64_t nThreads);
+
+// The running channel position of a plan (scheduleCollTasksToPlan's
+// trafficPerChannel / channelId / currentTraffic, enqueue.cc:549-565).
+struct PlanCursor {
+  uint64_t trafficPerChannel;
+  int channelId;
+  uint64_t currentTraffic;
+  int nMax;  // nMaxChannels[kind] = comm->nChannels
+};
+
+// VCCL's LL step (the default LL buffer, init.cc:617: 8 lines x 512 threads
+// x NCCL_STEPS x 16 B, over NCCL_STEPS): only the chunk fields of an LL
+// task's plan use it, and the one-hop LL kernels ignore those.
+constexpr int64_t kLLStepBytes = 8 * 512 * 16;
+
+CbdPlan cbd_place(PlanCursor& pc, int coll, int64_t count, int64_t eltSize, int nRanks, int proto, int64_t stepBytes);
+CbdPlan cbd_schedule(int coll, int64_t count, int64_t eltSize, int nRanks, int commChannels, int proto,
+                     int64_t stepBytes, int64_t nThreads);
+
+// The thresholds select_algo decides on (a comm's: launch.cc policy_of).
+struct AlgoPolicy {
+  int nRanks = 1, algoForce = 0;
+  int64_t llSlotBytes = 0;                 // 0: no LL buffers
+  uint64_t llMax = 0, llRsAgMax = 0;
+  bool ll128 = false;                      // LL128 FIFOs mapped
+  uint64_t ll128Min = 0, ll128Max = 0;     // automatic LL128 window (max 0 = off)
+  bool direct = false;                     // every peer's inbox mapped
+  uint64_t directMax = 0, directRsAgMax = 0;
+};
+int select_algo(const AlgoPolicy& p, int coll, int64_t eltSize, int64_t count);
+int proto_of_algo(int algo);
+
+struct GroupTask {
+  int coll;
+  int64_t count, eltSize;  // AG in bytes
+  int binKey;              // (func, devOp, type): ncclPrepareTasks' bins
+  int funcKey;             // the device function (batches merge per function)
+};
+// A call as the group planner takes it.  kernelType: dispatch.hpp
+// kernel_type_of (K_U8 for a byte copy), passed in so no kernel header is
+// needed here.
+GroupTask group_task_of(int coll, size_t count, ncclDataType_t datatype, int devOp, int kernelType);
+
+struct PlanGeometry {
+  int64_t stepBytes, nThreads;            // SIMPLE: FIFO step, NCCL_NTHREADS
+  int64_t ll128StepBytes, ll128Threads;   // LL128: step, NCCL_LL128_NTHREADS
+};
+// VCCL's default LL128 geometry: NCCL_LL128_BUFFSIZE / NCCL_STEPS, NCCL_LL128_NTHREADS.
+constexpr struct {
+  int64_t stepBytes, nThreads;
+} kDefaultLL128{120 * 640 * 8, 640};
+struct GroupPlanOut {
+  std::vector<int> order;        // tasks in execution (plan) order
+  std::vector<int> planOf;       // per task: the plan (kernel) it lands in
+  std::vector<int> algo;         // per task: the path of its aggregate
+  std::vector<CbdPlan> cbd;      // per task, under the path's protocol
+};
+uint32_t u32fp_encode(uint32_t x, int bitsPerPow2);
+void group_plan(const std::vector<GroupTask>& ts, int nRanks, int commChannels, const PlanGeometry& geo,
+                const AlgoPolicy* pol, GroupPlanOut* out);
+
+}  // namespace vccl
+#pragma GCC visibility pop
