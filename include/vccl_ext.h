@@ -113,6 +113,10 @@
  *                     1 SIMPLE ring, 2 LL, 3 direct, 4 LL128 ring; *allowed =
  *                     bit 0 LL, bit 1 LL128, bit 2 SIMPLE, bit 3 direct.
  *                     ncclInvalidUsage for an unknown name, as at init.
+ *   vcclCommSetup      everything initialisation decides before it touches
+ *                     the GPU, for given ranks and environment: the channel
+ *                     count, step / slot, thresholds, buffer sizes, net peers,
+ *                     shared-GPU caps, ring tables (see its declaration).
  */
 #ifndef VCCL_EXT_H_
 #define VCCL_EXT_H_
@@ -171,6 +175,34 @@ ncclResult_t vcclGroupPlanEx(int nCalls, const int* colls, const size_t* counts,
                              const int* ops, int nRanks, int nChannels, const int64_t* geometry,
                              const int64_t* policy, int* algos, int* order, int* planOf, int64_t* cbd);
 ncclResult_t vcclAlgoSelection(const char* algo, const char* proto, int* force, int* allowed);
+/* What initialisation decides for rank `rank` of an nRanks communicator with
+ * CTA bounds minCTAs / maxCTAs (a comm's defaults: 1 / 128), from the
+ * environment as at init and each rank's identity pid[r], hostHash[r],
+ * busId[r], cuCount[r] (host only, nothing allocated).  Outputs:
+ *   setup[19]  nChannels, stepBytes, slotBytes, nThreads, algoForce,
+ *              algoAllowed, llMaxBytes, llLines, llRsAgMaxBytes,
+ *              directMaxBytes, directRsAgMaxBytes, directMaxBlocks,
+ *              dRegionBytes, ll128StepBytes, ll128Threads, ll128SlotBytes,
+ *              ll128MinBytes, ll128MaxBytes, shareBlockCap
+ *   sizes[5]   bytes of the FIFO, flag, LL, direct inbox and LL128 buffers
+ *              (0: not allocated)
+ *   flags[3]   a peer is reached through the net proxy; LL128 buffers are
+ *              wanted; the local LL128 buffer is dropped again (net)
+ *   netPeer[nRanks]           1 = reached through the net proxy
+ *   llChain[min(nRanks, 8)]   the LL fold chain (VCCL_LL_CHAIN)
+ *   ring[3]    (may be NULL) ring position, next and previous rank of `rank`
+ *              on channel `channel` (0 <= channel < nChannels; the count is
+ *              known only once the setup has run, so a refusal below comes
+ *              before ncclInvalidArgument for a channel out of range)
+ *   ringTables[129]  (may be NULL) nRings, rsOrder[8][8], ringAt[8][8] of the
+ *              device communicator
+ * Returns what init would for these inputs: ncclInvalidUsage for an unknown
+ * NCCL_ALGO / NCCL_PROTO name, two ranks on one GPU, more ranks of one process
+ * on a GPU than hardware queues, or a VCCL_LL_CHAIN that is no permutation. */
+ncclResult_t vcclCommSetup(int nRanks, int rank, int minCTAs, int maxCTAs, const int* pid,
+                           const uint64_t* hostHash, const int64_t* busId, const int* cuCount,
+                           int64_t* setup, int64_t* sizes, int* flags, int* netPeer, int* llChain,
+                           int channel, int* ring, int* ringTables);
 
 #ifdef __cplusplus
 }

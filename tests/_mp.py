@@ -60,6 +60,6 @@ def worker_env(env):
 def shared_channel_cap(nranks, default, cus):
     """The ring channels each rank gets at library defaults: the default,
     capped at 7/8 of a shared GPU's CUs over the ranks sharing it
-    (host/init.cc co-residency cap) — no cap at one rank per GPU."""
+    (host/setup.cc co-residency cap) — no cap at one rank per GPU."""
     k = ranks_per_device(nranks)
     return default if k <= 1 else min(default, max(1, cus * 7 // 8 // k))

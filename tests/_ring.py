@@ -4,7 +4,7 @@ expected result of a ring collective with the CPU oracle.
 The ring's element -> (channel, chunk) partition is VCCL's own (the device
 follows it, host/plan.cc cbd_schedule; the tests take it from the oracle's
 independent restatement, oracle/vccl_sched.py); the ring set per channel and
-the channel count mirror vccl_amd/csrc/host/init.cc.  The oracle's ring_fold
+the channel count mirror vccl_amd/csrc/host/setup.cc.  The oracle's ring_fold
 then reproduces the fold order element by element, so ring results are
 checked bit-exactly against VCCL's schedule on the same rings and channels —
 the two-shot direct all-reduce folds in that same order — and the one-shot
@@ -31,7 +31,7 @@ RINGS[6] = [[0, 1, 2, 3, 4, 5], [0, 5, 4, 3, 2, 1], [0, 2, 4, 1, 5, 3], [0, 3, 5
 def walecki(n):
     """Odd n = 2m+1: Walecki's m edge-disjoint Hamiltonian cycles of K_n (hub
     n-1, then k, k+1, k-1, k+2, ... mod 2m), each in both directions, rotated
-    to start at 0 — an independent restatement of host/init.cc."""
+    to start at 0 — an independent restatement of host/setup.cc."""
     m, h = (n - 1) // 2, n - 1
     out = []
     for k in range(m):
@@ -57,7 +57,7 @@ def ring_orders(n):
 
 
 def default_per_ring(n):
-    """The library's link-bound channel model (host/init.cc):
+    """The library's link-bound channel model (host/setup.cc):
     ceil(8 x 76.8 GB/s / (k x 40 GB/s)) channels per ring, k = rings per arc
     (2 for the 4-GPU set), within VCCL's MAXCHANNELS of 64 in total."""
     k = 2 if n == 4 else 1
@@ -66,7 +66,7 @@ def default_per_ring(n):
 
 
 def n_channels(n, per_ring=None, nch=None):
-    """Library default channel count (host/init.cc) unless overridden."""
+    """Library default channel count (host/setup.cc) unless overridden."""
     rings = ring_orders(n)
     if per_ring is None:
         per_ring = default_per_ring(n)
@@ -256,7 +256,7 @@ def direct_shard_elts(count, n, elt_size):
 
 
 def direct_chunk_elts(count, n, elt_size, chunk_bytes=16 << 20):
-    """Elements per chunk (host/init.cc inbox region, host/launch.cc launch_direct)."""
+    """Elements per chunk (host/setup.cc inbox region, host/launch.cc launch_direct)."""
     region = (chunk_bytes + n - 1) // n // 256 * 256 + 256
     unit = n * max(1, 16 // elt_size)
     return min(count, (region - 16) // elt_size * n // unit * unit)

@@ -53,7 +53,7 @@ def _run(n, geom):
             env["VCCL_FENCES"] = "1"
         # library defaults: nothing overridden — no channel, LL-grid or
         # direct-grid knob — so the co-residency caps that ranks sharing one
-        # GPU get (host/init.cc: 7/8 of the CUs / sharing ranks, for ring
+        # GPU get (host/setup.cc: 7/8 of the CUs / sharing ranks, for ring
         # channels and the LL / direct grids alike; the fix of the 8-rank
         # capture abort, 10b3277) are what runs
         for k in TEST_GEOM:

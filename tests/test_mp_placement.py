@@ -25,7 +25,7 @@ def test_rank_device(monkeypatch, ndev, n, devs, shared, per_dev):
 
 
 def test_shared_channel_cap(monkeypatch):
-    # host/init.cc: ranks sharing a GPU get 7/8 of its CUs / sharing ranks;
+    # host/setup.cc: ranks sharing a GPU get 7/8 of its CUs / sharing ranks;
     # one rank per GPU keeps the link-bound default
     monkeypatch.setattr(_mp, "device_count", lambda: 8)
     assert _mp.shared_channel_cap(8, 63, 256) == 63

@@ -156,7 +156,7 @@ def test_six_rank_rings_edge_disjoint():
 
 
 def test_library_ring_sets_equal_restatement():
-    """vcclRingOrders (host/init.cc) == tests/_ring.py for every n."""
+    """vcclRingOrders (host/setup.cc) == tests/_ring.py for every n."""
     from vccl_amd import nccl
     for n in range(1, 9):
         assert nccl.ring_orders(n) == _ring.ring_orders(n), n

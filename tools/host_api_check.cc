@@ -2,10 +2,12 @@
 // UndefinedBehaviorSanitizer (`make sanitize`; the reference's ASAN=1 /
 // UBSAN=1 build knobs, makefiles/common.mk:98-109).  No GPU call is made:
 // the planner exports (vcclGroupPlanEx, vcclRingPartition, vcclRingChunkOf,
-// vcclAlgoSelection), the op encoding, error strings and the argument checks
+// vcclAlgoSelection), the communicator setup (vcclCommSetup) under random
+// environments, the op encoding, error strings and the argument checks
 // that reject bad handles before any device work.  Random inputs from a fixed
 // seed; prints a summary and exits non-zero on an unexpected result (the
 // sanitizers abort on any memory or UB error).
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -124,6 +126,84 @@ int main() {
     EXPECT(r == ncclSuccess || r == ncclInvalidUsage);
     strs++;
   }
+  // the communicator setup (vcclCommSetup): random rank counts, peer
+  // identities that collide, knobs set to values and junk, random chains
+  const char* knobs[] = {"NCCL_NCHANNELS", "VCCL_CHANNELS_PER_RING", "NCCL_MIN_NCHANNELS", "NCCL_MAX_NCHANNELS",
+                         "NCCL_MAX_NRINGS", "NCCL_BUFFSIZE", "VCCL_SLOT_BYTES", "VCCL_SLICE_BYTES", "NCCL_NTHREADS",
+                         "VCCL_LL_THRESHOLD", "VCCL_LL_GROUP_BYTES", "VCCL_LL_RSAG_THRESHOLD",
+                         "VCCL_DIRECT_THRESHOLD", "VCCL_DIRECT_RSAG_THRESHOLD", "VCCL_DIRECT_MAX_BLOCKS",
+                         "VCCL_DIRECT_CHUNK_BYTES", "VCCL_LL128", "VCCL_LL128_ALLOC", "NCCL_LL128_BUFFSIZE",
+                         "NCCL_LL128_NTHREADS", "VCCL_LL128_MIN", "VCCL_LL128_MAX", "VCCL_NET_FORCE",
+                         "VCCL_NET_NCHANNELS", "VCCL_ALLOW_SHARED_DEVICE"};
+  const char* algos[] = {"Ring", "Tree", "Direct", "^Tree", "ring,tree", "Rnig", "7"};
+  const char* protos[] = {"LL", "LL128", "Simple", "^LL", "LL,LL128", "LL256", ""};
+  const char* junk[] = {"", "x", "-", "0x", "12abc", " 7", "1e9", "Ring", "LL128", "^LL", "Simple,LL"};
+  long setups = 0, refusals = 0;
+  for (int trial = 0; trial < 20000; trial++) {
+    for (const char* k : knobs) {
+      const int how = (int)(rng() % 8);
+      if (how >= 3) unsetenv(k);
+      else if (how == 2) setenv(k, junk[rng() % 11], 1);
+      else setenv(k, std::to_string(pick({-1, 0, 1, 2, 3, 4, 8, 64, 100, 4096, 5000, 65536, 262144, 1 << 20,
+                                          (1 << 22) + 1, 1ll << 31, 1ll << 40}) - (int64_t)(rng() % 2)).c_str(), 1);
+    }
+    if (rng() % 4) unsetenv("NCCL_ALGO");
+    else setenv("NCCL_ALGO", algos[rng() % 7], 1);
+    if (rng() % 4) unsetenv("NCCL_PROTO");
+    else setenv("NCCL_PROTO", protos[rng() % 7], 1);
+    const int n = (int)pick({1, 2, 3, 4, 6, 7, 8, 9, 64});
+    std::string chain;
+    for (int j = (int)(rng() % (n + 2)); j > 0 && rng() % 3; j--)
+      chain += (rng() % 9 ? std::to_string((int64_t)(rng() % (n + 1)) - (rng() % 16 == 0)) : std::string("z")) +
+               (rng() % 8 ? "," : "");
+    if (rng() % 2) {  // a permutation as often as not
+      chain.clear();
+      std::vector<int> perm(n);
+      for (int j = 0; j < n; j++) perm[j] = j;
+      std::shuffle(perm.begin(), perm.end(), rng);
+      for (int j = 0; j < n; j++) chain += std::to_string(perm[j]) + (j + 1 < n ? "," : "");
+    }
+    if (rng() % 3 == 0) setenv("VCCL_LL_CHAIN", chain.c_str(), 1);
+    else unsetenv("VCCL_LL_CHAIN");
+    std::vector<int> pid(n), cus(n), net(n, -1);
+    std::vector<uint64_t> host(n);
+    std::vector<int64_t> bus(n);
+    const int nPid = 1 + (int)(rng() % 3), nHost = 1 + (int)(rng() % 8 == 0), nBus = (int)pick({1, 2, n, n, n, 2 * n});
+    for (int r = 0; r < n; r++) {
+      pid[r] = 100 + (int)(rng() % nPid);
+      host[r] = rng() % nHost;
+      bus[r] = rng() % 16 ? r % nBus : (int64_t)(rng() % nBus);
+      cus[r] = (int)pick({-5, 0, 1, 64, 256, 304, 70000});
+    }
+    int64_t words[19], sizes[5];
+    int flags[3], chainOut[8], ring[3], tables[129];
+    const int rank = (int)(rng() % n), ch = (int)(rng() % 4);
+    const ncclResult_t r = vcclCommSetup(n, rank, (int)pick({1, 1, 4, 200}), (int)pick({128, 128, 2, 64}),
+                                         pid.data(), host.data(), bus.data(), cus.data(), words, sizes, flags,
+                                         net.data(), chainOut, ch, rng() % 2 ? ring : nullptr,
+                                         rng() % 2 ? tables : nullptr);
+    EXPECT(r == ncclSuccess || r == ncclInvalidUsage || r == ncclInvalidArgument);
+    setups++;
+    if (r != ncclSuccess) {
+      refusals++;
+      continue;
+    }
+    EXPECT(words[0] >= 0 && words[0] <= 128);  // nChannels within kMaxChannels
+    EXPECT((words[0] == 0) == (n == 1));
+    for (int q = 0; q < n; q++) EXPECT(net[q] == 0 || net[q] == 1);
+  }
+  for (const char* k : knobs) unsetenv(k);
+  for (const char* k : {"VCCL_LL_CHAIN", "NCCL_ALGO", "NCCL_PROTO"}) unsetenv(k);
+  {
+    int i1[1] = {0}, f[3], c8[8];
+    uint64_t h[1] = {0};
+    int64_t b[1] = {0}, w[19], s[5];
+    EXPECT(vcclCommSetup(0, 0, 1, 128, i1, h, b, i1, w, s, f, i1, c8, 0, nullptr, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclCommSetup(65, 0, 1, 128, i1, h, b, i1, w, s, f, i1, c8, 0, nullptr, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclCommSetup(1, 1, 1, 128, i1, h, b, i1, w, s, f, i1, c8, 0, nullptr, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclCommSetup(1, 0, 1, 128, nullptr, h, b, i1, w, s, f, i1, c8, 0, nullptr, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclCommSetup(1, 0, 1, 128, i1, h, b, i1, w, s, f, i1, c8, 0, nullptr, nullptr) == ncclSuccess);
+  }
   // op encoding, error strings, handle checks (no device work)
   for (int op = 0; op < 6; op++)
     for (int d = 0; d < 13; d++) {
@@ -145,7 +225,7 @@ int main() {
   const ncclResult_t ge = ncclGroupEnd();
   EXPECT(ge == ncclInvalidArgument);  // the group fails as a whole (enqueue.cc:2516)
   EXPECT(vcclBuildInfo() != nullptr);
-  printf("host_api_check: %ld groups (%ld calls), %ld partitions, %ld selection strings, %d failures\n", groups,
-         calls, parts, strs, g_fail);
+  printf("host_api_check: %ld groups (%ld calls), %ld partitions, %ld selection strings, %ld setups (%ld refused), "
+         "%d failures\n", groups, calls, parts, strs, setups, refusals, g_fail);
   return g_fail == 0 ? 0 : 1;
 }

@@ -19,7 +19,7 @@ namespace vccl {
 constexpr int kSteps = 8;            // NCCL_STEPS (device.h:24)
 constexpr int kMaxRanks = 64;
 // MAXCHANNELS (device.h:62) is 64 in the reference: the default channel
-// counts stay within it (kVcclMaxChannels, host/init.cc), so VCCL can run the
+// counts stay within it (kVcclMaxChannels, host/setup.cc), so VCCL can run the
 // same geometry.  NCCL_NCHANNELS / VCCL_CHANNELS_PER_RING may go up to 128
 // here: a channel is one workgroup on one CU, and on one GPU shared by
 // several ranks (the rehearsals) the ring is bound by its channels' copy rate

@@ -15,6 +15,7 @@
 
 #include "../../../include/nccl.h"
 #include "../device/ring_types.hpp"
+#include "setup.h"
 
 namespace vccl {
 struct DirectPeers;  // direct.hpp
@@ -75,13 +76,9 @@ uint32_t bootstrap_local_ip(Bootstrap* b);
 // proxy thread pair over TCP (proxy.cc).  Opaque here.
 struct NetProxy;
 
-// ----------------------------------------------------------------- rings
-// Ring orders for one node: for n in {2,4,8} the
-// arc-balanced ring sets over the fully connected xGMI mesh; otherwise the
-// identity ring.  Returns the list of rings (each a permutation of 0..n-1).
-std::vector<std::vector<int>> ring_orders(int nranks);
-
 // ----------------------------------------------------------------- comm
+// The buffers a rank publishes to its peers.
+enum { kMapFifo = 0, kMapFlag = 1, kMapLL = 2, kMapDirect = 3, kMapDirectFlag = 4, kMapLL128 = 5, kMapCount = 6 };
 struct PeerMap {               // what one rank published about itself
   int pid;
   int device;
@@ -90,18 +87,10 @@ struct PeerMap {               // what one rank published about itself
   uint32_t netIp;              // net proxy listener (network order), see proxy.cc
   uint16_t netPort;
   uint16_t cuCount;            // compute units of the device (co-residency cap of shared GPUs)
-  hipIpcMemHandle_t fifoHandle;
-  hipIpcMemHandle_t flagHandle;
-  hipIpcMemHandle_t llHandle;
-  hipIpcMemHandle_t dBufHandle;
-  hipIpcMemHandle_t dFlagHandle;
-  hipIpcMemHandle_t ll128Handle;
-  char* fifoPtr;               // raw pointers (valid only in the owner process)
-  char* flagPtr;
-  char* llPtr;
-  char* dBufPtr;
-  char* dFlagPtr;
-  char* ll128Ptr;
+  struct {
+    hipIpcMemHandle_t handle;  // for peers in other processes
+    char* ptr;                 // raw pointer (valid only in the owner process)
+  } buf[kMapCount];
 };
 
 struct UserRedOp {             // ncclRedOpCreatePreMulSum state (enqueue.cc:2528-2567)
@@ -114,45 +103,29 @@ struct UserRedOp {             // ncclRedOpCreatePreMulSum state (enqueue.cc:252
 
 }  // namespace vccl
 
-struct ncclComm {
+// The channel count, FIFO geometry, thresholds and caps are CommSetup's
+// (setup.h): decided by setup.cc, read as c->nChannels, c->llMaxBytes, ...
+struct ncclComm : vccl::CommSetup {
   uint64_t magic;
   int rank = 0, nRanks = 1, device = 0;
-  int nChannels = 0, slotBytes = 0, nThreads = 0;
-  int stepBytes = 0;  // VCCL's FIFO step: the partition / chunk unit (slotBytes = the FIFO slot)
   uint64_t* ringTrace = nullptr;  // VCCL_RING_TRACE: nChannels x ringTraceCap RingTraceRec
   int ringTraceCap = 0;
-  int shareBlockCap = 0;  // ranks sharing a GPU: workgroups per launch that stay co-resident (0 = no cap)
   vccl::Bootstrap* bootstrap = nullptr;
   // device resources
   char* fifoBuf = nullptr;     // nChannels * kSteps * slotBytes, uncached
   char* flagBuf = nullptr;     // nChannels * 2 flags * kFlagStride, uncached
   // one-shot LL all-reduce (ll.hpp): [2 parities][nRanks][llLines] 16 B lines
   char* llBuf = nullptr;
-  int llLines = 0;             // lines per (parity, source) slot = llMaxBytes / 8
-  size_t llMaxBytes = 0;       // largest all-reduce carried by LL
   std::vector<char*> llPeer;   // every rank's LL buffer mapped into this process
   // LL128 ring (ring.hpp prim_ll128): nChannels x kSteps slots of
-  // ll128SlotBytes, uncached; VCCL's LL128 partition and chunk
-  // (ll128ChunkBytes of data per step, enqueue.cc:2027-2032) and thread count
-  // (NCCL_LL128_NTHREADS, tuning.cc:198-211) for the channel tuning.
+  // ll128SlotBytes, uncached
   char* ll128Buf = nullptr;
-  int64_t ll128SlotBytes = 0;
-  int64_t ll128StepBytes = 0;  // NCCL_LL128_BUFFSIZE / NCCL_STEPS (init.cc:617-633)
-  int ll128Threads = 640;
-  size_t ll128MinBytes = 0, ll128MaxBytes = 0;  // automatic LL128 window (0 = off)
   // two-shot direct all-reduce (direct.hpp): inbox [2 phases][nRanks][dRegionBytes]
   char* dBuf = nullptr;
   char* dFlags = nullptr;      // kDirectFlagBytes of epoch flags
-  size_t directMaxBytes = 0;   // largest all-reduce carried by the direct path
-  size_t llRsAgMaxBytes = 0;   // largest RS / AG bucket (n blocks) on the one-hop LL path
-  size_t directRsAgMaxBytes = 0;  // ... and on the one-hop direct path
-  int64_t dRegionBytes = 0;
-  int directMaxBlocks = 0;
   vccl::DirectPeers* dPeers = nullptr;  // device-resident peer table
   vccl::NetProxy* net = nullptr;  // inter-node ring connections (proxy.cc)
   int netListenFd = -1;        // proxy listener, open from init until connections are made
-  int algoForce = 0;           // NCCL_ALGO/NCCL_PROTO: 0 auto, 1 ring/SIMPLE, 2 tree/LL, 3 direct, 4 LL128 ring
-  int algoAllowed = 15;        // paths the NCCL_ALGO / NCCL_PROTO lists leave (init.cc algo_proto_select)
   vccl::DevComm* devComm = nullptr;
   vccl::DevChannel* devChannels = nullptr;
   volatile int* abortFlag = nullptr;  // host pinned, mapped

@@ -1,0 +1,96 @@
+// A communicator's setup as arithmetic (setup.cc): the channel count, FIFO
+// geometry, path thresholds and buffer sizes from (nRanks, CTA bounds) and the
+// environment; what the exchanged peer identities switch off or cap; the ring
+// tables of a rank.  No runtime call, no communicator, no stream — init.cc
+// applies the results, vcclCommSetup (vccl_ext.h) shows them to the CPU tests.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "../../../include/nccl.h"
+#include "../device/ring_types.hpp"
+
+namespace vccl {
+
+// Ring orders for one node: for n in {2,4,8} the
+// arc-balanced ring sets over the fully connected xGMI mesh; Walecki's rings
+// for odd n, two Hamiltonian cycles both ways for 6; otherwise the
+// identity ring.  Returns the list of rings (each a permutation of 0..n-1).
+std::vector<std::vector<int>> ring_orders(int nranks);
+// NCCL_ALGO / NCCL_PROTO lists -> the forced path and the allowed ones
+// (vcclAlgoSelection, vccl_ext.h).
+ncclResult_t algo_proto_select(const char* algo, const char* proto, int* force, int* allowed);
+
+#pragma GCC visibility push(hidden)  // internal: the library's exported symbols stay as they were
+
+// The fields of ncclComm (core.h, which derives from this) that the setup
+// decides.  vcclCommSetup reports them in this order.
+struct CommSetup {
+  int nChannels = 0;
+  int stepBytes = 0;  // VCCL's FIFO step: the partition / chunk unit (slotBytes = the FIFO slot)
+  int slotBytes = 0;
+  int nThreads = 0;
+  int algoForce = 0;     // NCCL_ALGO/NCCL_PROTO: 0 auto, 1 ring/SIMPLE, 2 tree/LL, 3 direct, 4 LL128 ring
+  int algoAllowed = 15;  // paths the NCCL_ALGO / NCCL_PROTO lists leave (algo_proto_select)
+  size_t llMaxBytes = 0;      // largest all-reduce carried by LL
+  int llLines = 0;            // lines per (parity, source) slot = llMaxBytes / 8
+  size_t llRsAgMaxBytes = 0;  // largest RS / AG bucket (n blocks) on the one-hop LL path
+  size_t directMaxBytes = 0;      // largest all-reduce carried by the direct path
+  size_t directRsAgMaxBytes = 0;  // largest RS / AG bucket on the one-hop direct path
+  int directMaxBlocks = 0;
+  int64_t dRegionBytes = 0;
+  // VCCL's LL128 partition and chunk (ll128ChunkBytes of data per step,
+  // enqueue.cc:2027-2032) and thread count (NCCL_LL128_NTHREADS,
+  // tuning.cc:198-211) for the channel tuning.
+  int64_t ll128StepBytes = 0;  // NCCL_LL128_BUFFSIZE / NCCL_STEPS (init.cc:617-633)
+  int ll128Threads = 640;
+  int64_t ll128SlotBytes = 0;
+  size_t ll128MinBytes = 0, ll128MaxBytes = 0;  // automatic LL128 window (0 = off)
+  int shareBlockCap = 0;  // ranks sharing a GPU: workgroups per launch that stay co-resident (0 = no cap)
+};
+
+// Bytes of the buffers a rank allocates (0 = none).  Sized for the channel
+// count before the net or shared-GPU caps; the LL buffer and the inbox exist
+// even when NCCL_ALGO / NCCL_PROTO drop their path from the automatic choice
+// (vcclCommSetAlgo may still pick it).
+struct SetupSizes {
+  size_t fifoBytes = 0, flagBytes = 0, llBytes = 0, inboxBytes = 0, ll128Bytes = 0;
+  bool wantLL128 = false;
+};
+// Everything one rank decides on its own, in the order the knobs have always
+// been read.  nChannels is 0 and nothing is sized at nRanks == 1.  Fails
+// with algo_proto_select's result.
+ncclResult_t setup_local(int nRanks, int minCTAs, int maxCTAs, CommSetup* s, SetupSizes* z);
+
+// What a rank publishes about where it runs (a PeerMap's identity fields).
+struct PeerId {
+  int pid;
+  uint64_t hostHash;
+  int64_t busId;
+  uint16_t cuCount;
+};
+inline uint16_t cu_count_of(int cus) { return (uint16_t)(cus < 1 ? 1 : cus > 65535 ? 65535 : cus); }
+struct MeshSetup {
+  std::vector<char> netPeer;  // per rank: reached through the net proxy
+  bool anyNet = false;
+  bool dropLL128 = false;     // free the local LL128 buffer: its ring is off
+};
+// What the peer table decides: net peers and what they switch off, the
+// channel caps, and the two refusals (ncclInvalidUsage).  Every rank
+// evaluates every pair / group of the same table, so all ranks agree.
+ncclResult_t setup_mesh(int rank, const std::vector<PeerId>& peers, CommSetup* s, MeshSetup* m);
+
+// DevComm::nRings / rsOrder / ringAt of `rank`.
+void ring_tables(const std::vector<std::vector<int>>& rings, int nRanks, int rank, DevComm* dc);
+// DevComm::llChain from VCCL_LL_CHAIN (identity by default).
+ncclResult_t ll_chain(int nRanks, int8_t* chain);
+// `rank` on the ring of channel `ch`; ringRanks (may be null): the ring
+// rotated to start at `rank` (DevChannel::ringRanks).
+struct RingView {
+  int pos, next, prev;
+};
+RingView ring_view(const std::vector<std::vector<int>>& rings, int ch, int rank, int* ringRanks);
+
+#pragma GCC visibility pop
+}  // namespace vccl

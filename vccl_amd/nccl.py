@@ -43,6 +43,7 @@ EXPORTED = [
     "vcclCommLaunchStats", "vcclCommNetStats", "vcclCommSetFences", "vcclCommDebugSetEpochs",
     "vcclCommSetRingWave", "vcclCommRingTrace", "vcclCommGroupAlgos",
     "vcclRingPartition", "vcclRingChunkOf", "vcclRingOrders", "vcclGroupPlan", "vcclGroupPlanEx", "vcclAlgoSelection",
+    "vcclCommSetup",
     # rooted rings, split and debug reload
     "ncclReduce", "ncclBcast", "ncclBroadcast", "ncclCommSplit", "ncclResetDebugInit",
     # out of scope, exported so libnccl-linked binaries load: WARN + ncclInvalidUsage
@@ -153,6 +154,10 @@ def lib() -> ctypes.CDLL:
                                ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
         "vcclAlgoSelection": [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(c_int),
                               ctypes.POINTER(c_int)],
+        "vcclCommSetup": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(u64),
+                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_int64),
+                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                          ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -299,6 +304,43 @@ def algo_selection(algo: str | None, proto: str | None) -> tuple[int, int]:
                                   proto.encode() if proto is not None else None, ctypes.byref(f),
                                   ctypes.byref(a)), "vcclAlgoSelection")
     return f.value, a.value
+
+
+SETUP_FIELDS = ("nChannels", "stepBytes", "slotBytes", "nThreads", "algoForce", "algoAllowed", "llMaxBytes",
+                "llLines", "llRsAgMaxBytes", "directMaxBytes", "directRsAgMaxBytes", "directMaxBlocks",
+                "dRegionBytes", "ll128StepBytes", "ll128Threads", "ll128SlotBytes", "ll128MinBytes",
+                "ll128MaxBytes", "shareBlockCap")
+SETUP_SIZES = ("fifoBytes", "flagBytes", "llBytes", "inboxBytes", "ll128Bytes")
+
+
+def comm_setup(nranks: int, rank: int, peers, min_ctas: int = 1, max_ctas: int = 128,
+               channel: int | None = None) -> dict:
+    """vcclCommSetup: what init decides for `rank` of `nranks` under the
+    current environment (host only).  peers = [(pid, hostHash, busId,
+    cuCount)] per rank.  Returns SETUP_FIELDS and SETUP_SIZES by name (the
+    unsigned thresholds as 64-bit unsigned), anyNet, ll128Wanted, ll128Drop,
+    netPeer, llChain, nRings, rsOrder, ringAt (8 x 8 each), and with
+    `channel` ringPos / next / prev."""
+    n = len(peers)
+    pid = (ctypes.c_int * n)(*[p[0] for p in peers])
+    host = (ctypes.c_uint64 * n)(*[p[1] for p in peers])
+    bus = (ctypes.c_int64 * n)(*[p[2] for p in peers])
+    cus = (ctypes.c_int * n)(*[p[3] for p in peers])
+    setup, sizes = (ctypes.c_int64 * len(SETUP_FIELDS))(), (ctypes.c_int64 * len(SETUP_SIZES))()
+    flags, net, chain = (ctypes.c_int * 3)(), (ctypes.c_int * max(nranks, 1))(), (ctypes.c_int * 8)()
+    ring, tables = (ctypes.c_int * 3)(), (ctypes.c_int * 129)()
+    check(lib().vcclCommSetup(nranks, rank, min_ctas, max_ctas, pid, host, bus, cus, setup, sizes, flags, net,
+                              chain, channel if channel is not None else 0,
+                              ring if channel is not None else None, tables), "vcclCommSetup")
+    out = {k: v % (1 << 64) if k.endswith("Bytes") else v for k, v in zip(SETUP_FIELDS, setup)}
+    out.update(zip(SETUP_SIZES, sizes))
+    out.update(anyNet=bool(flags[0]), ll128Wanted=bool(flags[1]), ll128Drop=bool(flags[2]),
+               netPeer=list(net[:nranks]), llChain=list(chain[:min(nranks, 8)]), nRings=tables[0],
+               rsOrder=[list(tables[1 + 8 * k:9 + 8 * k]) for k in range(8)],
+               ringAt=[list(tables[65 + 8 * k:73 + 8 * k]) for k in range(8)])
+    if channel is not None:
+        out.update(ringPos=ring[0], next=ring[1], prev=ring[2])
+    return out
 
 
 def reduce_copy(dev_op: int, dtype: int, red_arg: int, srcs, dsts, n_elts: int, stream: int = 0,
