@@ -250,6 +250,9 @@ typedef struct ncclSimInfo_v22200 {
  * (the tuner's cost model is out of scope) */
 ncclResult_t  ncclGroupSimulateEnd(ncclSimInfo_t* simInfo);
 ncclResult_t pncclGroupSimulateEnd(ncclSimInfo_t* simInfo);
+
+/* ---- point-to-point over per-peer xGMI FIFOs (2..8 ranks of one node;
+ * otherwise, or with a NULL comm, WARN + ncclInvalidUsage) ---- */
 /* nccl.h.in:403-406 */
 ncclResult_t  ncclSend(const void* sendbuff, size_t count, ncclDataType_t datatype, int peer,
     ncclComm_t comm, hipStream_t stream);
@@ -261,7 +264,8 @@ ncclResult_t  ncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, in
 ncclResult_t pncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, int peer,
     ncclComm_t comm, hipStream_t stream);
 /* RCCL's all-to-all extensions (not VCCL API; PyTorch's ROCm build imports
- * them): out of scope too */
+ * them): n sends and n recvs in one group, counts and displacements in
+ * elements; in place (sendbuff == recvbuff) is ncclInvalidArgument */
 ncclResult_t  ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
     ncclComm_t comm, hipStream_t stream);
 ncclResult_t pncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,

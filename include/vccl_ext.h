@@ -204,6 +204,25 @@ ncclResult_t vcclCommSetup(int nRanks, int rank, int minCTAs, int maxCTAs, const
                            int64_t* setup, int64_t* sizes, int* flags, int* netPeer, int* llChain,
                            int channel, int* ring, int* ringTables);
 
+/* The plan of one rank's grouped ncclSend / ncclRecv calls on the per-peer
+ * connections (host only, nothing launched).  Calls in call
+ * order: kinds[i] 0 send / 1 recv, peers[i], bytes[i], buffs[i] the buffer's
+ * address (NULL: all distinct; a self send and recv on one address need no
+ * copy).  parts (1..8), minPartBytes (>= 256) and stepBytes (>= 4096, a
+ * multiple of 512) are the comm-wide constants; gMin / gCap bound the
+ * workgroups per direction (gCap <= 0: one per connection in use); a launch
+ * carries at most maxWorks (1..120) items.  *nItems = the work items, *nWgs
+ * (may be NULL) = workgroups per direction (send workgroups [0, nWgs), recv
+ * workgroups [nWgs, 2 nWgs)); items[12 k ..] = launch, workgroup, kind (0
+ * send, 1 recv, 2 local copy), sweep, round, part, peer, call, second call (a
+ * copy's recv, else -1), byte offset in the message, bytes, FIFO steps — in
+ * execution order.  ncclInvalidUsage: a send to self without its recv of the
+ * same length, or the reverse; ncclInvalidArgument also when cap < *nItems. */
+ncclResult_t vcclP2pPlan(int rank, int nRanks, int nCalls, const int* kinds, const int* peers,
+                         const size_t* bytes, const uint64_t* buffs, int parts, size_t minPartBytes,
+                         size_t stepBytes, int gMin, int gCap, int maxWorks, int cap, int* nItems,
+                         int* nWgs, int64_t* items);
+
 #ifdef __cplusplus
 }
 #endif

@@ -225,6 +225,41 @@ int main() {
   const ncclResult_t ge = ncclGroupEnd();
   EXPECT(ge == ncclInvalidArgument);  // the group fails as a whole (enqueue.cc:2516)
   EXPECT(vcclBuildInfo() != nullptr);
+  // the point-to-point planner on random call lists (self traffic matched or
+  // not), and the NULL-comm answers of the p2p entry points
+  long p2pPlans = 0;
+  for (int trial = 0; trial < 3000; trial++) {
+    const int n = 1 + (int)(rng() % 8), rank = (int)(rng() % n), k = (int)(rng() % 24);
+    const int prt = (int)pick({1, 2, 4, 8}), maxWorks = (int)pick({1, 3, 120});
+    std::vector<int> kinds(k + 1), peers(k + 1);
+    std::vector<size_t> nb(k + 1);
+    for (int i = 0; i < k; i++) {
+      kinds[i] = (int)(rng() % 2);
+      peers[i] = (int)(rng() % n);
+      nb[i] = (size_t)pick({0, 1, 17, 4096, 65537, 3 << 20}) + rng() % 3;
+    }
+    int nItems = -1, nWgs = -1;
+    std::vector<int64_t> items(12 * (size_t)std::max(1, k * prt), -1);
+    const ncclResult_t r = vcclP2pPlan(rank, n, k, kinds.data(), peers.data(), nb.data(), nullptr, prt, 4096, 16384,
+                                       1, (int)pick({0, 1, 3}), maxWorks, k * prt, &nItems, &nWgs, items.data());
+    EXPECT(r == ncclSuccess || r == ncclInvalidUsage);
+    if (r == ncclSuccess) {
+      EXPECT(nItems >= 0 && nItems <= k * prt && nWgs >= 1);
+      for (int i = 0; i < nItems; i++) {
+        const int64_t* it = &items[12 * (size_t)i];
+        EXPECT(it[0] == i / maxWorks && it[1] >= 0 && it[1] < 2 * nWgs && it[2] >= 0 && it[2] <= 2);
+        EXPECT(it[5] >= 0 && it[5] < prt && it[6] >= 0 && it[6] < n && it[7] >= 0 && it[7] < k);
+        EXPECT(it[10] > 0 && it[9] + it[10] <= (int64_t)nb[it[7]]);
+      }
+    }
+    p2pPlans++;
+  }
+  EXPECT(ncclSend(nullptr, 4, ncclFloat32, 0, nullptr, nullptr) == ncclInvalidUsage);
+  EXPECT(ncclRecv(nullptr, 4, ncclFloat32, 0, nullptr, nullptr) == ncclInvalidUsage);
+  EXPECT(ncclAllToAll(nullptr, nullptr, 4, ncclFloat32, nullptr, nullptr) == ncclInvalidUsage);
+  EXPECT(ncclAllToAllv(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ncclFloat32, nullptr, nullptr) ==
+         ncclInvalidUsage);
+  printf("host_api_check: %ld p2p plans\n", p2pPlans);
   printf("host_api_check: %ld groups (%ld calls), %ld partitions, %ld selection strings, %ld setups (%ld refused), "
          "%d failures\n", groups, calls, parts, strs, setups, refusals, g_fail);
   return g_fail == 0 ? 0 : 1;

@@ -78,7 +78,8 @@ struct NetProxy;
 
 // ----------------------------------------------------------------- comm
 // The buffers a rank publishes to its peers.
-enum { kMapFifo = 0, kMapFlag = 1, kMapLL = 2, kMapDirect = 3, kMapDirectFlag = 4, kMapLL128 = 5, kMapCount = 6 };
+enum { kMapFifo = 0, kMapFlag = 1, kMapLL = 2, kMapDirect = 3, kMapDirectFlag = 4, kMapLL128 = 5, kMapP2p = 6,
+       kMapP2pFlag = 7, kMapCount = 8 };
 struct PeerMap {               // what one rank published about itself
   int pid;
   int device;
@@ -124,6 +125,13 @@ struct ncclComm : vccl::CommSetup {
   char* dBuf = nullptr;
   char* dFlags = nullptr;      // kDirectFlagBytes of epoch flags
   vccl::DirectPeers* dPeers = nullptr;  // device-resident peer table
+  // point-to-point (p2p_types.hpp): receive buffer [sender][part][kSteps slots],
+  // flag block [peer][part][tail | head], both uncached and mapped by every
+  // peer; the device-resident connection table (null: no p2p on this comm,
+  // p2pOff says why)
+  char* p2pBuf = nullptr;
+  char* p2pFlags = nullptr;
+  vccl::P2pConn* p2pConns = nullptr;
   vccl::NetProxy* net = nullptr;  // inter-node ring connections (proxy.cc)
   int netListenFd = -1;        // proxy listener, open from init until connections are made
   vccl::DevComm* devComm = nullptr;

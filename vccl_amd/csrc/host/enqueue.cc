@@ -6,7 +6,9 @@
 // misc/argcheck.cc:45-86 -> taskAppend enqueue.cc:2315-2442 with
 // hostToDevRedOp :2217-2310), re-implemented for one node.  Group semantics
 // (group.cc:92-110, :393-506): calls between ncclGroupStart/End are queued per
-// thread and launched at the outermost ncclGroupEnd (launch_group).  The vccl*
+// thread and launched at the outermost ncclGroupEnd (launch_group).  ncclSend /
+// ncclRecv (collectives.cc:160-186) take the same road as p2p tasks;
+// ncclAllToAll(v) is an internal group of them.  The vccl*
 // extension exports at the end are wrappers over plan.h and launch.h.
 #include <algorithm>
 #include <cstring>
@@ -126,23 +128,112 @@ using namespace vccl;
 // Out-of-scope calls of the reference API (include/nccl.h):
 // exported so a binary linked against libnccl loads, never silently wrong.
 static ncclResult_t out_of_scope(const char* name) {
-  VWARN("%s is not part of this library's scope (AllReduce / ReduceScatter / AllGather / Broadcast / Reduce only)",
-        name);
+  VWARN("%s is not part of this library's scope", name);
+  return ncclInvalidUsage;
+}
+// ncclSend / ncclRecv / ncclAllToAll(v) without a communicator: the reference
+// dereferences it (collectives.cc:165); here WARN + ncclInvalidUsage.
+static ncclResult_t p2p_null_comm(const char* name) {
+  VWARN("%s : comm argument is NULL", name);
   return ncclInvalidUsage;
 }
 
-VCCL_EXPORT ncclResult_t ncclSend(const void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) {
-  return out_of_scope("ncclSend");
+// ncclSend / ncclRecv (collectives.cc:160-186 -> ncclEnqueueCheck): checked,
+// then queued in the thread's group or launched alone.
+static ncclResult_t p2p_check_impl(bool send, const char* name, const void* buff, size_t count, ncclDataType_t dt,
+                                   int peer, ncclComm* comm, hipStream_t stream) {
+  NCCLCHECK(comm_check(comm, name));
+  if (peer < 0 || peer >= comm->nRanks) {  // argcheck.cc:58-61
+    VWARN("%s : invalid peer %d (peer should be in the 0..%d range)", name, peer, comm->nRanks);
+    return ncclInvalidArgument;
+  }
+  NCCLCHECK(args_check(comm, name, dt, ncclSum, false));
+  if (!buff && count > 0) {
+    VWARN("%s : NULL buffer", name);
+    return ncclInvalidArgument;
+  }
+  if (*(volatile int*)comm->errorFlag) {
+    const ncclResult_t e = error_word_result(comm);
+    comm->asyncError = e;
+    return e;
+  }
+  NCCLCHECK(p2p_usable(comm, name));
+  VINFO("%s: opCount %lx buff %p count %zu datatype %d peer %d comm %p [nranks=%d] stream %p", name,
+        (unsigned long)comm->opCount, buff, count, (int)dt, peer, (void*)comm, comm->nRanks, (void*)stream);
+  Task t{.coll = send ? kTaskSend : kTaskRecv, .sendbuff = send ? buff : nullptr,
+         .recvbuff = send ? nullptr : const_cast<void*>(buff), .count = count, .datatype = dt, .devOp = OP_COPY,
+         .root = peer, .comm = comm, .stream = stream};
+  if (tl_groupDepth > 0) {
+    tl_tasks.push_back(t);
+    return ncclSuccess;
+  }
+  std::vector<Task> one{t};
+  return launch_group(one);
 }
-VCCL_EXPORT ncclResult_t ncclRecv(void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) {
-  return out_of_scope("ncclRecv");
+static ncclResult_t p2p_check(bool send, const char* name, const void* buff, size_t count, ncclDataType_t dt,
+                              int peer, ncclComm* comm, hipStream_t stream) {
+  const ncclResult_t r = p2p_check_impl(send, name, buff, count, dt, peer, comm, stream);
+  if (r != ncclSuccess && tl_groupDepth > 0 && tl_groupError == ncclSuccess) tl_groupError = r;
+  return r;
 }
-VCCL_EXPORT ncclResult_t ncclAllToAll(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t) {
-  return out_of_scope("ncclAllToAll");
+
+VCCL_EXPORT ncclResult_t ncclSend(const void* sendbuff, size_t count, ncclDataType_t datatype, int peer,
+                                  ncclComm_t comm, hipStream_t stream) {
+  if (!comm) return p2p_null_comm("ncclSend");
+  return p2p_check(true, "Send", sendbuff, count, datatype, peer, comm, stream);
 }
-VCCL_EXPORT ncclResult_t ncclAllToAllv(const void*, const size_t[], const size_t[], void*, const size_t[],
-                                       const size_t[], ncclDataType_t, ncclComm_t, hipStream_t) {
-  return out_of_scope("ncclAllToAllv");
+VCCL_EXPORT ncclResult_t ncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
+                                  hipStream_t stream) {
+  if (!comm) return p2p_null_comm("ncclRecv");
+  return p2p_check(false, "Recv", recvbuff, count, datatype, peer, comm, stream);
+}
+
+// RCCL's all-to-alls: an internal group of n sends and n recvs (the self block
+// a local copy).  counts / displacements in elements; NULL arrays = the
+// uniform all-to-all of `count` elements per pair.
+static ncclResult_t all_to_all(const char* name, const void* sendbuff, const size_t* sendcounts, const size_t* sdispls,
+                               void* recvbuff, const size_t* recvcounts, const size_t* rdispls, size_t count,
+                               ncclDataType_t dt, ncclComm* comm, hipStream_t stream) {
+  ncclResult_t r = comm_check(comm, name);
+  if (r == ncclSuccess) r = args_check(comm, name, dt, ncclSum, false);
+  if (r == ncclSuccess && sendbuff == recvbuff) {
+    VWARN("%s : in-place operation is not supported (sendbuff == recvbuff)", name);
+    r = ncclInvalidArgument;
+  }
+  if (r != ncclSuccess) {
+    if (tl_groupDepth > 0 && tl_groupError == ncclSuccess) tl_groupError = r;
+    return r;
+  }
+  const size_t esz = (size_t)type_size(dt);
+  const int n = comm->nRanks;
+  ncclGroupStart();
+  for (int p = 0; p < n && r == ncclSuccess; p++) {
+    const size_t sc = sendcounts ? sendcounts[p] : count, so = sdispls ? sdispls[p] : (size_t)p * count;
+    const size_t rc = recvcounts ? recvcounts[p] : count, ro = rdispls ? rdispls[p] : (size_t)p * count;
+    r = p2p_check(true, name, sendbuff ? (const char*)sendbuff + so * esz : nullptr, sc, dt, p, comm, stream);
+    if (r == ncclSuccess)
+      r = p2p_check(false, name, recvbuff ? (char*)recvbuff + ro * esz : nullptr, rc, dt, p, comm, stream);
+  }
+  const ncclResult_t e = ncclGroupEnd();  // an inner group: launches only when this is the outermost
+  return r != ncclSuccess ? r : e;
+}
+
+VCCL_EXPORT ncclResult_t ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
+                                      ncclComm_t comm, hipStream_t stream) {
+  if (!comm) return p2p_null_comm("ncclAllToAll");
+  return all_to_all("AllToAll", sendbuff, nullptr, nullptr, recvbuff, nullptr, nullptr, count, datatype, comm, stream);
+}
+VCCL_EXPORT ncclResult_t ncclAllToAllv(const void* sendbuff, const size_t sendcounts[], const size_t sdispls[],
+                                       void* recvbuff, const size_t recvcounts[], const size_t rdispls[],
+                                       ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream) {
+  if (!comm) return p2p_null_comm("ncclAllToAllv");
+  if (!sendcounts || !sdispls || !recvcounts || !rdispls) {
+    VWARN("AllToAllv : NULL count or displacement array");
+    if (tl_groupDepth > 0 && tl_groupError == ncclSuccess) tl_groupError = ncclInvalidArgument;
+    return ncclInvalidArgument;
+  }
+  return all_to_all("AllToAllv", sendbuff, sendcounts, sdispls, recvbuff, recvcounts, rdispls, 0, datatype, comm,
+                    stream);
 }
 
 VCCL_EXPORT ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
@@ -194,7 +285,7 @@ VCCL_EXPORT ncclResult_t ncclGroupEnd(void) {
   std::vector<Task> tasks;
   tasks.swap(tl_tasks);
   if (err != ncclSuccess) {  // a call of the group failed: drop the whole group
-    VWARN("ncclGroupEnd: a call in the group failed (%d); %zu queued collectives not launched",
+    VWARN("ncclGroupEnd: a call in the group failed (%d); %zu queued calls not launched",
           (int)err, tasks.size());
     return err;
   }
@@ -404,6 +495,36 @@ VCCL_EXPORT ncclResult_t vcclCommGroupAlgos(ncclComm_t comm, int nCalls, const i
                          ll128 ? comm->ll128Threads : kDefaultLL128.nThreads};
   return group_plan_export(nCalls, colls, counts, datatypes, ops, comm->nRanks, comm->nChannels, geo, &pol, algos,
                            order.data(), planOf.data(), cbd.data());
+}
+
+// vccl_ext.h: the point-to-point planner on explicit inputs (host only).
+VCCL_EXPORT ncclResult_t vcclP2pPlan(int rank, int nRanks, int nCalls, const int* kinds, const int* peers,
+                                     const size_t* bytes, const uint64_t* buffs, int parts, size_t minPartBytes,
+                                     size_t stepBytes, int gMin, int gCap, int maxWorks, int cap, int* nItems,
+                                     int* nWgs, int64_t* items) {
+  if (nRanks < 1 || nRanks > kP2pMaxRanks || rank < 0 || rank >= nRanks || nCalls < 0 || (nCalls && (!kinds || !peers || !bytes)) ||
+      parts < 1 || parts > kP2pMaxParts || minPartBytes < 256 || stepBytes < 4096 || stepBytes % 512 || maxWorks < 1 ||
+      maxWorks > kP2pMaxWorks || !nItems || cap < 0 || (cap && !items))
+    return ncclInvalidArgument;
+  std::vector<P2pCall> calls;
+  for (int i = 0; i < nCalls; i++) {
+    if ((kinds[i] != kP2pCallSend && kinds[i] != kP2pCallRecv) || peers[i] < 0 || peers[i] >= nRanks)
+      return ncclInvalidArgument;
+    calls.push_back(P2pCall{kinds[i], peers[i], (int64_t)bytes[i], buffs ? buffs[i] : (uint64_t)(2 * i + 1)});
+  }
+  P2pPlanOut plan;
+  NCCLCHECK(p2p_plan(rank, nRanks, calls, P2pGeometry{parts, (int64_t)minPartBytes, (int64_t)stepBytes}, gMin, gCap,
+                     maxWorks, &plan));
+  *nItems = (int)plan.items.size();
+  if (nWgs) *nWgs = plan.nWgs;
+  if ((int)plan.items.size() > cap) return ncclInvalidArgument;
+  for (size_t k = 0; k < plan.items.size(); k++) {
+    const P2pItem& it = plan.items[k];
+    const int64_t v[12] = {it.launch, it.wg, it.kind, it.sweep, it.round, it.part,
+                           it.peer,   it.call, it.call2, it.offset, it.bytes, it.steps};
+    for (int j = 0; j < 12; j++) items[12 * k + j] = v[j];
+  }
+  return ncclSuccess;
 }
 
 VCCL_EXPORT ncclResult_t vcclCommSetAlgo(ncclComm_t comm, int algo) {

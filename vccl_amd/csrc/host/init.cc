@@ -116,6 +116,9 @@ static void free_resources(ncclComm* c) {
   free_null(c->dBuf);
   free_null(c->dFlags);
   free_null(c->dPeers);
+  free_null(c->p2pBuf);
+  free_null(c->p2pFlags);
+  free_null(c->p2pConns);
   free_null(c->devComm);
   free_null(c->ringTrace);
   free_null(c->devChannels);
@@ -231,6 +234,11 @@ static ncclResult_t alloc_buffers(ncclComm* c, const SetupSizes& z, PeerMap* me)
     NCCLCHECK(alloc_published(me, kMapDirectFlag, &c->dFlags, kDirectFlagBytes, true));
   }
   if (z.wantLL128) NCCLCHECK(alloc_published(me, kMapLL128, &c->ll128Buf, z.ll128Bytes, true));
+  if (z.p2pBytes) {
+    VINFO("rank %d: alloc p2p %zu B (%d parts x %d B steps)", c->rank, z.p2pBytes, c->p2pParts, c->p2pStepBytes);
+    NCCLCHECK(alloc_published(me, kMapP2p, &c->p2pBuf, z.p2pBytes, false));
+    NCCLCHECK(alloc_published(me, kMapP2pFlag, &c->p2pFlags, z.p2pFlagBytes, true));
+  }
   return ncclSuccess;
 }
 
@@ -248,6 +256,10 @@ static ncclResult_t apply_mesh(ncclComm* c, MeshSetup* mesh) {
   for (const PeerMap& p : c->peers) ids.push_back(PeerId{p.pid, p.hostHash, p.busId, p.cuCount});
   NCCLCHECK(setup_mesh(c->rank, ids, c, mesh));
   if (mesh->dropLL128) free_null(c->ll128Buf);
+  if (c->p2pOff) {  // a net peer: its memory is not mapped
+    free_null(c->p2pBuf);
+    free_null(c->p2pFlags);
+  }
   return ncclSuccess;
 }
 
@@ -287,6 +299,37 @@ static ncclResult_t upload_dev_comm(ncclComm* c, const std::vector<std::vector<i
   NCCLCHECK(ll_chain(n, dc.llChain));
   HIPCHECK(hipMalloc((void**)&c->devComm, sizeof(DevComm)));
   HIPCHECK(hipMemcpy(c->devComm, &dc, sizeof(dc), hipMemcpyHostToDevice));
+  return ncclSuccess;
+}
+
+// The point-to-point connection table (p2p_types.hpp): for every peer and
+// part, the slots and flags of both directions.
+static ncclResult_t connect_p2p(ncclComm* c, const MeshSetup& mesh) {
+  if (!c->p2pBuf || mesh.anyNet) return ncclSuccess;
+  const int n = c->nRanks, parts = c->p2pParts, me = c->rank;
+  std::vector<char*> bufOf(n), flagOf(n);
+  NCCLCHECK(map_all(c, kMapP2p, mesh.netPeer, bufOf.data()));
+  NCCLCHECK(map_all(c, kMapP2pFlag, mesh.netPeer, flagOf.data()));
+  const size_t perConn = (size_t)kSteps * slot_stride(c->p2pStepBytes);
+  auto fifo = [&](int owner, int sender, int q) { return bufOf[owner] + ((size_t)sender * parts + q) * perConn; };
+  auto flag = [&](int owner, int peer, int q, int which) {
+    return (uint64_t*)(flagOf[owner] + (((size_t)peer * parts + q) * 2 + which) * kFlagStride);
+  };
+  std::vector<P2pConn> conns((size_t)n * parts);
+  for (int p = 0; p < n; p++)
+    for (int q = 0; q < parts; q++) {
+      P2pConn& k = conns[(size_t)p * parts + q];
+      memset(&k, 0, sizeof(k));
+      if (p == me) continue;  // self traffic is a local copy
+      k.sendFifo = fifo(p, me, q);
+      k.nextRecvTail = flag(p, me, q, 0);
+      k.sendHead = flag(me, p, q, 1);
+      k.recvFifo = fifo(me, p, q);
+      k.recvTail = flag(me, p, q, 0);
+      k.prevSendHead = flag(p, me, q, 1);
+    }
+  HIPCHECK(hipMalloc((void**)&c->p2pConns, sizeof(P2pConn) * conns.size()));
+  HIPCHECK(hipMemcpy(c->p2pConns, conns.data(), sizeof(P2pConn) * conns.size(), hipMemcpyHostToDevice));
   return ncclSuccess;
 }
 
@@ -362,6 +405,7 @@ static ncclResult_t init_rank(ncclComm* c, const ncclUniqueId* id) {
   NCCLCHECK(upload_dev_comm(c, rings, mesh.anyNet));
   VINFO("rank %d: map peers", c->rank);
   if (c->nRanks > 1) NCCLCHECK(connect_channels(c, rings, mesh));
+  if (c->nRanks > 1) NCCLCHECK(connect_p2p(c, mesh));
   VINFO("rank %d: final barrier", c->rank);
   NCCLCHECK(bootstrap_barrier(c->bootstrap));
   VINFO("comm %p rank %d/%d dev %d: %d channels x %d threads, step %d B, FIFO slot %d B", (void*)c, c->rank,

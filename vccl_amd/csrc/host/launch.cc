@@ -15,6 +15,7 @@
 #include "../../../include/vccl_device.h"
 #include "../device/dispatch.hpp"
 #include "../device/launch.hpp"
+#include "../device/p2p_launch.hpp"
 #include "../device/ring_launch.hpp"
 
 namespace vccl {
@@ -611,7 +612,106 @@ static ncclResult_t launch_planned(std::vector<Task>& tasks, const std::vector<i
   return launch_runs(runs, runAlgo);
 }
 
-ncclResult_t launch_group(std::vector<Task>& tasks) {
+// ------------------------------------------------------------ point-to-point
+static_assert(kP2pSend == 0 && kP2pRecv == 1 && kP2pCopy == 2, "P2pItem::kind is the device's work kind");
+
+ncclResult_t p2p_usable(const ncclComm* c, const char* api) {
+  if (c->nRanks == 1 || c->p2pConns) return ncclSuccess;
+  if (c->p2pOff == kP2pOffEnv)
+    VWARN("%s : this communicator has no point-to-point buffers (VCCL_P2P_BUFFERS=0)", api);
+  else if (c->p2pOff == kP2pOffRanks)
+    VWARN("%s : point-to-point needs at most %d ranks, this communicator has %d", api, kP2pMaxRanks, c->nRanks);
+  else
+    VWARN("%s : point-to-point through the net proxy is not supported (a peer of this communicator is on "
+          "another node)", api);
+  return ncclInvalidUsage;
+}
+
+// The sends and recvs of one comm's group (call order), as 1 .. launches of
+// the p2p kernel on the first task's stream, the other tasks' streams joined
+// around them exactly as launch_runs does.
+static ncclResult_t launch_p2p(const std::vector<Task>& ts) {
+  ncclComm* comm = ts[0].comm;
+  const hipStream_t s0 = ts[0].stream;
+  const int n = comm->nRanks;
+  const bool conns = comm->p2pConns != nullptr;
+  const P2pGeometry geo{conns ? comm->p2pParts : 1, conns ? comm->p2pMinPartBytes : (int64_t)64 << 10,
+                        conns ? comm->p2pStepBytes : 512 << 10};
+  std::vector<P2pCall> calls;
+  for (const Task& t : ts) {
+    const bool send = t.coll == kTaskSend;
+    calls.push_back(P2pCall{send ? kP2pCallSend : kP2pCallRecv, t.root, (int64_t)t.count * type_size(t.datatype),
+                            (uint64_t)(uintptr_t)(send ? t.sendbuff : (const void*)t.recvbuff)});
+  }
+  comm->opCount += ts.size();  // whatever the outcome
+  // The grid (invariant I4): every rank's send and receive workgroups are
+  // resident at once — the CTA floor first, then the caps, as launch_ll and
+  // direct_work_of apply them.
+  int gCap = std::max(1, comm->maxCTAs / 2);
+  if (comm->shareBlockCap > 0) gCap = std::max(1, std::min(gCap, comm->shareBlockCap / 2));
+  P2pPlanOut plan;
+  const ncclResult_t pr = p2p_plan(comm->rank, n, calls, geo, (comm->minCTAs + 1) / 2, gCap, kP2pMaxWorks, &plan);
+  if (pr != ncclSuccess) {
+    VWARN("ncclGroupEnd : a send to self needs its recv from self of the same length in the same group (rank %d); "
+          "none of this communicator's sends and recvs were launched", comm->rank);
+    return pr;
+  }
+  if (plan.items.empty()) return ncclSuccess;  // zero-byte messages and in-place self pairs only
+  DeviceGuard dev(comm->device);
+  HIPCHECK(dev.status);
+  std::vector<hipStream_t> others;
+  for (const Task& t : ts)
+    if (t.stream != s0 && std::find(others.begin(), others.end(), t.stream) == others.end()) others.push_back(t.stream);
+  CaptureState cs{false, 0};
+  ncclResult_t r = stream_order(comm, s0, &cs);
+  for (hipStream_t s : others) {
+    if (r != ncclSuccess) break;
+    if (hipEventRecord(comm->joinEvent, s) != hipSuccess || hipStreamWaitEvent(s0, comm->joinEvent, 0) != hipSuccess)
+      r = ncclUnhandledCudaError;
+  }
+  bool bound = false;
+  for (size_t k = 0; k < plan.items.size() && r == ncclSuccess;) {
+    P2pBatch b{};
+    b.comm = comm->devComm;
+    b.conns = comm->p2pConns;
+    b.nConns = conns ? n * geo.parts : 0;
+    b.stepBytes = (int)geo.stepBytes;
+    b.nSendWgs = plan.nWgs;
+    const int launch = plan.items[k].launch;
+    for (; k < plan.items.size() && plan.items[k].launch == launch; k++) {
+      const P2pItem& it = plan.items[k];
+      if (b.nWorks >= kP2pMaxWorks || (it.kind != kP2pCopy && (!conns || it.peer == comm->rank)))
+        return ncclInternalError;
+      P2pWork& w = b.works[b.nWorks++];
+      w.kind = (int8_t)it.kind;
+      w.wg = (int16_t)it.wg;
+      w.conn = (int16_t)(it.peer * geo.parts + it.part);
+      w.bytes = it.bytes;
+      if (it.kind != kP2pRecv) w.a = (const char*)ts[it.call].sendbuff + it.offset;
+      if (it.kind != kP2pSend) w.b = (char*)ts[it.kind == kP2pCopy ? it.call2 : it.call].recvbuff + it.offset;
+    }
+    const hipEvent_t stop = stop_event(comm, cs);
+    const hipError_t e = p2p_launch(b, 2 * plan.nWgs, s0, stop);
+    if (e != hipSuccess) {
+      VWARN("p2p kernel launch failed: %s", hipGetErrorString(e));
+      r = ncclUnhandledCudaError;
+    }
+    bound |= r == ncclSuccess && stop != nullptr;
+  }
+  if (r == ncclSuccess) {
+    r = stream_mark(comm, s0, cs);
+  } else if (bound) {  // as launch_runs: an earlier launch already carries the ordering event
+    comm->lastStream = s0;
+    comm->hasLastLaunch = true;
+    comm->lastUnmarked = false;
+  }
+  const hipEvent_t done = stream_last_event(comm, cs);
+  for (hipStream_t s : others)
+    if (r == ncclSuccess && hipStreamWaitEvent(s, done, 0) != hipSuccess) r = ncclUnhandledCudaError;
+  return r;
+}
+
+static ncclResult_t launch_group_colls(std::vector<Task>& tasks) {
   ncclResult_t ret = ncclSuccess;
   const size_t n = tasks.size();
   std::vector<char> done(n, 0);
@@ -649,6 +749,26 @@ ncclResult_t launch_group(std::vector<Task>& tasks) {
     } else {
       r = launch_task(tasks[i]);
     }
+    if (ret == ncclSuccess) ret = r;
+  }
+  return ret;
+}
+
+ncclResult_t launch_group(std::vector<Task>& tasks) {
+  std::vector<Task> colls, p2p;
+  for (const Task& t : tasks) (is_p2p(t.coll) ? p2p : colls).push_back(t);
+  ncclResult_t ret = colls.empty() ? ncclSuccess : launch_group_colls(colls);
+  // per comm (first appearance): its sends and recvs behind its collectives
+  std::vector<char> done(p2p.size(), 0);
+  for (size_t i = 0; i < p2p.size(); i++) {
+    if (done[i]) continue;
+    std::vector<Task> mine;
+    for (size_t j = i; j < p2p.size(); j++)
+      if (!done[j] && p2p[j].comm == p2p[i].comm) {
+        mine.push_back(p2p[j]);
+        done[j] = 1;
+      }
+    const ncclResult_t r = launch_p2p(mine);
     if (ret == ncclSuccess) ret = r;
   }
   return ret;

@@ -9,6 +9,10 @@
 #pragma GCC visibility push(hidden)  // internal, as plan.h
 namespace vccl {
 
+// Task::coll of a point-to-point call (beside plan.h's Coll values).
+enum { kTaskSend = 5, kTaskRecv = 6 };
+inline bool is_p2p(int coll) { return coll == kTaskSend || coll == kTaskRecv; }
+
 struct Task {
   int coll;
   const void* sendbuff;
@@ -18,7 +22,7 @@ struct Task {
   int devOp;
   uint64_t arg;
   const void* argPtr;  // ncclScalarDevice PreMulSum scalar
-  int root;            // broadcast / reduce
+  int root;            // broadcast / reduce; send / recv: the peer
   ncclComm* comm;
   hipStream_t stream;
   // Set by the group planner (launch_planned): this call's partition inside
@@ -34,8 +38,11 @@ AlgoPolicy policy_of(const ncclComm* c);
 int kernel_type_of_call(int coll, int devOp, ncclDataType_t datatype);
 // One call outside a group.
 ncclResult_t launch_task(const Task& t);
-// A group's calls, at the outermost ncclGroupEnd.
+// A group's calls, at the outermost ncclGroupEnd: per comm its collectives,
+// then its sends and recvs (launch_p2p).
 ncclResult_t launch_group(std::vector<Task>& tasks);
+// Why `comm` cannot send or receive (WARN + ncclInvalidUsage), else ncclSuccess.
+ncclResult_t p2p_usable(const ncclComm* comm, const char* api);
 
 }  // namespace vccl
 #pragma GCC visibility pop

@@ -429,4 +429,83 @@ void group_plan(const std::vector<GroupTask>& ts, int nRanks, int commChannels, 
   }
 }
 
+// ------------------------------------------------------------ point-to-point
+P2pSplit p2p_split(int64_t bytes, const P2pGeometry& g) {
+  if (bytes <= 0) return P2pSplit{0, 0};
+  const int64_t want = (bytes + g.minPartBytes - 1) / g.minPartBytes;
+  const int64_t p = std::max<int64_t>(1, std::min<int64_t>(want, g.parts));
+  const int64_t len = ((bytes + p - 1) / p + 15) / 16 * 16;
+  return P2pSplit{(int)((bytes + len - 1) / len), len};
+}
+
+ncclResult_t p2p_plan(int rank, int nRanks, const std::vector<P2pCall>& calls, const P2pGeometry& g, int gMin,
+                      int gCap, int maxWorks, P2pPlanOut* out) {
+  out->items.clear();
+  out->nWgs = out->nLaunches = 0;
+  const int n = nRanks;
+  // per peer, in call order (enqueue.cc:2318-2337)
+  std::vector<std::vector<int>> sends(n), recvs(n);
+  for (int i = 0; i < (int)calls.size(); i++)
+    (calls[i].kind == kP2pCallSend ? sends : recvs)[calls[i].peer].push_back(i);
+  // self traffic is matched inside the group (enqueue.cc:1057-1066)
+  if (sends[rank].size() != recvs[rank].size()) return ncclInvalidUsage;
+  for (size_t s = 0; s < sends[rank].size(); s++)
+    if (calls[sends[rank][s]].bytes != calls[recvs[rank][s]].bytes) return ncclInvalidUsage;
+  size_t nSweeps = 0;
+  for (int p = 0; p < n; p++) nSweeps = std::max({nSweeps, sends[p].size(), recvs[p].size()});
+  // a send-side / receive-side connection -> its index in order of first use
+  std::vector<int> sendIx(n * g.parts, -1), recvIx(n * g.parts, -1);
+  int nSend = 0, nRecv = 0;
+  for (size_t s = 0; s < nSweeps; s++) {
+    for (int d = 0; d < n; d++) {
+      const int to = (rank + d) % n, from = (rank - d + n) % n;
+      const int sc = s < sends[to].size() ? sends[to][s] : -1;
+      const int rc = s < recvs[from].size() ? recvs[from][s] : -1;
+      if (d == 0) {  // both or neither (checked above)
+        if (sc < 0 || calls[sc].buff == calls[rc].buff) continue;
+        const P2pSplit sp = p2p_split(calls[sc].bytes, g);
+        for (int q = 0; q < sp.nParts; q++) {
+          const int64_t off = q * sp.partBytes;
+          int& ix = sendIx[rank * g.parts + q];
+          if (ix < 0) ix = nSend++;
+          out->items.push_back(P2pItem{0, ix, 2, (int)s, d, q, rank, sc, rc, off,
+                                       std::min(sp.partBytes, calls[sc].bytes - off), 0});
+        }
+        continue;
+      }
+      const P2pSplit ss = sc >= 0 ? p2p_split(calls[sc].bytes, g) : P2pSplit{0, 0};
+      const P2pSplit rs = rc >= 0 ? p2p_split(calls[rc].bytes, g) : P2pSplit{0, 0};
+      for (int q = 0; q < std::max(ss.nParts, rs.nParts); q++) {
+        if (q < ss.nParts) {
+          const int64_t off = q * ss.partBytes, len = std::min(ss.partBytes, calls[sc].bytes - off);
+          int& ix = sendIx[to * g.parts + q];
+          if (ix < 0) ix = nSend++;
+          out->items.push_back(P2pItem{0, ix, 0, (int)s, d, q, to, sc, -1, off, len,
+                                       (len + g.stepBytes - 1) / g.stepBytes});
+        }
+        if (q < rs.nParts) {
+          const int64_t off = q * rs.partBytes, len = std::min(rs.partBytes, calls[rc].bytes - off);
+          int& ix = recvIx[from * g.parts + q];
+          if (ix < 0) ix = nRecv++;
+          out->items.push_back(P2pItem{0, ix, 1, (int)s, d, q, from, rc, -1, off, len,
+                                       (len + g.stepBytes - 1) / g.stepBytes});
+        }
+      }
+    }
+  }
+  // the grid: one workgroup per connection in use and direction, within the
+  // CTA floor and then the co-residency cap (I4)
+  int G = std::max(std::max(nSend, nRecv), gMin);
+  if (gCap > 0) G = std::min(G, gCap);
+  G = std::max(G, 1);
+  out->nWgs = G;
+  for (size_t k = 0; k < out->items.size(); k++) {
+    P2pItem& it = out->items[k];
+    it.wg = it.kind == 1 ? G + it.wg % G : it.wg % G;  // I1: a function of the connection alone
+    it.launch = (int)(k / (size_t)maxWorks);
+  }
+  out->nLaunches = (int)((out->items.size() + maxWorks - 1) / maxWorks);
+  return ncclSuccess;
+}
+
 }  // namespace vccl

@@ -116,5 +116,60 @@ uint32_t u32fp_encode(uint32_t x, int bitsPerPow2);
 void group_plan(const std::vector<GroupTask>& ts, int nRanks, int commChannels, const PlanGeometry& geo,
                 const AlgoPolicy* pol, GroupPlanOut* out);
 
+// ------------------------------------------------------------ point-to-point
+// The plan of a group's ncclSend / ncclRecv calls of one comm on its per-peer
+// connections (device/p2p_types.hpp), restating the reference's queueing
+// (enqueue.cc:1042-1109, :2318-2337; round pairing init.cc:1117-1137 on one
+// flat node): sends and recvs are queued per peer in call order; sweep s takes
+// the s-th send to and the s-th recv from every peer; within a sweep round
+// d = 0..n-1 pairs "send to (rank + d) mod n" with "recv from (rank - d) mod n".
+// A message of B bytes uses p = clamp(ceil(B / minPartBytes), 1, parts) parts
+// of alignUp(ceil(B / p), 16) bytes (the last one shorter); part q travels on
+// connection (peer, q) in ceil(bytes / stepBytes) steps.  Both ends derive
+// that from B and the comm-wide constants alone.  A zero-byte message is
+// matched and moves nothing.
+//
+// Invariants of every plan:
+//   I1  a connection direction is driven by one workgroup for the whole group;
+//   I2  a workgroup runs its items in increasing (sweep, round, part) order;
+//   I3  sender and receiver compute the same (sweep, parts, part sizes, steps);
+//   I4  (the caller's gCap) every rank's whole grid is co-resident.
+// With I1-I3 a blocked item waits on a workgroup at a lower or equal key whose
+// own wait is on the other direction, so no cycle exists for any matched set
+// of calls, any grid, and any cut of the list into launches.
+enum { kP2pCallSend = 0, kP2pCallRecv = 1 };
+struct P2pCall {
+  int kind;       // kP2pCallSend / kP2pCallRecv
+  int peer;
+  int64_t bytes;
+  uint64_t buff;  // the user buffer's address (self pairs: same buffer = no copy)
+};
+struct P2pGeometry {
+  int parts;
+  int64_t minPartBytes, stepBytes;
+};
+struct P2pSplit {
+  int nParts;         // parts that carry bytes (0 for an empty message)
+  int64_t partBytes;  // part q covers [q * partBytes, min(B, (q + 1) * partBytes))
+};
+P2pSplit p2p_split(int64_t bytes, const P2pGeometry& g);
+struct P2pItem {
+  int launch, wg;
+  int kind;  // device/p2p_types.hpp kP2pSend / kP2pRecv / kP2pCopy
+  int sweep, round, part, peer;
+  int call, call2;  // the call; a copy: the send and its recv
+  int64_t offset, bytes, steps;
+};
+struct P2pPlanOut {
+  std::vector<P2pItem> items;  // in (sweep, round, part) order, a send before its round's recv
+  int nWgs = 0;                // workgroups per direction (the grid is twice that)
+  int nLaunches = 0;
+};
+// gMin / gCap: the CTA floor, applied before the cap (gCap <= 0: none).
+// maxWorks: items per launch.  ncclInvalidUsage: a send to self without its
+// recv, or the reverse, or the two of different lengths.
+ncclResult_t p2p_plan(int rank, int nRanks, const std::vector<P2pCall>& calls, const P2pGeometry& g, int gMin,
+                      int gCap, int maxWorks, P2pPlanOut* out);
+
 }  // namespace vccl
 #pragma GCC visibility pop

@@ -318,6 +318,30 @@ static void ll128_ring(CommSetup* s, SetupSizes* z) {
   }
 }
 
+// Per-peer point-to-point connections (device/p2p_types.hpp): every rank of a
+// 2..8-rank comm holds, per sender and part, kSteps slots of the step.  The
+// defaults are the reference's NVLink ones and are unmeasured on xGMI.
+static void p2p_connections(int n, CommSetup* s, SetupSizes* z) {
+  if (param_int("P2P_BUFFERS", 1) == 0) {
+    s->p2pOff = kP2pOffEnv;
+    return;
+  }
+  if (n > kP2pMaxRanks) {
+    s->p2pOff = kP2pOffRanks;
+    return;
+  }
+  s->p2pParts = (int)std::max<int64_t>(1, std::min<int64_t>(param_int("P2P_PARTS", 4), kP2pMaxParts));
+  int64_t step = param_int("P2P_NVL_CHUNKSIZE", 512 << 10);
+  if (step < 4096 || step % 512 || step > (64 << 20)) {
+    VWARN("NCCL_P2P_NVL_CHUNKSIZE must be a multiple of 512 from 4096 to 64 MiB, using 524288");
+    step = 512 << 10;
+  }
+  s->p2pStepBytes = (int)step;
+  s->p2pMinPartBytes = std::max<int64_t>(256, param_int("P2P_MIN_PART_BYTES", 64 << 10));
+  z->p2pBytes = (size_t)n * s->p2pParts * kSteps * slot_stride(s->p2pStepBytes);
+  z->p2pFlagBytes = (size_t)n * s->p2pParts * 2 * kFlagStride;
+}
+
 ncclResult_t setup_local(int n, int minCTAs, int maxCTAs, CommSetup* s, SetupSizes* z) {
   s->nChannels = channel_count(n, minCTAs, maxCTAs);
   step_and_slot(s);
@@ -335,6 +359,7 @@ ncclResult_t setup_local(int n, int minCTAs, int maxCTAs, CommSetup* s, SetupSiz
     z->flagBytes = (size_t)s->nChannels * 2 * kFlagStride;
     one_hop_paths(n, s, z);
     ll128_ring(s, z);
+    p2p_connections(n, s, z);
   }
   // paths NCCL_ALGO / NCCL_PROTO exclude drop out of the automatic choice
   // (after llRsAgMaxBytes took its default from llMaxBytes; the buffers stay)
@@ -373,6 +398,7 @@ ncclResult_t setup_mesh(int rank, const std::vector<PeerId>& peers, CommSetup* s
     // (dropLL128), so that neither the automatic choice nor
     // vcclCommSetAlgo(LL128) can pick a ring whose channels carry no LL128
     // slots
+    if (!s->p2pOff) s->p2pOff = kP2pOffNet;  // p2p FIFOs need every peer's memory mapped too
     s->nChannels = std::max(1, std::min(s->nChannels, (int)param_int("NET_NCHANNELS", 8)));
     VINFO("rank %d: inter-node ring through the net proxy, %d channels", rank, s->nChannels);
   }

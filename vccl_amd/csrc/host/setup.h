@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../../include/nccl.h"
+#include "../device/p2p_types.hpp"
 #include "../device/ring_types.hpp"
 
 namespace vccl {
@@ -48,7 +49,17 @@ struct CommSetup {
   int64_t ll128SlotBytes = 0;
   size_t ll128MinBytes = 0, ll128MaxBytes = 0;  // automatic LL128 window (0 = off)
   int shareBlockCap = 0;  // ranks sharing a GPU: workgroups per launch that stay co-resident (0 = no cap)
+  // Point-to-point connections (device/p2p_types.hpp; not part of what
+  // vcclCommSetup reports): parts per ordered pair (VCCL_P2P_PARTS), the step
+  // (NCCL_P2P_NVL_CHUNKSIZE, init.cc:626), the smallest message a second part
+  // is opened for (VCCL_P2P_MIN_PART_BYTES).  p2pOff: why the comm has none
+  // (kP2pOff*), 0 when it has them.
+  int p2pParts = 0;
+  int p2pStepBytes = 0;
+  int64_t p2pMinPartBytes = 0;
+  int p2pOff = 0;
 };
+enum { kP2pOn = 0, kP2pOffEnv = 1, kP2pOffRanks = 2, kP2pOffNet = 3 };
 
 // Bytes of the buffers a rank allocates (0 = none).  Sized for the channel
 // count before the net or shared-GPU caps; the LL buffer and the inbox exist
@@ -57,6 +68,7 @@ struct CommSetup {
 struct SetupSizes {
   size_t fifoBytes = 0, flagBytes = 0, llBytes = 0, inboxBytes = 0, ll128Bytes = 0;
   bool wantLL128 = false;
+  size_t p2pBytes = 0, p2pFlagBytes = 0;  // the p2p receive buffer and flag block
 };
 // Everything one rank decides on its own, in the order the knobs have always
 // been read.  nChannels is 0 and nothing is sized at nRanks == 1.  Fails

@@ -46,8 +46,10 @@ EXPORTED = [
     "vcclCommSetup",
     # rooted rings, split and debug reload
     "ncclReduce", "ncclBcast", "ncclBroadcast", "ncclCommSplit", "ncclResetDebugInit",
+    # point-to-point over per-peer FIFOs (RCCL's all-to-alls grouped from them) and its planner
+    "ncclSend", "ncclRecv", "ncclAllToAll", "ncclAllToAllv", "vcclP2pPlan",
     # out of scope, exported so libnccl-linked binaries load: WARN + ncclInvalidUsage
-    "ncclSend", "ncclRecv", "ncclGroupSimulateEnd", "ncclAllToAll", "ncclAllToAllv",
+    "ncclGroupSimulateEnd",
     # memory / registration / scalable init (what a libnccl caller such as
     # PyTorch's nccl backend imports)
     "ncclMemAlloc", "ncclMemFree", "ncclCommInitRankScalable", "ncclCommRegister", "ncclCommDeregister",
@@ -126,6 +128,14 @@ def lib() -> ctypes.CDLL:
         "ncclAllGather": [vp, vp, c_size, c_int, vp, vp],
         "ncclBroadcast": [vp, vp, c_size, c_int, c_int, vp, vp],
         "ncclReduce": [vp, vp, c_size, c_int, c_int, c_int, vp, vp],
+        "ncclSend": [vp, c_size, c_int, c_int, vp, vp],
+        "ncclRecv": [vp, c_size, c_int, c_int, vp, vp],
+        "ncclAllToAll": [vp, vp, c_size, c_int, vp, vp],
+        "ncclAllToAllv": [vp, ctypes.POINTER(c_size), ctypes.POINTER(c_size), vp, ctypes.POINTER(c_size),
+                          ctypes.POINTER(c_size), c_int, vp, vp],
+        "vcclP2pPlan": [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_size),
+                        ctypes.POINTER(u64), c_int, c_size, c_size, c_int, c_int, c_int, c_int,
+                        ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_int64)],
         "ncclGroupStart": [],
         "ncclGroupEnd": [],
         "vcclReduceCopy": [c_int, c_int, u64, c_int, c_int, c_int, ctypes.POINTER(vp), c_int,
@@ -297,6 +307,32 @@ def group_plan_ex(calls, nranks: int, nchannels: int, policy: dict | None, slot_
             [tuple(cbd[8 * i:8 * i + 8]) for i in range(n)])
 
 
+P2P_SEND, P2P_RECV, P2P_COPY = 0, 1, 2
+P2P_ITEM_FIELDS = ("launch", "wg", "kind", "sweep", "round", "part", "peer", "call", "call2", "offset", "bytes",
+                   "steps")
+
+
+def p2p_plan(rank: int, nranks: int, calls, parts: int = 4, min_part_bytes: int = 64 << 10,
+             step_bytes: int = 512 << 10, g_min: int = 1, g_cap: int = 0, max_works: int = 120):
+    """vcclP2pPlan: the plan of one rank's grouped sends and recvs (host only).
+    calls = [(kind P2P_SEND / P2P_RECV, peer, bytes[, buffer address])] in call
+    order.  Returns (items, n_wgs): items as dicts of P2P_ITEM_FIELDS in
+    execution order, n_wgs workgroups per direction (send workgroups
+    [0, n_wgs), recv workgroups [n_wgs, 2 n_wgs)).  Raises VcclError
+    (ncclInvalidUsage) for an unmatched self send or recv."""
+    n = len(calls)
+    ci = ctypes.c_int * max(n, 1)
+    kinds, peers = ci(*[c[0] for c in calls]), ci(*[c[1] for c in calls])
+    nbytes = (ctypes.c_size_t * max(n, 1))(*[c[2] for c in calls])
+    buffs = (ctypes.c_uint64 * max(n, 1))(*[c[3] if len(c) > 3 else 2 * i + 1 for i, c in enumerate(calls)])
+    cap = max(1, n * parts)
+    items = (ctypes.c_int64 * (12 * cap))()
+    n_items, n_wgs = ctypes.c_int(), ctypes.c_int()
+    check(lib().vcclP2pPlan(rank, nranks, n, kinds, peers, nbytes, buffs, parts, min_part_bytes, step_bytes, g_min,
+                            g_cap, max_works, cap, ctypes.byref(n_items), ctypes.byref(n_wgs), items), "vcclP2pPlan")
+    return ([dict(zip(P2P_ITEM_FIELDS, items[12 * k:12 * k + 12])) for k in range(n_items.value)], n_wgs.value)
+
+
 def algo_selection(algo: str | None, proto: str | None) -> tuple[int, int]:
     """vcclAlgoSelection: (force, allowed mask) for NCCL_ALGO / NCCL_PROTO strings."""
     f, a = ctypes.c_int(), ctypes.c_int()
@@ -426,6 +462,26 @@ class Comm:
     def reduce(self, send: int, recv: int, count: int, dtype: int, op: int, root: int, stream: int = 0):
         """ncclReduce (reduce.h ring): `count` elements reduced into root's `recv`."""
         check(lib().ncclReduce(send, recv, count, dtype, op, root, self.handle, stream), "ncclReduce")
+
+    def send(self, buf: int, count: int, dtype: int, peer: int, stream: int = 0):
+        """ncclSend: `count` elements to `peer` (matched by its ncclRecv)."""
+        check(lib().ncclSend(buf, count, dtype, peer, self.handle, stream), "ncclSend")
+
+    def recv(self, buf: int, count: int, dtype: int, peer: int, stream: int = 0):
+        """ncclRecv: `count` elements from `peer` (matched by its ncclSend)."""
+        check(lib().ncclRecv(buf, count, dtype, peer, self.handle, stream), "ncclRecv")
+
+    def all_to_all(self, send: int, recv: int, count: int, dtype: int, stream: int = 0):
+        """ncclAllToAll (RCCL): block p of `send` (count elements) to rank p, block p of `recv` from it."""
+        check(lib().ncclAllToAll(send, recv, count, dtype, self.handle, stream), "ncclAllToAll")
+
+    def all_to_allv(self, send: int, sendcounts, sdispls, recv: int, recvcounts, rdispls, dtype: int,
+                    stream: int = 0):
+        """ncclAllToAllv (RCCL): per-peer counts and displacements in elements."""
+        n = len(sendcounts)
+        arr = ctypes.c_size_t * n
+        check(lib().ncclAllToAllv(send, arr(*sendcounts), arr(*sdispls), recv, arr(*recvcounts), arr(*rdispls),
+                                  dtype, self.handle, stream), "ncclAllToAllv")
 
     def coll_algo(self, coll: int, count: int, dtype: int) -> str:
         """vcclCommCollAlgo: "ring" | "ll" | "direct" | "ll128" | "one_rank" (coll 0 AR, 1 RS, 2 AG, 3 broadcast, 4 reduce)."""
