@@ -107,6 +107,29 @@
  *                     direct inboxes (0/1), direct all-reduce max bytes,
  *                     direct RS / AG max bucket bytes; algos[i] (may be
  *                     NULL) = the vcclAlgo_t of call i.
+ *   vcclRootedAlgo     the path of one call on an explicit policy that also
+ *                     carries the rooted LL threshold (host only): policy[10]
+ *                     as in vcclGroupPlanEx; `threshold` = the comm's
+ *                     VCCL_LL_ROOTED_THRESHOLD in bytes (negative: read it
+ *                     from the environment; default 0 = off); llAllowed = the
+ *                     NCCL_ALGO / NCCL_PROTO lists leave protocol LL; anyNet =
+ *                     a peer is reached through the net proxy.  *effective
+ *                     (may be NULL) = the threshold as the comm takes it:
+ *                     clamped to the LL slot (policy[1]), 0 without LL
+ *                     buffers, with LL excluded, with a net peer or above 8
+ *                     ranks.  A broadcast or reduce of at most that many
+ *                     bytes takes vcclAlgoLL (automatic or forced LL); with 0
+ *                     every call takes what vcclGroupPlanEx's policy gives it.
+ *   vcclLLRootedPlan   the line layout of one rooted LL launch (broadcast or
+ *                     reduce, 1..16 parts with a root and a byte count each) as
+ *                     rank `rank` sees it (host only): line0[i]
+ *                     (may be NULL) = the first slot line of part i; stores /
+ *                     polls = 4 words per range {peer, part (-1: the arrival
+ *                     token), first line, end line}: the lines this rank
+ *                     writes into its slot at `peer`, and the lines it reads
+ *                     from `peer`'s slot in its own buffer.
+ *                     ncclInvalidArgument when the lines exceed linesPerSlot
+ *                     or a range count exceeds cap.
  *   vcclAlgoSelection  how NCCL_ALGO / NCCL_PROTO strings select paths (the
  *                     reference's parseList, graph/tuning.cc:53-116: comma
  *                     lists, a leading '^' excludes): *force = 0 automatic,
@@ -138,7 +161,7 @@ typedef enum {
 } vcclColl_t;
 typedef enum {
   vcclAlgoRing = 0,     /* SIMPLE ring over arc-balanced ring sets */
-  vcclAlgoLL = 1,       /* one-shot LL all-reduce, chain-tree fold */
+  vcclAlgoLL = 1,       /* one-hop LL: all-reduce (chain-tree fold), RS / AG, opt-in broadcast / reduce */
   vcclAlgoDirect = 2,   /* two-shot direct all-reduce over the full mesh */
   vcclAlgoOneRank = 3,  /* nRanks == 1: copy / PreMulSum kernel */
   vcclAlgoLL128 = 4     /* ring over LL128 FIFOs (64-byte lines by default, in-line flags) */
@@ -175,6 +198,11 @@ ncclResult_t vcclGroupPlanEx(int nCalls, const int* colls, const size_t* counts,
                              const int* ops, int nRanks, int nChannels, const int64_t* geometry,
                              const int64_t* policy, int* algos, int* order, int* planOf, int64_t* cbd);
 ncclResult_t vcclAlgoSelection(const char* algo, const char* proto, int* force, int* allowed);
+ncclResult_t vcclRootedAlgo(int coll, size_t count, ncclDataType_t datatype, int nRanks, const int64_t* policy,
+                            int64_t threshold, int llAllowed, int anyNet, int64_t* effective, int* algo);
+ncclResult_t vcclLLRootedPlan(int coll, int nRanks, int rank, int nParts, const int* roots, const size_t* bytes,
+                              int64_t linesPerSlot, int cap, int64_t* line0, int* nStores, int64_t* stores,
+                              int* nPolls, int64_t* polls);
 /* What initialisation decides for rank `rank` of an nRanks communicator with
  * CTA bounds minCTAs / maxCTAs (a comm's defaults: 1 / 128), from the
  * environment as at init and each rank's identity pid[r], hostHash[r],

@@ -259,6 +259,61 @@ int main() {
   EXPECT(ncclAllToAll(nullptr, nullptr, 4, ncclFloat32, nullptr, nullptr) == ncclInvalidUsage);
   EXPECT(ncclAllToAllv(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ncclFloat32, nullptr, nullptr) ==
          ncclInvalidUsage);
+  // the rooted LL selection (vcclRootedAlgo) and launch layout
+  // (vcclLLRootedPlan) on random policies, thresholds, part lists and caps
+  long rooted = 0;
+  for (int trial = 0; trial < 20000; trial++) {
+    const int n = (int)pick({0, 1, 2, 3, 4, 8, 9, 64, 65});
+    const int64_t slot = pick({0, 0, 8, 4096, 1 << 20, -1});
+    const int64_t pol[10] = {pick({0, 0, 1, 2, 3, 4, 5}), slot, pick({0, 1 << 20}), pick({0, 4 << 20}), pick({0, 1}),
+                             64 << 10, pick({0, 1 << 20}), pick({0, 1}), pick({0, 8 << 20}), pick({0, 64 << 20})};
+    const int64_t thr = pick({-1, 0, 1, 4096, 1 << 20, 1ll << 40});
+    if (rng() % 4 == 0) setenv("VCCL_LL_ROOTED_THRESHOLD", junk[rng() % 11], 1);
+    else if (rng() % 2) setenv("VCCL_LL_ROOTED_THRESHOLD", "65536", 1);
+    else unsetenv("VCCL_LL_ROOTED_THRESHOLD");
+    int64_t eff = -7;
+    int algo = -7;
+    const int coll = (int)(rng() % 7) - 1;
+    const size_t count = (size_t)pick({0, 1, 8, 4097, 1 << 20, 1 << 24});
+    const ncclResult_t r = vcclRootedAlgo(coll, count, (ncclDataType_t)dts[rng() % 10], n, rng() % 16 ? pol : nullptr,
+                                          thr, (int)(rng() % 2), (int)(rng() % 2), rng() % 2 ? &eff : nullptr,
+                                          rng() % 16 ? &algo : nullptr);
+    EXPECT(r == ncclSuccess || r == ncclInvalidArgument);
+    if (r == ncclSuccess) {
+      EXPECT(algo == vcclAlgoRing || algo == vcclAlgoLL || algo == vcclAlgoDirect || algo == vcclAlgoLL128);
+      EXPECT(eff == -7 || (eff >= 0 && eff <= (slot > 0 ? slot : 0)));
+    }
+    const int nr = (int)pick({1, 2, 3, 5, 8, 9}), k = (int)(rng() % 19);
+    const int64_t lps = pick({0, 1, 16, 512, 131072});
+    std::vector<int> roots(k + 1);
+    std::vector<size_t> nb(k + 1);
+    for (int i = 0; i < k; i++) {
+      roots[i] = (int)(rng() % (nr + 1)) - (rng() % 32 == 0);
+      nb[i] = (size_t)pick({0, 1, 7, 8, 9, 100, 4096}) + (rng() % 64 == 0 ? (size_t)lps * 8 : 0);
+    }
+    const int cap = (int)pick({0, 1, 4, (nr - 1) * (k + 1), 200});
+    std::vector<int64_t> l0(k + 1, -1), st(4 * (size_t)cap + 1, -1), po(4 * (size_t)cap + 1, -1);
+    int ns = -1, np = -1;
+    const ncclResult_t q = vcclLLRootedPlan((int)pick({3, 4, 4, 3, 2}), nr, (int)(rng() % (nr + 1)), k, roots.data(),
+                                            nb.data(), lps, cap, rng() % 4 ? l0.data() : nullptr, &ns,
+                                            rng() % 8 ? st.data() : nullptr, &np, rng() % 8 ? po.data() : nullptr);
+    EXPECT(q == ncclSuccess || q == ncclInvalidArgument);
+    if (q == ncclSuccess) {
+      EXPECT(ns >= nr - 1 && ns <= cap && np >= nr - 1 && np <= cap);  // line 0 of every pair, at least
+      for (int i = 0; i < ns; i++) {
+        const int64_t* x = &st[4 * (size_t)i];
+        EXPECT(x[0] >= 0 && x[0] < nr && x[1] >= -1 && x[1] < k && x[2] >= 0 && x[2] < x[3] && x[3] <= lps);
+      }
+      for (int i = 0; i < np; i++) {
+        const int64_t* x = &po[4 * (size_t)i];
+        EXPECT(x[0] >= 0 && x[0] < nr && x[1] >= -1 && x[1] < k && x[2] >= 0 && x[2] < x[3] && x[3] <= lps);
+      }
+    }
+    EXPECT(st[4 * (size_t)cap] == -1 && po[4 * (size_t)cap] == -1);  // nothing past cap ranges
+    rooted++;
+  }
+  unsetenv("VCCL_LL_ROOTED_THRESHOLD");
+  printf("host_api_check: %ld rooted selections and layouts\n", rooted);
   printf("host_api_check: %ld p2p plans\n", p2pPlans);
   printf("host_api_check: %ld groups (%ld calls), %ld partitions, %ld selection strings, %ld setups (%ld refused), "
          "%d failures\n", groups, calls, parts, strs, setups, refusals, g_fail);

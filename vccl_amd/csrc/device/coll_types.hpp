@@ -17,13 +17,16 @@ constexpr int kLLMaxParts = 16;
 // Reduce-scatter / all-gather: nbytes = the bytes of ONE rank's block (send
 // holds n blocks for a reduce-scatter, recv n blocks for an all-gather); the
 // reduce-scatter folds each line on the ring of its channel (VCCL's cbd
-// partition of the block, `cbd`, DevComm::rsOrder).
+// partition of the block, `cbd`, DevComm::rsOrder).  Broadcast / reduce:
+// nbytes = the call's bytes; the part's root is LLWork::partRoot[i], and a
+// reduce folds on the ring of each element's channel like the reduce-scatter
+// (`cbd` = the call's partition under the LL protocol).
 struct LLPart {
   const char* send;
   char* recv;
   int64_t nbytes;
   int64_t line0;           // first line of this part in the slot
-  CbdLite cbd;             // reduce-scatter only
+  CbdLite cbd;             // reduce-scatter / reduce only
 };
 
 struct LLWork {
@@ -39,7 +42,18 @@ struct LLWork {
   char* localBuf;          // my LL buffer: [2 parities][nRanks sources][linesPerSlot] lines
   char* peerBuf[kMaxRanks];  // every rank's LL buffer mapped here (peerBuf[rank] = local)
   LLPart parts[kLLMaxParts];
+  int8_t partRoot[kLLMaxParts];  // broadcast / reduce: the root of each part (nRanks <= kOrderMaxRanks)
 };
+// hipModuleLaunchKernel's by-value argument segment is 4 KiB
+static_assert(sizeof(LLWork) <= 4096, "LLWork must fit the kernel-argument budget");
+
+// Rooted LL launches (ll.hpp ll_broadcast / ll_reduce; host/plan.cc
+// ll_rooted_plan): line 0 of slot (parity, writer) at `reader` carries data
+// when the writer is the root of the part holding line 0 (broadcast) or the
+// reader is (reduce); otherwise the writer stores the zero arrival token there.
+__host__ __device__ __forceinline__ bool ll_rooted_line0_is_data(bool reduce, int writer, int reader, int root0) {
+  return reduce ? reader == root0 : writer == root0;
+}
 
 // Byte offset of the (parity, source rank) slot inside an LL buffer.
 __host__ __device__ __forceinline__ size_t ll_slot_off(int parity, int src, int nRanks,

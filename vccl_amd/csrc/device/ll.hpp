@@ -18,6 +18,22 @@
 // ahead of us (it needs our contribution to finish), so parity reuse is safe
 // and no buffer is ever cleared.
 //
+// Rooted calls (ll_broadcast / ll_reduce below) break that premise on their
+// own: a broadcast root and a reduce non-root wait for nobody, so a fast root
+// could write epochs e+2, e+4, ... into a slot a slow peer still reads at e —
+// and the root changes from call to call, so any (writer -> reader) parity
+// slot could be reused arbitrarily early.  The arrival token restores it: in
+// every rooted launch every rank stores line 0 of its slot (parity, me) at
+// EVERY peer with the call's epoch — the data line where it carries data to
+// that peer, else a zero line — and before the launch retires the epoch one
+// thread of its grid has seen line 0 at epoch e from EVERY peer's slot in its
+// own buffer (through ll_read_line: bounded by the abort word, the error word
+// and the spin timeout like every LL wait).  Every LL launch of a comm, rooted
+// or not, is then an arrival barrier, and the induction goes through:
+//   1. a rank that finishes call e+1 has seen every peer inside e+1;
+//   2. launches of one comm are serialised, so a peer inside e+1 has finished e;
+//   3. therefore nobody writes e+2 into a slot still being read at e.
+//
 // Group aggregation (the reference's planner packing several collectives of
 // one ncclGroupStart/End into one kernel, enqueue.cc:352-508 / :518-769): one
 // launch carries up to kLLMaxParts all-reduces of the same type and op; part
@@ -345,6 +361,181 @@ __device__ inline void ll_allgather(const LLWork& w) {
       ll_store8(part.recv + (int64_t)q * nb, pl, nb, x);
     }
   }
+  ll_epoch_retire(w.comm, e);
+}
+
+// ------------------------------------------------------ broadcast and reduce
+// One-hop rooted collectives: part i's lines sit at [line0_i, line0_i +
+// ceil(nbytes_i / 8)) of the slot (parity, writer) and each part has its own
+// root (LLWork::partRoot).  Broadcast: the root's lines go to every peer.
+// Reduce: every non-root's input lines go to the root alone, which folds them
+// as the reduce-scatter folds the block it owns.  Line 0 of every (writer,
+// reader) pair is stored and seen in every launch — the arrival token of the
+// header — as data where the pair carries the part holding line 0 (part 0),
+// else as a zero line; thread 0 of the grid stores and polls the tokens.
+struct LLRootedParts {
+  LLParts parts;
+  int8_t root[kLLMaxParts];
+};
+__device__ __forceinline__ void ll_load_rooted(const LLWork& w, LLRootedParts* sh) {
+#pragma unroll
+  for (int i = 0; i < kLLMaxParts; i++)
+    if ((int)threadIdx.x == i && i < w.nParts) sh->root[i] = w.partRoot[i];
+  ll_load_parts(w, &sh->parts);
+}
+// The zero token lines of this launch, from thread 0 of the grid: line 0 of my
+// slot at every peer that gets no data line 0 from me.
+__device__ __forceinline__ void ll_token_store(const LLWork& w, bool reduce, int root0, int parity, uint32_t e) {
+  u32x4 line;
+  line.x = 0;
+  line.y = e;
+  line.z = 0;
+  line.w = e;
+  for (int k = 1; k < w.nRanks; k++) {
+    const int p = w.rank + k < w.nRanks ? w.rank + k : w.rank + k - w.nRanks;
+    if (ll_rooted_line0_is_data(reduce, w.rank, p, root0)) continue;
+    const SysAddr d = sys_addr(w.peerBuf[p] + ll_slot_off(parity, w.rank, w.nRanks, w.linesPerSlot));
+    __builtin_amdgcn_raw_buffer_store_b128(line, d.r, d.voff, 0, kSysAux);
+  }
+}
+// ... and the wait for every peer's line 0 that this rank does not read as data.
+__device__ __forceinline__ bool ll_token_wait(const LLWork& w, bool reduce, int root0, int parity, uint32_t e) {
+  for (int k = 1; k < w.nRanks; k++) {
+    const int q = w.rank + k < w.nRanks ? w.rank + k : w.rank + k - w.nRanks;
+    if (ll_rooted_line0_is_data(reduce, q, w.rank, root0)) continue;
+    uint64_t x;
+    if (!ll_read_line(w.localBuf + ll_slot_off(parity, q, w.nRanks, w.linesPerSlot), e, w.comm, &x)) return false;
+  }
+  return true;
+}
+
+// Byte copy (the K_U8 unit).  A non-root never dereferences its `send`.
+__device__ inline void ll_broadcast(const LLWork& w) {
+  __shared__ LLRootedParts sh;
+  ll_load_rooted(w, &sh);
+  const uint32_t e = ll_epoch_of(w.comm);
+  const int parity = (int)(e & 1);
+  const int n = w.nRanks, me = w.rank, nParts = w.nParts;
+  const int64_t nLines = w.nLines;
+  const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t gthreads = (int64_t)gridDim.x * blockDim.x;
+  const int root0 = sh.root[0];
+  int pc = 0;
+  for (int64_t l = gtid; l < nLines; l += gthreads) {
+    pc = ll_advance(sh.parts, nParts, pc, l);
+    if (sh.root[pc] != me) continue;
+    const LLPart& part = sh.parts.p[pc];
+    const int64_t nb = part.nbytes, pl = l - part.line0;
+    const uint64_t v = ll_load8(part.send, pl, nb);
+    u32x4 line;
+    line.x = (uint32_t)v;
+    line.y = e;
+    line.z = (uint32_t)(v >> 32);
+    line.w = e;
+    for (int k = 1; k < n; k++) {
+      const int p = me + k < n ? me + k : me + k - n;
+      const SysAddr d = sys_addr(w.peerBuf[p] + ll_slot_off(parity, me, n, w.linesPerSlot) + l * 16);
+      __builtin_amdgcn_raw_buffer_store_b128(line, d.r, d.voff, 0, kSysAux);
+    }
+    if (part.recv != part.send) ll_store8(part.recv, pl, nb, v);
+  }
+  if (gtid == 0) ll_token_store(w, false, root0, parity, e);
+  bool ok = true;
+  pc = 0;
+  for (int64_t l = gtid; l < nLines && ok; l += gthreads) {
+    pc = ll_advance(sh.parts, nParts, pc, l);
+    const int root = sh.root[pc];
+    if (root == me) continue;
+    const LLPart& part = sh.parts.p[pc];
+    uint64_t x;
+    ok = ll_read_line(w.localBuf + ll_slot_off(parity, root, n, w.linesPerSlot) + l * 16, e, w.comm, &x);
+    if (!ok) break;
+    ll_store8(part.recv, l - part.line0, part.nbytes, x);
+  }
+  if (gtid == 0 && ok) ll_token_wait(w, false, root0, parity, e);
+  ll_epoch_retire(w.comm, e);
+}
+
+// A non-root never writes its `recv`.  The root folds line l on the ring of
+// the line's channel (the call's cbd partition under the LL protocol), from
+// its ring successor around to itself: preOp on every input, postOp once.
+template <class Fn>
+__device__ void ll_reduce(const LLWork& w) {
+  using T = typename Fn::EltType;
+  const Fn fn(load_op_arg(w.redArgPtr, w.redArgBytes, w.redArg));
+  __shared__ LLRootedParts sh;
+  ll_load_rooted(w, &sh);
+  const uint32_t e = ll_epoch_of(w.comm);
+  const int parity = (int)(e & 1);
+  const int n = w.nRanks, me = w.rank, nParts = w.nParts;
+  const int64_t nLines = w.nLines;
+  const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t gthreads = (int64_t)gridDim.x * blockDim.x;
+  const int root0 = sh.root[0];
+  int pc = 0;
+  for (int64_t l = gtid; l < nLines; l += gthreads) {
+    pc = ll_advance(sh.parts, nParts, pc, l);
+    const int root = sh.root[pc];
+    if (root == me) continue;
+    const LLPart& part = sh.parts.p[pc];
+    const uint64_t v = ll_load8(part.send, l - part.line0, part.nbytes);
+    u32x4 line;
+    line.x = (uint32_t)v;
+    line.y = e;
+    line.z = (uint32_t)(v >> 32);
+    line.w = e;
+    // lanes of one wave may sit in parts with different roots: one peer's
+    // buffer per store instruction (sys_addr takes one base per wave)
+    for (int k = 1; k < n; k++) {
+      const int p = me + k < n ? me + k : me + k - n;
+      if (root != p) continue;
+      const SysAddr d = sys_addr(w.peerBuf[p] + ll_slot_off(parity, me, n, w.linesPerSlot) + l * 16);
+      __builtin_amdgcn_raw_buffer_store_b128(line, d.r, d.voff, 0, kSysAux);
+    }
+  }
+  if (gtid == 0) ll_token_store(w, true, root0, parity, e);
+  bool ok = true;
+  pc = 0;
+  for (int64_t l = gtid; l < nLines && ok; l += gthreads) {
+    pc = ll_advance(sh.parts, nParts, pc, l);
+    if (sh.root[pc] != me) continue;
+    const LLPart& part = sh.parts.p[pc];
+    const int64_t nb = part.nbytes, pl = l - part.line0;
+    int64_t end;
+    const int ch = cbd_channel_of(part.cbd, pl * 8 / (int64_t)sizeof(T), &end);
+    const int8_t* order = w.comm->rsOrder[ch % w.comm->nRings];
+    u32x4 v[kOrderMaxRanks];
+#pragma unroll
+    for (int j = 0; j < kOrderMaxRanks; j++) {  // every peer line of l in flight at once
+      const int q = j < n ? order[j] : me;
+      if (q != me) {
+        const SysAddr a = sys_addr_window(w.localBuf + ll_slot_off(parity, q, n, w.linesPerSlot) + l * 16);
+        v[j] = __builtin_amdgcn_raw_buffer_load_b128(a.r, a.voff, 0, kSysAux);
+      }
+    }
+    uint64_t acc = 0;
+#pragma unroll
+    for (int j = 0; j < kOrderMaxRanks; j++) {
+      if (j >= n) break;
+      const int q = order[j];
+      uint64_t x;
+      if (q == me) {
+        x = ll_load8(part.send, pl, nb);
+      } else if (v[j].y == e && v[j].w == e) {
+        x = (uint64_t)v[j].x | ((uint64_t)v[j].z << 32);
+      } else {
+        ok = ll_read_line(w.localBuf + ll_slot_off(parity, q, n, w.linesPerSlot) + l * 16, e, w.comm,
+                          &x);
+        if (!ok) break;
+      }
+      if (Fn::kPreOp && w.preOp) x = ll_apply(fn, 0, x, 1);
+      acc = j == 0 ? x : ll_apply(fn, acc, x, 0);
+    }
+    if (!ok) break;
+    if (Fn::kPostOp) acc = ll_apply(fn, acc, 0, 2);
+    ll_store8(part.recv, pl, nb, acc);
+  }
+  if (gtid == 0 && ok) ll_token_wait(w, true, root0, parity, e);
   ll_epoch_retire(w.comm, e);
 }
 

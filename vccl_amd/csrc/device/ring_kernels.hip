@@ -158,13 +158,20 @@ __global__ __launch_bounds__(256) void k_ll_reducescatter(LLWork w) {
 }
 template <int K>  // instantiated in the K_U8 unit only (byte copies)
 __global__ __launch_bounds__(256) void k_ll_allgather(LLWork w) { ll_allgather(w); }
+template <int K>  // the K_U8 unit only
+__global__ __launch_bounds__(256) void k_ll_broadcast(LLWork w) { ll_broadcast(w); }
+template <class Fn>
+__global__ __launch_bounds__(256) void k_ll_reduce(LLWork w) {
+  ll_reduce<Fn>(w);
+}
 
 template <>
 hipError_t ll_launch<VCCL_KT>(int coll, int devOp, const LLWork& w, int grid, hipStream_t stream,
                               hipEvent_t stop) {
   using T = typename KTypeOf<VCCL_KT>::T;
-  if (coll == kCollAllGather) {
+  if (coll == kCollAllGather || coll == kCollBroadcast) {
     if constexpr (VCCL_KT == K_U8) {
+      if (coll == kCollBroadcast) return launch_k(k_ll_broadcast<K_U8>, dim3(grid), dim3(256), stream, stop, w);
       return launch_k(k_ll_allgather<K_U8>, dim3(grid), dim3(256), stream, stop, w);
     }
     return hipErrorInvalidValue;
@@ -173,6 +180,7 @@ hipError_t ll_launch<VCCL_KT>(int coll, int devOp, const LLWork& w, int grid, hi
   dispatch_op<T>(devOp, [&]<class Fn>() {
     if constexpr (!std::is_same<Fn, FnCopy<T>>::value) {
       err = coll == kCollAllReduce ? launch_k(k_ll_allreduce<Fn>, dim3(grid), dim3(256), stream, stop, w)
+            : coll == kCollReduce  ? launch_k(k_ll_reduce<Fn>, dim3(grid), dim3(256), stream, stop, w)
                                    : launch_k(k_ll_reducescatter<Fn>, dim3(grid), dim3(256), stream, stop, w);
     }
   });

@@ -52,7 +52,7 @@ inline hipError_t ring_launch_any(int variant, int coll, int devOp, const RingBa
 }
 
 // One-hop LL collectives (ll.hpp): 256-thread workgroups, `grid` of them.
-// All-gather only in the K_U8 unit (byte copies).
+// All-gather and broadcast only in the K_U8 unit (byte copies).
 template <int K>
 hipError_t ll_launch(int coll, int devOp, const LLWork& w, int grid, hipStream_t stream, hipEvent_t stop);
 

@@ -16,6 +16,7 @@
 
 #include "../../../include/vccl_device.h"
 #include "../../../include/vccl_ext.h"
+#include "../device/coll_types.hpp"
 #include "../device/dispatch.hpp"
 #include "launch.h"
 
@@ -524,6 +525,56 @@ VCCL_EXPORT ncclResult_t vcclP2pPlan(int rank, int nRanks, int nCalls, const int
                            it.peer,   it.call, it.call2, it.offset, it.bytes, it.steps};
     for (int j = 0; j < 12; j++) items[12 * k + j] = v[j];
   }
+  return ncclSuccess;
+}
+
+// vccl_ext.h: select_algo on an explicit policy with the rooted LL threshold
+// as a comm would carry it (host only).
+VCCL_EXPORT ncclResult_t vcclRootedAlgo(int coll, size_t count, ncclDataType_t datatype, int nRanks,
+                                        const int64_t* policy, int64_t threshold, int llAllowed, int anyNet,
+                                        int64_t* effective, int* algo) {
+  if (!policy || !algo || coll < kAllReduce || coll > kReduce || type_size(datatype) < 1 || nRanks < 1 ||
+      nRanks > kMaxRanks || policy[0] < 0 || policy[0] > 4 || policy[1] < 0)
+    return ncclInvalidArgument;
+  const int64_t* q = policy;
+  AlgoPolicy pol{nRanks, (int)q[0], q[1], (uint64_t)q[2], (uint64_t)q[3], q[4] != 0, (uint64_t)q[5],
+                 (uint64_t)q[6], q[7] != 0, (uint64_t)q[8], (uint64_t)q[9]};
+  if (threshold < 0) threshold = param_int("LL_ROOTED_THRESHOLD", 0);
+  pol.llRootedMax = ll_rooted_max(threshold, pol.llSlotBytes, llAllowed != 0, anyNet != 0, nRanks);
+  if (effective) *effective = (int64_t)pol.llRootedMax;
+  const CallSize sz = call_size(coll, count, datatype);
+  *algo = public_algo(select_algo(pol, coll, sz.eltSize, sz.count));  // one rank: the ring, as select_algo says
+  return ncclSuccess;
+}
+
+// vccl_ext.h: the line layout of one rooted LL launch (host only).
+VCCL_EXPORT ncclResult_t vcclLLRootedPlan(int coll, int nRanks, int rank, int nParts, const int* roots,
+                                          const size_t* bytes, int64_t linesPerSlot, int cap, int64_t* line0,
+                                          int* nStores, int64_t* stores, int* nPolls, int64_t* polls) {
+  if ((coll != kBroadcast && coll != kReduce) || nRanks < 2 || nRanks > kOrderMaxRanks || rank < 0 ||
+      rank >= nRanks || nParts < 1 || nParts > kLLMaxParts || !roots || !bytes || linesPerSlot < 1 || cap < 0 ||
+      !nStores || !nPolls || (cap && (!stores || !polls)))
+    return ncclInvalidArgument;
+  std::vector<int> r(roots, roots + nParts);
+  std::vector<int64_t> b(nParts);
+  for (int i = 0; i < nParts; i++) {
+    if (r[i] < 0 || r[i] >= nRanks || bytes[i] > (size_t)linesPerSlot * 8) return ncclInvalidArgument;
+    b[i] = (int64_t)bytes[i];
+  }
+  LLRootedPlanOut out;
+  NCCLCHECK(ll_rooted_plan(coll, nRanks, rank, r, b, linesPerSlot, &out));
+  *nStores = (int)out.stores.size();
+  *nPolls = (int)out.polls.size();
+  if (line0)
+    for (int i = 0; i < nParts; i++) line0[i] = out.line0[i];
+  if (*nStores > cap || *nPolls > cap) return ncclInvalidArgument;
+  auto put = [](const std::vector<LLRange>& v, int64_t* o) {
+    for (size_t k = 0; k < v.size(); k++) {
+      o[4 * k] = v[k].peer, o[4 * k + 1] = v[k].part, o[4 * k + 2] = v[k].line0, o[4 * k + 3] = v[k].line1;
+    }
+  };
+  put(out.stores, stores);
+  put(out.polls, polls);
   return ncclSuccess;
 }
 

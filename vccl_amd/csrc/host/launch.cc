@@ -181,7 +181,7 @@ AlgoPolicy policy_of(const ncclComm* c) {
                     .llMax = c->llMaxBytes, .llRsAgMax = c->llRsAgMaxBytes,
                     .ll128 = c->ll128Buf != nullptr, .ll128Min = c->ll128MinBytes, .ll128Max = c->ll128MaxBytes,
                     .direct = c->dPeers != nullptr, .directMax = c->directMaxBytes,
-                    .directRsAgMax = c->directRsAgMaxBytes};
+                    .directRsAgMax = c->directRsAgMaxBytes, .llRootedMax = c->llRootedMaxBytes};
 }
 
 int kernel_type_of_call(int coll, int devOp, ncclDataType_t datatype) {
@@ -303,8 +303,9 @@ static CbdLite rs_cbd(const Task& t, int proto) {
 }
 
 // One-hop LL collectives: `ts` holds 1 .. kLLMaxParts calls of one comm with
-// the same collective, type and op (fusable) whose lines — all-reduce: the
-// bucket's, reduce-scatter / all-gather: one rank's block's — fit one slot;
+// the same collective, type and op (fusable) whose lines — all-reduce,
+// broadcast (any roots) and reduce (any roots): the call's, reduce-scatter /
+// all-gather: one rank's block's — fit one slot;
 // they run as one launch on ts[0].stream (the caller orders the other
 // streams around it).
 static int64_t ll_lines_of(const Task& t) {
@@ -320,6 +321,7 @@ static ncclResult_t launch_ll(const Task* ts, int nTasks, hipEvent_t stop) {
   w.localBuf = comm->llBuf;
   for (int r = 0; r < comm->nRanks; r++) w.peerBuf[r] = comm->llPeer[r];
   if (nTasks < 1 || nTasks > kLLMaxParts) return ncclInternalError;
+  const bool rooted = t.coll == kBroadcast || t.coll == kReduce;
   int64_t lines = 0;
   for (int i = 0; i < nTasks; i++) {
     if (ts[i].coll != t.coll) return ncclInternalError;
@@ -327,13 +329,31 @@ static ncclResult_t launch_ll(const Task* ts, int nTasks, hipEvent_t stop) {
     w.parts[i].recv = (char*)ts[i].recvbuff;
     w.parts[i].nbytes = (int64_t)ts[i].count * type_size(ts[i].datatype);
     w.parts[i].line0 = lines;
-    if (t.coll == kReduceScatter) w.parts[i].cbd = rs_cbd(ts[i], kProtoLL);
+    // reduce: the call's own partition, as the reduce-scatter takes its block's
+    if (t.coll == kReduceScatter || t.coll == kReduce) w.parts[i].cbd = rs_cbd(ts[i], kProtoLL);
     lines += ll_lines_of(ts[i]);
   }
   w.nParts = nTasks;
   w.nLines = lines;
   if (lines > comm->llLines) return ncclInternalError;
-  const int kt = t.coll == kAllGather ? K_U8 : kernel_type_of(t.devOp, (int)t.datatype);
+  if (rooted) {
+    // the layout is ll_rooted_plan's (plan.cc): per-part roots, every part
+    // with at least one line (a zero-count call never becomes a task)
+    if (comm->nRanks > kOrderMaxRanks) return ncclInternalError;
+    std::vector<int> roots(nTasks);
+    std::vector<int64_t> bytes(nTasks);
+    for (int i = 0; i < nTasks; i++) roots[i] = ts[i].root, bytes[i] = w.parts[i].nbytes;
+    LLRootedPlanOut lp;
+    if (ll_rooted_plan(t.coll, comm->nRanks, comm->rank, roots, bytes, comm->llLines, &lp) != ncclSuccess ||
+        lp.nLines != lines)
+      return ncclInternalError;
+    for (int i = 0; i < nTasks; i++) {
+      if (lp.line0[i] != w.parts[i].line0 || bytes[i] <= 0) return ncclInternalError;
+      w.partRoot[i] = (int8_t)roots[i];
+    }
+  }
+  const bool copy = is_copy_coll(t.coll);
+  const int kt = copy ? K_U8 : kernel_type_of(t.devOp, (int)t.datatype);
   if (kt < 0) return ncclInvalidArgument;
   // A bounded grid (256-thread workgroups, each thread looping over lines):
   // one workgroup per 256 lines, within the comm's CTA bounds (minCTAs /
@@ -346,7 +366,7 @@ static ncclResult_t launch_ll(const Task* ts, int nTasks, hipEvent_t stop) {
   int grid = (int)std::max<int64_t>(1, (lines + 255) / 256);
   grid = std::max(std::min(grid, comm->maxCTAs), comm->minCTAs);
   grid = std::max(1, std::min(grid, maxBlocks));
-  const int devOp = t.coll == kAllGather ? OP_COPY : t.devOp;
+  const int devOp = copy ? OP_COPY : t.devOp;
   const hipError_t e = by_kernel_type(kt, [&]<int K>() { return ll_launch<K>(t.coll, devOp, w, grid, t.stream, stop); });
   if (e != hipSuccess) {
     VWARN("LL kernel launch failed: %s", hipGetErrorString(e));

@@ -245,7 +245,9 @@ CbdPlan cbd_schedule(int coll, int64_t count, int64_t eltSize, int nRanks, int c
 // all-gather one-hop), larger ones the SIMPLE ring.  NCCL_ALGO / NCCL_PROTO
 // force one: Ring/SIMPLE -> ring; Tree/LL -> LL where it fits; Direct -> direct
 // where the mesh has it; LL128 -> the LL128 ring where its FIFOs exist;
-// anything that does not fit falls through to the ring.  A pure function of
+// anything that does not fit falls through to the ring.  Broadcast and reduce
+// take their rings unless the comm opted into the one-hop rooted LL kernels
+// (llRootedMax, VCCL_LL_ROOTED_THRESHOLD; 0 = off).  A pure function of
 // the comm's thresholds (AlgoPolicy), so the group planner can ask it for an
 // aggregate of calls as ncclPrepareTasks asks getAlgoInfo (enqueue.cc:398).
 // count in elements of eltSize (all-gather: any element type, or bytes)
@@ -253,8 +255,14 @@ int select_algo(const AlgoPolicy& p, int coll, int64_t eltSize, int64_t count) {
   if (p.nRanks < 2 || p.algoForce == 1) return kAlgoRing;
   // NCCL_PROTO=LL128 (or vcclCommSetAlgo): the LL128 ring for every size
   if (p.algoForce == 4) return p.ll128 ? kAlgoRingLL128 : kAlgoRing;
-  if (coll == kBroadcast || coll == kReduce) {  // the rings of broadcast.h / reduce.h: SIMPLE or the LL128 window
+  if (coll == kBroadcast || coll == kReduce) {
     const uint64_t bytes = (uint64_t)(count * eltSize);
+    // the one-hop rooted LL kernels, when the comm opted in (llRootedMax, off
+    // by default): automatic or forced LL; every other force keeps its ring
+    if (p.llRootedMax > 0 && p.llSlotBytes > 0 && p.nRanks <= kOrderMaxRanks && bytes <= p.llRootedMax &&
+        bytes <= (uint64_t)p.llSlotBytes && (p.algoForce == 0 || p.algoForce == 2))
+      return kAlgoLL;
+    // the rings of broadcast.h / reduce.h: SIMPLE or the LL128 window
     return p.ll128 && p.ll128Max && bytes >= p.ll128Min && bytes <= p.ll128Max ? kAlgoRingLL128 : kAlgoRing;
   }
   const uint64_t block = (uint64_t)(count * eltSize);
@@ -278,6 +286,10 @@ int select_algo(const AlgoPolicy& p, int coll, int64_t eltSize, int64_t count) {
   if (p.ll128 && p.ll128Max && bytes >= p.ll128Min && bytes <= p.ll128Max) return kAlgoRingLL128;
   if (directFits) return kAlgoDirect;
   return kAlgoRing;
+}
+uint64_t ll_rooted_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks) {
+  if (threshold <= 0 || llSlotBytes <= 0 || !llAllowed || anyNet || nRanks > kOrderMaxRanks) return 0;
+  return (uint64_t)std::min(threshold, llSlotBytes);
 }
 // The protocol VCCL runs a path's calls with: the one-hop LL stands in for
 // VCCL's LL (tree for the all-reduce, ring otherwise), the direct path for a
@@ -427,6 +439,39 @@ void group_plan(const std::vector<GroupTask>& ts, int nRanks, int commChannels, 
       nPlanColls--;
     }
   }
+}
+
+// ------------------------------------------------------------ rooted LL
+ncclResult_t ll_rooted_plan(int coll, int nRanks, int rank, const std::vector<int>& roots,
+                            const std::vector<int64_t>& bytes, int64_t linesPerSlot, LLRootedPlanOut* out) {
+  const bool reduce = coll == kReduce;
+  const int nParts = (int)roots.size();
+  out->line0.assign(nParts, 0);
+  out->stores.clear();
+  out->polls.clear();
+  int64_t lines = 0;
+  int root0 = -1;  // the root of the part holding line 0
+  for (int i = 0; i < nParts; i++) {
+    out->line0[i] = lines;
+    const int64_t nl = (bytes[i] + 7) / 8;
+    if (nl > 0 && root0 < 0) root0 = roots[i];
+    lines += nl;
+  }
+  out->nLines = lines;
+  if (lines > linesPerSlot) return ncclInvalidArgument;
+  for (int k = 1; k < nRanks; k++) {
+    const int peer = (rank + k) % nRanks;
+    for (int i = 0; i < nParts; i++) {
+      const int64_t l0 = out->line0[i], l1 = l0 + (bytes[i] + 7) / 8;
+      if (l1 == l0) continue;
+      // broadcast: the root writes to everyone; reduce: everyone to the root
+      if (reduce ? roots[i] == peer : roots[i] == rank) out->stores.push_back(LLRange{peer, i, l0, l1});
+      if (reduce ? roots[i] == rank : roots[i] == peer) out->polls.push_back(LLRange{peer, i, l0, l1});
+    }
+    if (root0 < 0 || !ll_rooted_line0_is_data(reduce, rank, peer, root0)) out->stores.push_back(LLRange{peer, -1, 0, 1});
+    if (root0 < 0 || !ll_rooted_line0_is_data(reduce, peer, rank, root0)) out->polls.push_back(LLRange{peer, -1, 0, 1});
+  }
+  return ncclSuccess;
 }
 
 // ------------------------------------------------------------ point-to-point

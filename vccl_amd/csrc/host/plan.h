@@ -83,7 +83,12 @@ struct AlgoPolicy {
   uint64_t ll128Min = 0, ll128Max = 0;     // automatic LL128 window (max 0 = off)
   bool direct = false;                     // every peer's inbox mapped
   uint64_t directMax = 0, directRsAgMax = 0;
+  uint64_t llRootedMax = 0;                // largest broadcast / reduce on the one-hop LL path (0 = off)
 };
+// A comm's VCCL_LL_ROOTED_THRESHOLD as it takes effect: clamped to what one
+// LL slot holds; 0 without LL buffers, with LL excluded by NCCL_PROTO, with a
+// peer behind the net proxy, or with more ranks than the fold-order tables.
+uint64_t ll_rooted_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks);
 int select_algo(const AlgoPolicy& p, int coll, int64_t eltSize, int64_t count);
 int proto_of_algo(int algo);
 
@@ -115,6 +120,27 @@ struct GroupPlanOut {
 uint32_t u32fp_encode(uint32_t x, int bitsPerPow2);
 void group_plan(const std::vector<GroupTask>& ts, int nRanks, int commChannels, const PlanGeometry& geo,
                 const AlgoPolicy* pol, GroupPlanOut* out);
+
+// ------------------------------------------------------------ rooted LL
+// The line layout of one rooted LL launch (device/ll.hpp ll_broadcast /
+// ll_reduce) as `rank` sees it: part i (root roots[i], bytes[i] bytes) sits at
+// lines [line0[i], line0[i] + ceil(bytes[i] / 8)) of every slot.  stores: the
+// line ranges this rank writes into slot (parity, rank) of `peer`'s buffer;
+// polls: the line ranges it reads from slot (parity, peer) of its own.  A
+// range of part -1 is the arrival token: line 0 of every ordered pair that
+// carries no data line 0 (ll_rooted_line0_is_data).  ncclInvalidArgument when
+// the lines do not fit one slot.
+struct LLRange {
+  int peer, part;          // part -1: the token line
+  int64_t line0, line1;    // [line0, line1)
+};
+struct LLRootedPlanOut {
+  std::vector<int64_t> line0;  // per part
+  int64_t nLines = 0;
+  std::vector<LLRange> stores, polls;
+};
+ncclResult_t ll_rooted_plan(int coll, int nRanks, int rank, const std::vector<int>& roots,
+                            const std::vector<int64_t>& bytes, int64_t linesPerSlot, LLRootedPlanOut* out);
 
 // ------------------------------------------------------------ point-to-point
 // The plan of a group's ncclSend / ncclRecv calls of one comm on its per-peer

@@ -14,6 +14,7 @@
 #include "../device/coll_types.hpp"
 #include "../device/ring_launch.hpp"  // kRingMaxThreads
 #include "core.h"                     // VWARN / VINFO / param_int
+#include "plan.h"                     // ll_rooted_max
 
 namespace vccl {
 
@@ -366,6 +367,11 @@ ncclResult_t setup_local(int n, int minCTAs, int maxCTAs, CommSetup* s, SetupSiz
   if (!(s->algoAllowed & kAllowLL)) s->llMaxBytes = 0;
   if (!(s->algoAllowed & kAllowLLRsAg)) s->llRsAgMaxBytes = 0;
   if (!(s->algoAllowed & kAllowDirect)) s->directMaxBytes = s->directRsAgMaxBytes = 0;
+  // Rooted LL (ncclBroadcast / ncclReduce in one hop): opt-in, off by default —
+  // the size where one hop stops winning over xGMI is unmeasured.  The
+  // reference runs both on its ring under LL: protocol LL with Tree or Ring.
+  s->llRootedMaxBytes = (size_t)ll_rooted_max(param_int("LL_ROOTED_THRESHOLD", 0), (int64_t)s->llLines * 8,
+                                              (s->algoAllowed & kAllowLLRsAg) != 0, false, n);
   return ncclSuccess;
 }
 
@@ -390,7 +396,7 @@ ncclResult_t setup_mesh(int rank, const std::vector<PeerId>& peers, CommSetup* s
     // LL and the two-shot direct path need every peer's memory mapped
     // (full xGMI mesh): all-reduce takes the ring.  Net channels move
     // through the proxy, a few are enough (NCCL's net defaults use 2-4).
-    s->llMaxBytes = s->llRsAgMaxBytes = 0;
+    s->llMaxBytes = s->llRsAgMaxBytes = s->llRootedMaxBytes = 0;
     s->directMaxBytes = s->directRsAgMaxBytes = 0;
     s->ll128MinBytes = s->ll128MaxBytes = 0;
     if (s->algoForce == 4) s->algoForce = 1;  // LL128 lines need the xGMI mesh: SIMPLE

@@ -58,6 +58,10 @@ struct CommSetup {
   int p2pStepBytes = 0;
   int64_t p2pMinPartBytes = 0;
   int p2pOff = 0;
+  // Largest ncclBroadcast / ncclReduce on the one-hop LL path
+  // (VCCL_LL_ROOTED_THRESHOLD, plan.h ll_rooted_max; default 0 = off; not part
+  // of what vcclCommSetup reports)
+  size_t llRootedMaxBytes = 0;
 };
 enum { kP2pOn = 0, kP2pOffEnv = 1, kP2pOffRanks = 2, kP2pOffNet = 3 };
 

@@ -48,6 +48,8 @@ EXPORTED = [
     "ncclReduce", "ncclBcast", "ncclBroadcast", "ncclCommSplit", "ncclResetDebugInit",
     # point-to-point over per-peer FIFOs (RCCL's all-to-alls grouped from them) and its planner
     "ncclSend", "ncclRecv", "ncclAllToAll", "ncclAllToAllv", "vcclP2pPlan",
+    # one-hop LL broadcast / reduce: the selection with its threshold, and the launch's line layout
+    "vcclRootedAlgo", "vcclLLRootedPlan",
     # out of scope, exported so libnccl-linked binaries load: WARN + ncclInvalidUsage
     "ncclGroupSimulateEnd",
     # memory / registration / scalable init (what a libnccl caller such as
@@ -162,6 +164,11 @@ def lib() -> ctypes.CDLL:
                             ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_int64)],
         "vcclCommGroupAlgos": [vp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_size), ctypes.POINTER(c_int),
                                ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
+        "vcclRootedAlgo": [c_int, c_size, c_int, c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, c_int, c_int,
+                           ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int)],
+        "vcclLLRootedPlan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_size),
+                             ctypes.c_int64, c_int, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int),
+                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_int64)],
         "vcclAlgoSelection": [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(c_int),
                               ctypes.POINTER(c_int)],
         "vcclCommSetup": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(u64),
@@ -305,6 +312,36 @@ def group_plan_ex(calls, nranks: int, nchannels: int, policy: dict | None, slot_
                                 cbd), "vcclGroupPlanEx")
     return ([ALGO_NAMES[a] for a in algos], list(order), list(plan_of),
             [tuple(cbd[8 * i:8 * i + 8]) for i in range(n)])
+
+
+def rooted_algo(coll: int, count: int, dtype: int, nranks: int, policy: dict, threshold: int | None = None,
+                ll_allowed: bool = True, any_net: bool = False) -> tuple[str, int]:
+    """vcclRootedAlgo: (path, effective threshold) of one call on `policy`
+    (POLICY_FIELDS) plus the rooted LL threshold in bytes as a comm would take
+    it (None: VCCL_LL_ROOTED_THRESHOLD from the environment)."""
+    pol = (ctypes.c_int64 * 10)(*[int(policy[k]) for k in POLICY_FIELDS])
+    eff, a = ctypes.c_int64(), ctypes.c_int()
+    check(lib().vcclRootedAlgo(coll, count, dtype, nranks, pol, -1 if threshold is None else threshold,
+                               int(ll_allowed), int(any_net), ctypes.byref(eff), ctypes.byref(a)), "vcclRootedAlgo")
+    return ALGO_NAMES[a.value], eff.value
+
+
+def ll_rooted_plan(coll: int, nranks: int, rank: int, parts, lines_per_slot: int):
+    """vcclLLRootedPlan: the line layout of one rooted LL launch as `rank` sees
+    it.  coll 3 broadcast / 4 reduce; parts = [(root, bytes)].  Returns (line0
+    per part, stores, polls); stores / polls = [(peer, part, first line, end
+    line)], part -1 = the arrival token line."""
+    k = len(parts)
+    roots = (ctypes.c_int * k)(*[p[0] for p in parts])
+    nbytes = (ctypes.c_size_t * k)(*[p[1] for p in parts])
+    cap = (nranks - 1) * (k + 1)
+    line0 = (ctypes.c_int64 * k)()
+    st, po = (ctypes.c_int64 * (4 * cap))(), (ctypes.c_int64 * (4 * cap))()
+    ns, np_ = ctypes.c_int(), ctypes.c_int()
+    check(lib().vcclLLRootedPlan(coll, nranks, rank, k, roots, nbytes, lines_per_slot, cap, line0, ctypes.byref(ns),
+                                 st, ctypes.byref(np_), po), "vcclLLRootedPlan")
+    return (list(line0), [tuple(st[4 * i:4 * i + 4]) for i in range(ns.value)],
+            [tuple(po[4 * i:4 * i + 4]) for i in range(np_.value)])
 
 
 P2P_SEND, P2P_RECV, P2P_COPY = 0, 1, 2
