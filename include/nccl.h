@@ -11,9 +11,12 @@
  * repo's own transport (xGMI peer memory, no RCCL) and the comm lifecycle they
  * need, Broadcast / Bcast (the byte-copy ring), Reduce (the reduce ring),
  * CommSplit, MemAlloc / MemFree, Register / Deregister (a no-op) and
- * InitRankScalable.  The calls of the "out of scope" block at the end (Send, Recv,
- * GroupSimulateEnd, RCCL's AllToAll / AllToAllv) are declared and exported so a binary linked against
- * libnccl still loads; each logs a WARN and returns ncclInvalidUsage.
+ * InitRankScalable, Send / Recv and RCCL's AllToAll / AllToAllv over per-peer
+ * xGMI FIFOs (one node, at most 8 ranks) — with VCCL_LL_A2A_THRESHOLD set (off
+ * by default) the all-to-alls' pairs of at most that many bytes move in one
+ * hop over the LL slots instead.  GroupSimulateEnd is declared and exported so
+ * a binary linked against libnccl still loads; it logs a WARN and returns
+ * ncclInvalidUsage.
  */
 #ifndef VCCL_NCCL_H_
 #define VCCL_NCCL_H_
@@ -265,7 +268,11 @@ ncclResult_t pncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, in
     ncclComm_t comm, hipStream_t stream);
 /* RCCL's all-to-all extensions (not VCCL API; PyTorch's ROCm build imports
  * them): n sends and n recvs in one group, counts and displacements in
- * elements; in place (sendbuff == recvbuff) is ncclInvalidArgument */
+ * elements; in place (sendbuff == recvbuff) is ncclInvalidArgument.  On a
+ * communicator created with VCCL_LL_A2A_THRESHOLD=<bytes per pair> (default 0
+ * = off) every ordered pair of at most that many bytes travels in one one-hop
+ * LL launch per call and only the larger pairs stay sends and recvs; plain
+ * ncclSend / ncclRecv never take that path (they are not collective). */
 ncclResult_t  ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
     ncclComm_t comm, hipStream_t stream);
 ncclResult_t pncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,

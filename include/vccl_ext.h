@@ -130,6 +130,35 @@
  *                     from `peer`'s slot in its own buffer.
  *                     ncclInvalidArgument when the lines exceed linesPerSlot
  *                     or a range count exceeds cap.
+ *   vcclLLA2aMax       a comm's VCCL_LL_A2A_THRESHOLD (bytes per ordered pair of
+ *                     an ncclAllToAll(v); negative: read it from the
+ *                     environment; default 0 = off) as it takes effect (host
+ *                     only): clamped to the LL slot
+ *                     (llSlotBytes), 0 without LL buffers, with LL excluded,
+ *                     with a net peer, below 2 or above 8 ranks, or without
+ *                     point-to-point connections.
+ *   vcclLLA2aPlan      how one ncclAllToAll (uniform != 0: every entry of both
+ *                     rows the same) / ncclAllToAllv call of sendBytes[nRanks]
+ *                     / recvBytes[nRanks] splits, as rank `rank` runs it, on a
+ *                     comm whose effective limit is llA2aMax (host only).  The
+ *                     ordered pair of B bytes is an LL pair iff llA2aMax > 0 and
+ *                     B <= llA2aMax; *launch = the call has an LL launch (a
+ *                     uniform call iff 0 < B <= llA2aMax, a v-call iff llA2aMax
+ *                     > 0; without one no pair is LL).  sendLL / recvLL[nRanks]
+ *                     = the pair bit of each direction; stores / polls = with
+ *                     a launch nRanks - 1 ranges of 4 words {peer, part (0 data,
+ *                     -1 the zero arrival token), first line, end line}: what
+ *                     this rank writes into its slot at `peer` and reads from
+ *                     `peer`'s slot in its own buffer; resSends / resRecvs
+ *                     [<= nRanks] = the peers whose send / recv stays on the
+ *                     p2p FIFOs, in peer order.
+ *   vcclCommA2aStats   cumulative: LL all-to-all launches, and the sends + recvs
+ *                     (2 nRanks per call, the self block included) of this
+ *                     comm's all-to-alls that went by LL / to the p2p FIFOs.
+ *   vcclCommSetA2aThreshold  re-derives the per-pair limit on a live comm from
+ *                     `bytes` (as VCCL_LL_A2A_THRESHOLD at init); *effective
+ *                     (may be NULL) = the result.  A tuning / measurement knob:
+ *                     every rank must call it alike, outside a group.
  *   vcclAlgoSelection  how NCCL_ALGO / NCCL_PROTO strings select paths (the
  *                     reference's parseList, graph/tuning.cc:53-116: comma
  *                     lists, a leading '^' excludes): *force = 0 automatic,
@@ -161,7 +190,8 @@ typedef enum {
 } vcclColl_t;
 typedef enum {
   vcclAlgoRing = 0,     /* SIMPLE ring over arc-balanced ring sets */
-  vcclAlgoLL = 1,       /* one-hop LL: all-reduce (chain-tree fold), RS / AG, opt-in broadcast / reduce */
+  vcclAlgoLL = 1,       /* one-hop LL: all-reduce (chain-tree fold), RS / AG, opt-in broadcast / reduce
+                           (the opt-in LL all-to-all is per pair, not a vcclAlgo_t: vcclCommA2aStats) */
   vcclAlgoDirect = 2,   /* two-shot direct all-reduce over the full mesh */
   vcclAlgoOneRank = 3,  /* nRanks == 1: copy / PreMulSum kernel */
   vcclAlgoLL128 = 4     /* ring over LL128 FIFOs (64-byte lines by default, in-line flags) */
@@ -203,6 +233,15 @@ ncclResult_t vcclRootedAlgo(int coll, size_t count, ncclDataType_t datatype, int
 ncclResult_t vcclLLRootedPlan(int coll, int nRanks, int rank, int nParts, const int* roots, const size_t* bytes,
                               int64_t linesPerSlot, int cap, int64_t* line0, int* nStores, int64_t* stores,
                               int* nPolls, int64_t* polls);
+ncclResult_t vcclLLA2aMax(int64_t threshold, int64_t llSlotBytes, int llAllowed, int anyNet, int nRanks,
+                          int hasP2p, int64_t* effective);
+ncclResult_t vcclLLA2aPlan(int nRanks, int rank, const size_t* sendBytes, const size_t* recvBytes, int uniform,
+                           int64_t llA2aMax, int64_t linesPerSlot, int* sendLL, int* recvLL, int* launch,
+                           int64_t* stores, int64_t* polls, int* nResSends, int* resSends, int* nResRecvs,
+                           int* resRecvs);
+ncclResult_t vcclCommA2aStats(ncclComm_t comm, unsigned long long* llLaunches, unsigned long long* llPairs,
+                              unsigned long long* fifoPairs);
+ncclResult_t vcclCommSetA2aThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
 /* What initialisation decides for rank `rank` of an nRanks communicator with
  * CTA bounds minCTAs / maxCTAs (a comm's defaults: 1 / 128), from the
  * environment as at init and each rank's identity pid[r], hostHash[r],

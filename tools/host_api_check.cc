@@ -313,6 +313,65 @@ int main() {
     rooted++;
   }
   unsetenv("VCCL_LL_ROOTED_THRESHOLD");
+  // the LL all-to-all limit (vcclLLA2aMax) and one call's split (vcclLLA2aPlan)
+  // on random byte matrices, limits, slots and invalid arguments
+  long a2a = 0;
+  for (int trial = 0; trial < 20000; trial++) {
+    if (rng() % 4 == 0) setenv("VCCL_LL_A2A_THRESHOLD", junk[rng() % 11], 1);
+    else if (rng() % 2) setenv("VCCL_LL_A2A_THRESHOLD", "65536", 1);
+    else unsetenv("VCCL_LL_A2A_THRESHOLD");
+    const int64_t slot = pick({0, 8, 4096, 1 << 20, -1});
+    int64_t eff = -7;
+    const ncclResult_t r = vcclLLA2aMax(pick({-1, 0, 1, 4096, 1 << 20, 1ll << 40}), slot, (int)(rng() % 2),
+                                        (int)(rng() % 2), (int)pick({0, 1, 2, 8, 9, 64}), (int)(rng() % 2),
+                                        rng() % 16 ? &eff : nullptr);
+    EXPECT(r == ncclSuccess || r == ncclInvalidArgument);
+    if (r == ncclSuccess) EXPECT(eff >= 0 && eff <= (slot > 0 ? slot : 0));
+    const int n = (int)pick({1, 2, 3, 4, 5, 8, 8, 9}), rank = (int)(rng() % (n + 1)) - (rng() % 32 == 0);
+    const int64_t lps = pick({0, 1, 16, 512, 131072});
+    const int64_t lim = pick({0, 8, 100, 4096, lps * 8, lps * 8 + 1, -1});
+    const int uniform = (int)(rng() % 3 == 0);
+    std::vector<size_t> sb(n + 1), rb(n + 1);
+    const size_t u = (size_t)pick({0, 1, 8, 4096, 4097});
+    for (int p = 0; p < n; p++) {
+      sb[p] = uniform && rng() % 16 ? u : (size_t)pick({0, 1, 7, 8, 9, 100, 4096, 4097, 1 << 20}) + rng() % 2;
+      rb[p] = uniform && rng() % 16 ? u : (size_t)pick({0, 1, 7, 8, 9, 100, 4096, 4097, 1 << 20}) + rng() % 2;
+      if (rng() % 256 == 0) sb[p] = ~(size_t)0;
+    }
+    std::vector<int> sll(n + 1, -1), rll(n + 1, -1), rs(n + 1, -1), rr(n + 1, -1);
+    std::vector<int64_t> st(4 * (size_t)n + 1, -1), po(4 * (size_t)n + 1, -1);
+    int launch = -1, nrs = -1, nrr = -1;
+    const ncclResult_t q = vcclLLA2aPlan(n, rank, rng() % 32 ? sb.data() : nullptr, rb.data(), uniform, lim, lps,
+                                         sll.data(), rng() % 32 ? rll.data() : nullptr, &launch, st.data(), po.data(),
+                                         &nrs, rs.data(), &nrr, rr.data());
+    EXPECT(q == ncclSuccess || q == ncclInvalidArgument);
+    if (q == ncclSuccess) {
+      EXPECT(launch == 0 || launch == 1);
+      EXPECT(nrs >= 0 && nrs <= n && nrr >= 0 && nrr <= n);
+      int nll = 0;
+      for (int p = 0; p < n; p++) {
+        EXPECT((sll[p] == 0 || sll[p] == 1) && (rll[p] == 0 || rll[p] == 1));
+        if (!launch) EXPECT(!sll[p] && !rll[p]);
+        if (sll[p]) EXPECT((int64_t)sb[p] <= lim);
+        if (rll[p]) EXPECT((int64_t)rb[p] <= lim);
+        nll += sll[p] + rll[p];
+      }
+      EXPECT(nll + nrs + nrr == 2 * n);
+      for (int i = 0; i < (launch ? n - 1 : 0); i++) {
+        for (const int64_t* x : {&st[4 * (size_t)i], &po[4 * (size_t)i]})
+          EXPECT(x[0] >= 0 && x[0] < n && x[0] != rank && (x[1] == 0 || x[1] == -1) && x[2] == 0 && x[3] >= 1 &&
+                 x[3] <= lps);
+      }
+      if (!launch) EXPECT(st[0] == -1 && po[0] == -1);
+    }
+    EXPECT(st[4 * (size_t)(n - 1)] == -1 && po[4 * (size_t)(n - 1)] == -1);  // nothing past n - 1 ranges
+    EXPECT(sll[n] == -1 && rll[n] == -1 && rs[n] == -1 && rr[n] == -1);
+    a2a++;
+  }
+  unsetenv("VCCL_LL_A2A_THRESHOLD");
+  EXPECT(vcclCommA2aStats(nullptr, nullptr, nullptr, nullptr) == ncclInvalidArgument);
+  EXPECT(vcclCommSetA2aThreshold(nullptr, 4096, nullptr) == ncclInvalidArgument);
+  printf("host_api_check: %ld all-to-all limits and plans\n", a2a);
   printf("host_api_check: %ld rooted selections and layouts\n", rooted);
   printf("host_api_check: %ld p2p plans\n", p2pPlans);
   printf("host_api_check: %ld groups (%ld calls), %ld partitions, %ld selection strings, %ld setups (%ld refused), "

@@ -55,6 +55,33 @@ __host__ __device__ __forceinline__ bool ll_rooted_line0_is_data(bool reduce, in
   return reduce ? reader == root0 : writer == root0;
 }
 
+// One-hop LL all-to-all (ll.hpp ll_alltoall; host/plan.cc ll_a2a_plan).  The
+// tables are ROTATED to the rank: entry k belongs to rank (rank + k) mod
+// nRanks, entry 0 to the rank itself.  An ordered pair whose "LL pair" bit is
+// set moves its bytes as lines [0, ceil(bytes / 8)) of slot (parity, writer) at
+// the reader; every other pair moves in the FIFO launch of the same call and
+// only exchanges the zero arrival token on line 0 here.  The LL pairs' lines
+// are flattened in entry order: entry k's send lines are the grid-stride
+// indices [sendLine0[k], sendLine0[k + 1]), likewise recvLine0.
+constexpr int kLLA2aMaxRanks = kOrderMaxRanks;
+struct LLA2aPeer {
+  const char* send;        // my block for this peer
+  char* recv;              // where this peer's block lands
+  int64_t sendBytes, recvBytes;
+  int32_t sendLL, recvLL;  // the "LL pair" bit of each direction
+};
+struct LLA2aWork {
+  DevComm* comm;
+  int rank, nRanks;
+  int linesPerSlot;        // capacity of one (parity, source) slot
+  int pad;
+  char* localBuf;          // my LL buffer
+  char* peerBuf[kLLA2aMaxRanks];  // rotated: peerBuf[k] = the LL buffer of rank (rank + k) mod nRanks
+  LLA2aPeer peer[kLLA2aMaxRanks];
+  int64_t sendLine0[kLLA2aMaxRanks + 1], recvLine0[kLLA2aMaxRanks + 1];  // [1 .. nRanks]; [nRanks] = the totals
+};
+static_assert(sizeof(LLA2aWork) <= 4096, "LLA2aWork must fit the kernel-argument budget");
+
 // Byte offset of the (parity, source rank) slot inside an LL buffer.
 __host__ __device__ __forceinline__ size_t ll_slot_off(int parity, int src, int nRanks,
                                                        int linesPerSlot) {

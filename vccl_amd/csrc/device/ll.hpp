@@ -364,6 +364,114 @@ __device__ inline void ll_allgather(const LLWork& w) {
   ll_epoch_retire(w.comm, e);
 }
 
+// ---------------------------------------------------------------- all-to-all
+// One-hop LL all-to-all(v) (bytes): the reduce-scatter's write pattern without
+// the fold.  The block of ordered pair (me -> p) goes, as lines [0, ceil(B / 8)),
+// into slot (parity, me) at p, and p copies it out — for the pairs the host
+// marked "LL pair" (B <= the comm's per-pair limit, host/plan.cc ll_a2a_plan;
+// both ends decide on the same B).  A v-call's larger pairs travel in the FIFO
+// launch behind this one, so a rank may have nothing to say to a peer here:
+// line 0 of EVERY ordered pair is still stored once and seen once per launch —
+// the data line of an LL pair with B > 0, else the zero arrival token of the
+// header (thread 0 of the grid stores and polls the tokens) — so this launch
+// is an arrival barrier like every other LL launch of the comm.
+// The per-peer table (rotated to me: entry k = rank me + k) sits in LDS, filled
+// through constant indices like ll_load_parts.
+struct LLA2aTable {
+  LLA2aPeer p[kLLA2aMaxRanks];
+  char* buf[kLLA2aMaxRanks];
+  int64_t sendLine0[kLLA2aMaxRanks + 1], recvLine0[kLLA2aMaxRanks + 1];
+};
+__device__ __forceinline__ void ll_load_a2a(const LLA2aWork& w, LLA2aTable* sh) {
+#pragma unroll
+  for (int i = 0; i < kLLA2aMaxRanks; i++)
+    if ((int)threadIdx.x == i) {
+      sh->p[i] = w.peer[i];
+      sh->buf[i] = w.peerBuf[i];
+    }
+#pragma unroll
+  for (int i = 0; i <= kLLA2aMaxRanks; i++)
+    if ((int)threadIdx.x == 64 + i) {
+      sh->sendLine0[i] = w.sendLine0[i];
+      sh->recvLine0[i] = w.recvLine0[i];
+    }
+  __syncthreads();
+}
+
+__device__ inline void ll_alltoall(const LLA2aWork& w) {
+  __shared__ LLA2aTable sh;
+  ll_load_a2a(w, &sh);
+  const uint32_t e = ll_epoch_of(w.comm);
+  const int parity = (int)(e & 1);
+  const int n = w.nRanks, me = w.rank;
+  const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t gthreads = (int64_t)gridDim.x * blockDim.x;
+  const size_t mySlot = ll_slot_off(parity, me, n, w.linesPerSlot);
+  // Write phase: one index over the concatenated send lines of the LL pairs
+  // (peers me+1 .. me+n-1), so every peer's stores are in flight together.
+  const int64_t sendLines = sh.sendLine0[n];
+  int k = 1;
+  for (int64_t l = gtid; l < sendLines; l += gthreads) {
+    while (k + 1 < n && l >= sh.sendLine0[k + 1]) k++;
+    const LLA2aPeer& p = sh.p[k];
+    const int64_t pl = l - sh.sendLine0[k];
+    const uint64_t v = ll_load8(p.send, pl, p.sendBytes);
+    u32x4 line;
+    line.x = (uint32_t)v;
+    line.y = e;
+    line.z = (uint32_t)(v >> 32);
+    line.w = e;
+    // lanes of one wave may sit in different peers' blocks: one peer's buffer
+    // per store instruction (sys_addr takes one base per wave)
+    for (int j = 1; j < n; j++) {
+      if (j != k) continue;
+      const SysAddr d = sys_addr(sh.buf[j] + mySlot + pl * 16);
+      __builtin_amdgcn_raw_buffer_store_b128(line, d.r, d.voff, 0, kSysAux);
+    }
+  }
+  if (gtid == 0) {  // the zero tokens: line 0 of my slot at every peer that gets no data line 0
+    u32x4 line;
+    line.x = 0;
+    line.y = e;
+    line.z = 0;
+    line.w = e;
+    for (int j = 1; j < n; j++) {
+      if (sh.p[j].sendLL && sh.p[j].sendBytes > 0) continue;
+      const SysAddr d = sys_addr(sh.buf[j] + mySlot);
+      __builtin_amdgcn_raw_buffer_store_b128(line, d.r, d.voff, 0, kSysAux);
+    }
+  }
+  // The self block: a local copy (nothing when it is already in place).
+  if (sh.p[0].sendLL && sh.p[0].recv != sh.p[0].send) {
+    const int64_t nb = sh.p[0].sendBytes;
+    for (int64_t l = gtid; l < (nb + 7) / 8; l += gthreads)
+      ll_store8(sh.p[0].recv, l, nb, ll_load8(sh.p[0].send, l, nb));
+  }
+  // Read phase: the same flattening over the recv lines.
+  const int64_t recvLines = sh.recvLine0[n];
+  bool ok = true;
+  k = 1;
+  for (int64_t l = gtid; l < recvLines && ok; l += gthreads) {
+    while (k + 1 < n && l >= sh.recvLine0[k + 1]) k++;
+    const LLA2aPeer& p = sh.p[k];
+    const int64_t pl = l - sh.recvLine0[k];
+    const int q = me + k < n ? me + k : me + k - n;
+    uint64_t x;
+    ok = ll_read_line(w.localBuf + ll_slot_off(parity, q, n, w.linesPerSlot) + pl * 16, e, w.comm, &x);
+    if (!ok) break;
+    ll_store8(p.recv, pl, p.recvBytes, x);
+  }
+  if (gtid == 0 && ok) {  // ... and every peer's line 0 that was not read as data
+    for (int j = 1; j < n; j++) {
+      if (sh.p[j].recvLL && sh.p[j].recvBytes > 0) continue;
+      const int q = me + j < n ? me + j : me + j - n;
+      uint64_t x;
+      if (!ll_read_line(w.localBuf + ll_slot_off(parity, q, n, w.linesPerSlot), e, w.comm, &x)) break;
+    }
+  }
+  ll_epoch_retire(w.comm, e);
+}
+
 // ------------------------------------------------------ broadcast and reduce
 // One-hop rooted collectives: part i's lines sit at [line0_i, line0_i +
 // ceil(nbytes_i / 8)) of the slot (parity, writer) and each part has its own

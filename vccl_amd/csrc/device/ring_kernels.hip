@@ -165,6 +165,13 @@ __global__ __launch_bounds__(256) void k_ll_reduce(LLWork w) {
   ll_reduce<Fn>(w);
 }
 
+#if VCCL_KT == 0  // K_U8: the byte-copy object also holds the one-hop LL all-to-all
+__global__ __launch_bounds__(256) void k_ll_alltoall(LLA2aWork w) { ll_alltoall(w); }
+hipError_t ll_a2a_launch(const LLA2aWork& w, int grid, hipStream_t stream, hipEvent_t stop) {
+  return launch_k(k_ll_alltoall, dim3(grid), dim3(256), stream, stop, w);
+}
+#endif
+
 template <>
 hipError_t ll_launch<VCCL_KT>(int coll, int devOp, const LLWork& w, int grid, hipStream_t stream,
                               hipEvent_t stop) {

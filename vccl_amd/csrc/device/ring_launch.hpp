@@ -56,6 +56,10 @@ inline hipError_t ring_launch_any(int variant, int coll, int devOp, const RingBa
 template <int K>
 hipError_t ll_launch(int coll, int devOp, const LLWork& w, int grid, hipStream_t stream, hipEvent_t stop);
 
+// One-hop LL all-to-all(v) (ll.hpp ll_alltoall): a byte copy, built once in
+// the K_U8 unit; 256-thread workgroups, `grid` of them.
+hipError_t ll_a2a_launch(const LLA2aWork& w, int grid, hipStream_t stream, hipEvent_t stop);
+
 // Direct collectives over the full mesh (direct.hpp): two-shot all-reduce,
 // one-hop reduce-scatter / all-gather, 1 .. kDirectMaxWorks calls per launch;
 // b.w.nBlocks workgroups (the largest part's) of kDirectThreads threads.

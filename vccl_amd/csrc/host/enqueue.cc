@@ -8,10 +8,13 @@
 // (group.cc:92-110, :393-506): calls between ncclGroupStart/End are queued per
 // thread and launched at the outermost ncclGroupEnd (launch_group).  ncclSend /
 // ncclRecv (collectives.cc:160-186) take the same road as p2p tasks;
-// ncclAllToAll(v) is an internal group of them.  The vccl*
+// ncclAllToAll(v) is an internal group of them — or, on a comm that opted into
+// the one-hop LL all-to-all (VCCL_LL_A2A_THRESHOLD), one task of its own whose
+// small pairs take one LL launch (launch.cc launch_comm_p2p).  The vccl*
 // extension exports at the end are wrappers over plan.h and launch.h.
 #include <algorithm>
 #include <cstring>
+#include <deque>
 #include <vector>
 
 #include "../../../include/vccl_device.h"
@@ -189,6 +192,59 @@ VCCL_EXPORT ncclResult_t ncclRecv(void* recvbuff, size_t count, ncclDataType_t d
   return p2p_check(false, "Recv", recvbuff, count, datatype, peer, comm, stream);
 }
 
+// The all-to-all of a comm whose one-hop LL all-to-all is on (llA2aMaxBytes >
+// 0): ONE queued task (kTaskA2a) — launch_group splits its pairs between the LL
+// launch and the p2p launch.  The per-pair checks of the expansion below, in
+// its order; the rows live in tl_a2a until the group has launched.
+static thread_local std::deque<A2aArgs> tl_a2a;
+static ncclResult_t all_to_all_task(const char* name, const void* sendbuff, const size_t* sendcounts,
+                                    const size_t* sdispls, void* recvbuff, const size_t* recvcounts,
+                                    const size_t* rdispls, size_t count, ncclDataType_t dt, ncclComm* comm,
+                                    hipStream_t stream) {
+  const size_t esz = (size_t)type_size(dt);
+  const int n = comm->nRanks;
+  A2aArgs a{};
+  a.uniform = sendcounts == nullptr;
+  auto pair_check = [&](const void* buff, size_t cnt) -> ncclResult_t {  // p2p_check_impl's, after its peer and type checks
+    if (!buff && cnt > 0) {
+      VWARN("%s : NULL buffer", name);
+      return ncclInvalidArgument;
+    }
+    if (*(volatile int*)comm->errorFlag) {
+      const ncclResult_t e = error_word_result(comm);
+      comm->asyncError = e;
+      return e;
+    }
+    return p2p_usable(comm, name);
+  };
+  ncclResult_t r = ncclSuccess;
+  for (int p = 0; p < n && r == ncclSuccess; p++) {
+    const size_t sc = sendcounts ? sendcounts[p] : count, so = sdispls ? sdispls[p] : (size_t)p * count;
+    const size_t rc = recvcounts ? recvcounts[p] : count, ro = rdispls ? rdispls[p] : (size_t)p * count;
+    a.sendBytes[p] = (int64_t)(sc * esz), a.sendOff[p] = (int64_t)(so * esz);
+    a.recvBytes[p] = (int64_t)(rc * esz), a.recvOff[p] = (int64_t)(ro * esz);
+    r = pair_check(sendbuff, sc);
+    if (r == ncclSuccess) r = pair_check(recvbuff, rc);
+  }
+  if (r != ncclSuccess) {
+    if (tl_groupDepth > 0 && tl_groupError == ncclSuccess) tl_groupError = r;
+    return r;
+  }
+  VINFO("%s: opCount %lx sendbuff %p recvbuff %p count %zu datatype %d comm %p [nranks=%d] stream %p", name,
+        (unsigned long)comm->opCount, sendbuff, recvbuff, count, (int)dt, (void*)comm, n, (void*)stream);
+  Task t{.coll = kTaskA2a, .sendbuff = sendbuff, .recvbuff = recvbuff, .count = count, .datatype = dt,
+         .devOp = OP_COPY, .root = 0, .comm = comm, .stream = stream};
+  if (tl_groupDepth > 0) {
+    tl_a2a.push_back(a);
+    t.a2a = &tl_a2a.back();  // a deque: earlier tasks' rows stay where they are
+    tl_tasks.push_back(t);
+    return ncclSuccess;
+  }
+  t.a2a = &a;
+  std::vector<Task> one{t};
+  return launch_group(one);
+}
+
 // RCCL's all-to-alls: an internal group of n sends and n recvs (the self block
 // a local copy).  counts / displacements in elements; NULL arrays = the
 // uniform all-to-all of `count` elements per pair.
@@ -207,6 +263,8 @@ static ncclResult_t all_to_all(const char* name, const void* sendbuff, const siz
   }
   const size_t esz = (size_t)type_size(dt);
   const int n = comm->nRanks;
+  if (comm->llA2aMaxBytes > 0 && n <= kOrderMaxRanks)
+    return all_to_all_task(name, sendbuff, sendcounts, sdispls, recvbuff, recvcounts, rdispls, count, dt, comm, stream);
   ncclGroupStart();
   for (int p = 0; p < n && r == ncclSuccess; p++) {
     const size_t sc = sendcounts ? sendcounts[p] : count, so = sdispls ? sdispls[p] : (size_t)p * count;
@@ -216,6 +274,7 @@ static ncclResult_t all_to_all(const char* name, const void* sendbuff, const siz
       r = p2p_check(false, name, recvbuff ? (char*)recvbuff + ro * esz : nullptr, rc, dt, p, comm, stream);
   }
   const ncclResult_t e = ncclGroupEnd();  // an inner group: launches only when this is the outermost
+  if (r == ncclSuccess) comm->a2aFifoPairs += 2 * (size_t)n;  // vcclCommA2aStats: every pair on the FIFOs
   return r != ncclSuccess ? r : e;
 }
 
@@ -288,9 +347,12 @@ VCCL_EXPORT ncclResult_t ncclGroupEnd(void) {
   if (err != ncclSuccess) {  // a call of the group failed: drop the whole group
     VWARN("ncclGroupEnd: a call in the group failed (%d); %zu queued calls not launched",
           (int)err, tasks.size());
+    tl_a2a.clear();
     return err;
   }
-  return launch_group(tasks);
+  const ncclResult_t r = launch_group(tasks);
+  tl_a2a.clear();  // the all-to-all tasks' rows: launched, no longer referenced
+  return r;
 }
 
 // nccl.h.in:472-473: ends the group like ncclGroupEnd but launches nothing;
@@ -303,6 +365,7 @@ VCCL_EXPORT ncclResult_t ncclGroupSimulateEnd(ncclSimInfo_t* simInfo) {
   if (--tl_groupDepth > 0) return ncclSuccess;
   tl_groupError = ncclSuccess;
   tl_tasks.clear();
+  tl_a2a.clear();
   if (simInfo) simInfo->estimatedTime = NCCL_UNDEF_FLOAT;
   return out_of_scope("ncclGroupSimulateEnd");
 }
@@ -575,6 +638,70 @@ VCCL_EXPORT ncclResult_t vcclLLRootedPlan(int coll, int nRanks, int rank, int nP
   };
   put(out.stores, stores);
   put(out.polls, polls);
+  return ncclSuccess;
+}
+
+// vccl_ext.h: a comm's VCCL_LL_A2A_THRESHOLD as it takes effect (host only).
+VCCL_EXPORT ncclResult_t vcclLLA2aMax(int64_t threshold, int64_t llSlotBytes, int llAllowed, int anyNet, int nRanks,
+                                      int hasP2p, int64_t* effective) {
+  if (!effective || llSlotBytes < 0 || nRanks < 1) return ncclInvalidArgument;
+  if (threshold < 0) threshold = param_int("LL_A2A_THRESHOLD", 0);
+  *effective = (int64_t)ll_a2a_max(threshold, llSlotBytes, llAllowed != 0, anyNet != 0, nRanks, hasP2p != 0);
+  return ncclSuccess;
+}
+
+// vccl_ext.h: one all-to-all(v) call's split between the LL launch and the
+// FIFO launch as `rank` runs it (host only).
+VCCL_EXPORT ncclResult_t vcclLLA2aPlan(int nRanks, int rank, const size_t* sendBytes, const size_t* recvBytes,
+                                       int uniform, int64_t llA2aMax, int64_t linesPerSlot, int* sendLL, int* recvLL,
+                                       int* launch, int64_t* stores, int64_t* polls, int* nResSends, int* resSends,
+                                       int* nResRecvs, int* resRecvs) {
+  if (nRanks < 2 || nRanks > kOrderMaxRanks || rank < 0 || rank >= nRanks || !sendBytes || !recvBytes ||
+      llA2aMax < 0 || linesPerSlot < 1 || llA2aMax > linesPerSlot * 8 || !sendLL || !recvLL || !launch || !stores ||
+      !polls || !nResSends || !resSends || !nResRecvs || !resRecvs)
+    return ncclInvalidArgument;
+  int64_t sb[kOrderMaxRanks], rb[kOrderMaxRanks];
+  for (int p = 0; p < nRanks; p++) {
+    if (sendBytes[p] > (size_t)1 << 60 || recvBytes[p] > (size_t)1 << 60) return ncclInvalidArgument;
+    if (uniform && (sendBytes[p] != sendBytes[0] || recvBytes[p] != sendBytes[0])) return ncclInvalidArgument;
+    sb[p] = (int64_t)sendBytes[p];
+    rb[p] = (int64_t)recvBytes[p];
+  }
+  LLA2aPlanOut out;
+  NCCLCHECK(ll_a2a_plan(nRanks, rank, sb, rb, uniform != 0, (uint64_t)llA2aMax, linesPerSlot, &out));
+  *launch = out.launch;
+  for (int p = 0; p < nRanks; p++) sendLL[p] = out.sendLL[p], recvLL[p] = out.recvLL[p];
+  auto put = [](const std::vector<LLRange>& v, int64_t* o) {  // nRanks - 1 ranges with a launch, else none
+    for (size_t k = 0; k < v.size(); k++) {
+      o[4 * k] = v[k].peer, o[4 * k + 1] = v[k].part, o[4 * k + 2] = v[k].line0, o[4 * k + 3] = v[k].line1;
+    }
+  };
+  put(out.stores, stores);
+  put(out.polls, polls);
+  *nResSends = (int)out.resSends.size();
+  *nResRecvs = (int)out.resRecvs.size();
+  std::copy(out.resSends.begin(), out.resSends.end(), resSends);
+  std::copy(out.resRecvs.begin(), out.resRecvs.end(), resRecvs);
+  return ncclSuccess;
+}
+
+VCCL_EXPORT ncclResult_t vcclCommA2aStats(ncclComm_t comm, unsigned long long* llLaunches, unsigned long long* llPairs,
+                                          unsigned long long* fifoPairs) {
+  NCCLCHECK(comm_check(comm, "vcclCommA2aStats"));
+  if (llLaunches) *llLaunches = comm->a2aLLLaunches;
+  if (llPairs) *llPairs = comm->a2aLLPairs;
+  if (fifoPairs) *fifoPairs = comm->a2aFifoPairs;
+  return ncclSuccess;
+}
+
+// A tuning / measurement knob: every rank must call it alike, between calls.
+VCCL_EXPORT ncclResult_t vcclCommSetA2aThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective) {
+  NCCLCHECK(comm_check(comm, "vcclCommSetA2aThreshold"));
+  if (bytes < 0) return ncclInvalidArgument;
+  comm->llA2aMaxBytes = ll_a2a_max_of(*comm, bytes, comm->nRanks, comm->p2pOff == kP2pOffNet,
+                                      comm->p2pConns != nullptr && comm->llBuf != nullptr &&
+                                          (int)comm->llPeer.size() >= comm->nRanks);
+  if (effective) *effective = (int64_t)comm->llA2aMaxBytes;
   return ncclSuccess;
 }
 

@@ -311,6 +311,19 @@ static CbdLite rs_cbd(const Task& t, int proto) {
 static int64_t ll_lines_of(const Task& t) {
   return ((int64_t)t.count * type_size(t.datatype) + 7) / 8;
 }
+// A bounded grid (256-thread workgroups, each thread looping over lines):
+// one workgroup per 256 lines, within the comm's CTA bounds (minCTAs /
+// maxCTAs, default 1 / 128), and never above VCCL_LL_MAX_BLOCKS (256): every
+// rank's LL workgroups must be resident at once for the peers' spins to
+// complete, so that co-residency cap is applied LAST (tests that
+// put 8 ranks on ONE GPU lower it).
+static int ll_grid(const ncclComm* comm, int64_t lines) {
+  int maxBlocks = (int)std::max<int64_t>(1, param_int("LL_MAX_BLOCKS", 256));
+  if (comm->shareBlockCap > 0) maxBlocks = std::min(maxBlocks, comm->shareBlockCap);
+  int grid = (int)std::max<int64_t>(1, (lines + 255) / 256);
+  grid = std::max(std::min(grid, comm->maxCTAs), comm->minCTAs);
+  return std::max(1, std::min(grid, maxBlocks));
+}
 static ncclResult_t launch_ll(const Task* ts, int nTasks, hipEvent_t stop) {
   const Task& t = ts[0];
   ncclComm* comm = t.comm;
@@ -355,17 +368,7 @@ static ncclResult_t launch_ll(const Task* ts, int nTasks, hipEvent_t stop) {
   const bool copy = is_copy_coll(t.coll);
   const int kt = copy ? K_U8 : kernel_type_of(t.devOp, (int)t.datatype);
   if (kt < 0) return ncclInvalidArgument;
-  // A bounded grid (256-thread workgroups, each thread looping over lines):
-  // one workgroup per 256 lines, within the comm's CTA bounds (minCTAs /
-  // maxCTAs, default 1 / 128), and never above VCCL_LL_MAX_BLOCKS (256): every
-  // rank's LL workgroups must be resident at once for the peers' spins to
-  // complete, so that co-residency cap is applied LAST (tests that
-  // put 8 ranks on ONE GPU lower it).
-  int maxBlocks = (int)std::max<int64_t>(1, param_int("LL_MAX_BLOCKS", 256));
-  if (comm->shareBlockCap > 0) maxBlocks = std::min(maxBlocks, comm->shareBlockCap);
-  int grid = (int)std::max<int64_t>(1, (lines + 255) / 256);
-  grid = std::max(std::min(grid, comm->maxCTAs), comm->minCTAs);
-  grid = std::max(1, std::min(grid, maxBlocks));
+  const int grid = ll_grid(comm, lines);
   const int devOp = copy ? OP_COPY : t.devOp;
   const hipError_t e = by_kernel_type(kt, [&]<int K>() { return ll_launch<K>(t.coll, devOp, w, grid, t.stream, stop); });
   if (e != hipSuccess) {
@@ -731,6 +734,116 @@ static ncclResult_t launch_p2p(const std::vector<Task>& ts) {
   return r;
 }
 
+// ------------------------------------------------------------ LL all-to-all
+// The LL launch of one ncclAllToAll(v) (ll.hpp ll_alltoall) on the call's
+// stream, ordered against the comm's other launches like a call outside a
+// group (launch_task).  The tables go in rotated to this rank, the LL pairs'
+// lines flattened in that order.  Plain ncclSend / ncclRecv never come here:
+// they are not collective — a peer outside the exchange launches nothing, so
+// the arrival barrier the slot reuse rests on (ll.hpp header) would not hold.
+static ncclResult_t launch_ll_a2a(const Task& t, const LLA2aPlanOut& plan) {
+  ncclComm* comm = t.comm;
+  const int n = comm->nRanks, me = comm->rank;
+  const A2aArgs& a = *t.a2a;
+  if (n > kLLA2aMaxRanks || !comm->llBuf || (int)comm->llPeer.size() < n) return ncclInternalError;
+  LLA2aWork w{};
+  w.comm = comm->devComm;
+  w.rank = me;
+  w.nRanks = n;
+  w.linesPerSlot = comm->llLines;
+  w.localBuf = comm->llBuf;
+  int64_t sl = 0, rl = 0;
+  for (int k = 0; k < n; k++) {
+    const int p = (me + k) % n;
+    w.peerBuf[k] = comm->llPeer[p];
+    LLA2aPeer& e = w.peer[k];
+    e.send = t.sendbuff ? (const char*)t.sendbuff + a.sendOff[p] : nullptr;
+    e.recv = t.recvbuff ? (char*)t.recvbuff + a.recvOff[p] : nullptr;
+    e.sendBytes = a.sendBytes[p];
+    e.recvBytes = a.recvBytes[p];
+    e.sendLL = plan.sendLL[p];
+    e.recvLL = plan.recvLL[p];
+    w.sendLine0[k] = sl;
+    w.recvLine0[k] = rl;
+    if (k == 0) continue;  // the self block is not part of the flattening
+    const int64_t s = e.sendLL ? (e.sendBytes + 7) / 8 : 0, r = e.recvLL ? (e.recvBytes + 7) / 8 : 0;
+    if (s > comm->llLines || r > comm->llLines) return ncclInternalError;
+    sl += s;
+    rl += r;
+  }
+  for (int k = n; k <= kLLA2aMaxRanks; k++) w.sendLine0[k] = sl, w.recvLine0[k] = rl;
+  const int grid = ll_grid(comm, std::max(sl, rl));
+  DeviceGuard dev(comm->device);
+  HIPCHECK(dev.status);
+  CaptureState cs{false, 0};
+  NCCLCHECK(stream_order(comm, t.stream, &cs));
+  const hipError_t e = ll_a2a_launch(w, grid, t.stream, stop_event(comm, cs));
+  if (e != hipSuccess) {
+    VWARN("LL all-to-all kernel launch failed: %s", hipGetErrorString(e));
+    return ncclUnhandledCudaError;
+  }
+  return stream_mark(comm, t.stream, cs);
+}
+
+// One comm's sends, recvs and all-to-all tasks of a group (call order): each
+// all-to-all's LL launch in call order, then the one p2p launch with the
+// plain sends and recvs and the all-to-alls' pairs above the limit, in call
+// order per peer — so matching by sweep is what it was.
+static ncclResult_t launch_comm_p2p(const std::vector<Task>& mine) {
+  if (std::none_of(mine.begin(), mine.end(), [](const Task& t) { return t.coll == kTaskA2a; }))
+    return launch_p2p(mine);
+  ncclComm* comm = mine[0].comm;
+  const int n = comm->nRanks, me = comm->rank;
+  // launch_p2p's refusal (an unmatched self send or recv), before any LL
+  // launch: a refused group launches nothing
+  std::vector<int64_t> selfSends, selfRecvs;
+  for (const Task& t : mine) {
+    if (t.coll == kTaskA2a) {
+      selfSends.push_back(t.a2a->sendBytes[me]);
+      selfRecvs.push_back(t.a2a->recvBytes[me]);
+    } else if (t.root == me) {
+      (t.coll == kTaskSend ? selfSends : selfRecvs).push_back((int64_t)t.count * type_size(t.datatype));
+    }
+  }
+  if (selfSends != selfRecvs) {
+    VWARN("ncclGroupEnd : a send to self needs its recv from self of the same length in the same group (rank %d); "
+          "none of this communicator's sends and recvs were launched", me);
+    comm->opCount += mine.size();
+    return ncclInvalidUsage;
+  }
+  std::vector<Task> fifo;
+  for (const Task& t : mine) {
+    if (t.coll != kTaskA2a) {
+      fifo.push_back(t);
+      continue;
+    }
+    const A2aArgs& a = *t.a2a;
+    LLA2aPlanOut plan;
+    if (ll_a2a_plan(n, me, a.sendBytes, a.recvBytes, a.uniform, comm->llA2aMaxBytes, comm->llLines, &plan) !=
+        ncclSuccess)
+      return ncclInternalError;
+    const size_t nFifo = plan.resSends.size() + plan.resRecvs.size();
+    comm->a2aLLPairs += 2 * (size_t)n - nFifo;
+    comm->a2aFifoPairs += nFifo;
+    if (plan.launch) {
+      comm->opCount += 2 * (size_t)n - nFifo;  // as the FIFO path counts them; whatever the outcome
+      comm->a2aLLLaunches++;
+      NCCLCHECK(launch_ll_a2a(t, plan));
+    }
+    for (int p = 0; p < n; p++) {  // the API's own expansion order: send p, recv p
+      Task s{.coll = kTaskSend, .sendbuff = t.sendbuff ? (const char*)t.sendbuff + a.sendOff[p] : nullptr,
+             .recvbuff = nullptr, .count = (size_t)a.sendBytes[p], .datatype = ncclUint8, .devOp = t.devOp,
+             .root = p, .comm = comm, .stream = t.stream};
+      Task r{.coll = kTaskRecv, .sendbuff = nullptr,
+             .recvbuff = t.recvbuff ? (char*)t.recvbuff + a.recvOff[p] : nullptr, .count = (size_t)a.recvBytes[p],
+             .datatype = ncclUint8, .devOp = t.devOp, .root = p, .comm = comm, .stream = t.stream};
+      if (!plan.sendLL[p]) fifo.push_back(s);
+      if (!plan.recvLL[p]) fifo.push_back(r);
+    }
+  }
+  return fifo.empty() ? ncclSuccess : launch_p2p(fifo);
+}
+
 static ncclResult_t launch_group_colls(std::vector<Task>& tasks) {
   ncclResult_t ret = ncclSuccess;
   const size_t n = tasks.size();
@@ -776,9 +889,9 @@ static ncclResult_t launch_group_colls(std::vector<Task>& tasks) {
 
 ncclResult_t launch_group(std::vector<Task>& tasks) {
   std::vector<Task> colls, p2p;
-  for (const Task& t : tasks) (is_p2p(t.coll) ? p2p : colls).push_back(t);
+  for (const Task& t : tasks) (is_p2p(t.coll) || t.coll == kTaskA2a ? p2p : colls).push_back(t);
   ncclResult_t ret = colls.empty() ? ncclSuccess : launch_group_colls(colls);
-  // per comm (first appearance): its sends and recvs behind its collectives
+  // per comm (first appearance): its sends, recvs and all-to-alls behind its collectives
   std::vector<char> done(p2p.size(), 0);
   for (size_t i = 0; i < p2p.size(); i++) {
     if (done[i]) continue;
@@ -788,7 +901,7 @@ ncclResult_t launch_group(std::vector<Task>& tasks) {
         mine.push_back(p2p[j]);
         done[j] = 1;
       }
-    const ncclResult_t r = launch_p2p(mine);
+    const ncclResult_t r = launch_comm_p2p(mine);
     if (ret == ncclSuccess) ret = r;
   }
   return ret;

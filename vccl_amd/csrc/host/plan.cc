@@ -474,6 +474,44 @@ ncclResult_t ll_rooted_plan(int coll, int nRanks, int rank, const std::vector<in
   return ncclSuccess;
 }
 
+// ------------------------------------------------------------ LL all-to-all
+uint64_t ll_a2a_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks, bool hasP2p) {
+  if (threshold <= 0 || llSlotBytes <= 0 || !llAllowed || anyNet || nRanks < 2 || nRanks > kOrderMaxRanks || !hasP2p)
+    return 0;
+  return (uint64_t)std::min(threshold, llSlotBytes);
+}
+
+ncclResult_t ll_a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const int64_t* recvBytes, bool uniform,
+                         uint64_t llA2aMax, int64_t linesPerSlot, LLA2aPlanOut* out) {
+  const int n = nRanks;
+  out->sendLL.assign(n, 0);
+  out->recvLL.assign(n, 0);
+  out->stores.clear();
+  out->polls.clear();
+  out->resSends.clear();
+  out->resRecvs.clear();
+  // uniform: every pair carries sendBytes[0]; all of them LL, or none
+  out->launch = llA2aMax > 0 && (!uniform || (sendBytes[0] > 0 && ll_a2a_pair(llA2aMax, sendBytes[0])));
+  for (int k = 0; k < n; k++) {
+    const int p = (rank + k) % n;
+    bool s = out->launch && ll_a2a_pair(llA2aMax, sendBytes[p]);
+    bool r = out->launch && ll_a2a_pair(llA2aMax, recvBytes[p]);
+    if (p == rank) s = r = s && r && sendBytes[p] == recvBytes[p];  // else the FIFO launch's copy (or its refusal)
+    out->sendLL[p] = s;
+    out->recvLL[p] = r;
+    if (p == rank || !out->launch) continue;
+    const int64_t sl = s ? (sendBytes[p] + 7) / 8 : 0, rl = r ? (recvBytes[p] + 7) / 8 : 0;
+    if (sl > linesPerSlot || rl > linesPerSlot) return ncclInvalidArgument;
+    out->stores.push_back(sl > 0 ? LLRange{p, 0, 0, sl} : LLRange{p, -1, 0, 1});
+    out->polls.push_back(rl > 0 ? LLRange{p, 0, 0, rl} : LLRange{p, -1, 0, 1});
+  }
+  for (int p = 0; p < n; p++) {
+    if (!out->sendLL[p]) out->resSends.push_back(p);
+    if (!out->recvLL[p]) out->resRecvs.push_back(p);
+  }
+  return ncclSuccess;
+}
+
 // ------------------------------------------------------------ point-to-point
 P2pSplit p2p_split(int64_t bytes, const P2pGeometry& g) {
   if (bytes <= 0) return P2pSplit{0, 0};

@@ -142,6 +142,41 @@ struct LLRootedPlanOut {
 ncclResult_t ll_rooted_plan(int coll, int nRanks, int rank, const std::vector<int>& roots,
                             const std::vector<int64_t>& bytes, int64_t linesPerSlot, LLRootedPlanOut* out);
 
+// ------------------------------------------------------------ LL all-to-all
+// A comm's VCCL_LL_A2A_THRESHOLD (bytes per ordered pair) as it takes effect:
+// clamped to what one LL slot holds; 0 without LL buffers, with LL excluded by
+// NCCL_PROTO, with a peer behind the net proxy, with fewer than 2 or more than
+// kOrderMaxRanks ranks, or on a comm without point-to-point connections (the
+// pairs above the limit need them).
+uint64_t ll_a2a_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks, bool hasP2p);
+// Pair rule: the ordered pair (writer -> reader) of B bytes travels by LL iff
+// llA2aMax > 0 && B <= llA2aMax (B = 0 counts as LL: its token is all it needs).
+// Both ends know B and the comm-wide constant, nothing else enters.
+inline bool ll_a2a_pair(uint64_t llA2aMax, int64_t bytes) { return llA2aMax > 0 && (uint64_t)bytes <= llA2aMax; }
+// One ncclAllToAll (uniform) / ncclAllToAllv call as `rank` runs it (device/
+// ll.hpp ll_alltoall).  Launch rule, identical on every rank: a uniform call
+// launches LL iff 0 < bytes per pair <= llA2aMax and then has no FIFO work at
+// all, else it takes the FIFO path whole; a v-call launches LL whenever
+// llA2aMax > 0 — peers may hold LL pairs among themselves and expect this
+// rank's arrival token — and its pairs above the limit follow in the FIFO
+// launch.  Without an LL launch no pair is LL.  Pair (r -> p)'s data occupies
+// lines [0, ceil(B / 8)) of slot (parity, r) at p; stores / polls list them as
+// LLRange{peer, 0, 0, lines} and the 1-line zero token of every other pair as
+// LLRange{peer, -1, 0, 1}, so line 0 of every ordered pair is written once and
+// read once per launch.  The self block is LL (a local copy in the LL kernel)
+// when the launch happens, both its lengths agree and fit the limit; otherwise
+// it stays a FIFO-launch copy.  resSends / resRecvs: the peers whose send /
+// recv stays on the FIFOs, in peer order.  ncclInvalidArgument when an LL pair
+// exceeds the slot.
+struct LLA2aPlanOut {
+  std::vector<char> sendLL, recvLL;  // per peer
+  bool launch = false;
+  std::vector<LLRange> stores, polls;
+  std::vector<int> resSends, resRecvs;
+};
+ncclResult_t ll_a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const int64_t* recvBytes, bool uniform,
+                         uint64_t llA2aMax, int64_t linesPerSlot, LLA2aPlanOut* out);
+
 // ------------------------------------------------------------ point-to-point
 // The plan of a group's ncclSend / ncclRecv calls of one comm on its per-peer
 // connections (device/p2p_types.hpp), restating the reference's queueing

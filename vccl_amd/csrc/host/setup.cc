@@ -372,7 +372,15 @@ ncclResult_t setup_local(int n, int minCTAs, int maxCTAs, CommSetup* s, SetupSiz
   // reference runs both on its ring under LL: protocol LL with Tree or Ring.
   s->llRootedMaxBytes = (size_t)ll_rooted_max(param_int("LL_ROOTED_THRESHOLD", 0), (int64_t)s->llLines * 8,
                                               (s->algoAllowed & kAllowLLRsAg) != 0, false, n);
+  // LL all-to-all (the small pairs of ncclAllToAll(v) in one hop): opt-in the
+  // same way, bytes per ordered pair; the pairs above it keep the p2p FIFOs
+  s->llA2aMaxBytes = ll_a2a_max_of(*s, param_int("LL_A2A_THRESHOLD", 0), n, false, n > 1 && s->p2pOff == kP2pOn);
   return ncclSuccess;
+}
+
+size_t ll_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool hasP2p) {
+  return (size_t)ll_a2a_max(threshold, (int64_t)s.llLines * 8, (s.algoAllowed & kAllowLLRsAg) != 0, anyNet, nRanks,
+                            hasP2p);
 }
 
 static bool same_gpu(const PeerId& a, const PeerId& b) { return a.hostHash == b.hostHash && a.busId == b.busId; }
@@ -396,7 +404,7 @@ ncclResult_t setup_mesh(int rank, const std::vector<PeerId>& peers, CommSetup* s
     // LL and the two-shot direct path need every peer's memory mapped
     // (full xGMI mesh): all-reduce takes the ring.  Net channels move
     // through the proxy, a few are enough (NCCL's net defaults use 2-4).
-    s->llMaxBytes = s->llRsAgMaxBytes = s->llRootedMaxBytes = 0;
+    s->llMaxBytes = s->llRsAgMaxBytes = s->llRootedMaxBytes = s->llA2aMaxBytes = 0;
     s->directMaxBytes = s->directRsAgMaxBytes = 0;
     s->ll128MinBytes = s->ll128MaxBytes = 0;
     if (s->algoForce == 4) s->algoForce = 1;  // LL128 lines need the xGMI mesh: SIMPLE

@@ -62,6 +62,10 @@ struct CommSetup {
   // (VCCL_LL_ROOTED_THRESHOLD, plan.h ll_rooted_max; default 0 = off; not part
   // of what vcclCommSetup reports)
   size_t llRootedMaxBytes = 0;
+  // Largest ordered pair of an ncclAllToAll(v) on the one-hop LL path
+  // (VCCL_LL_A2A_THRESHOLD, plan.h ll_a2a_max; default 0 = off; not part of
+  // what vcclCommSetup reports either)
+  size_t llA2aMaxBytes = 0;
 };
 enum { kP2pOn = 0, kP2pOffEnv = 1, kP2pOffRanks = 2, kP2pOffNet = 3 };
 
@@ -78,6 +82,10 @@ struct SetupSizes {
 // been read.  nChannels is 0 and nothing is sized at nRanks == 1.  Fails
 // with algo_proto_select's result.
 ncclResult_t setup_local(int nRanks, int minCTAs, int maxCTAs, CommSetup* s, SetupSizes* z);
+
+// CommSetup::llA2aMaxBytes for a VCCL_LL_A2A_THRESHOLD of `threshold` on a comm
+// whose other fields are decided (setup_local; vcclCommSetA2aThreshold).
+size_t ll_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool hasP2p);
 
 // What a rank publishes about where it runs (a PeerMap's identity fields).
 struct PeerId {

@@ -50,6 +50,8 @@ EXPORTED = [
     "ncclSend", "ncclRecv", "ncclAllToAll", "ncclAllToAllv", "vcclP2pPlan",
     # one-hop LL broadcast / reduce: the selection with its threshold, and the launch's line layout
     "vcclRootedAlgo", "vcclLLRootedPlan",
+    # one-hop LL all-to-all: the per-pair limit, one call's LL / FIFO split, the counters, the live knob
+    "vcclLLA2aMax", "vcclLLA2aPlan", "vcclCommA2aStats", "vcclCommSetA2aThreshold",
     # out of scope, exported so libnccl-linked binaries load: WARN + ncclInvalidUsage
     "ncclGroupSimulateEnd",
     # memory / registration / scalable init (what a libnccl caller such as
@@ -169,6 +171,14 @@ def lib() -> ctypes.CDLL:
         "vcclLLRootedPlan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_size),
                              ctypes.c_int64, c_int, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int),
                              ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_int64)],
+        "vcclLLA2aMax": [ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int64)],
+        "vcclLLA2aPlan": [c_int, c_int, ctypes.POINTER(c_size), ctypes.POINTER(c_size), c_int, ctypes.c_int64,
+                          ctypes.c_int64, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int),
+                          ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
+        "vcclCommA2aStats": [vp, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong),
+                             ctypes.POINTER(ctypes.c_ulonglong)],
+        "vcclCommSetA2aThreshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
         "vcclAlgoSelection": [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(c_int),
                               ctypes.POINTER(c_int)],
         "vcclCommSetup": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(u64),
@@ -342,6 +352,38 @@ def ll_rooted_plan(coll: int, nranks: int, rank: int, parts, lines_per_slot: int
                                  st, ctypes.byref(np_), po), "vcclLLRootedPlan")
     return (list(line0), [tuple(st[4 * i:4 * i + 4]) for i in range(ns.value)],
             [tuple(po[4 * i:4 * i + 4]) for i in range(np_.value)])
+
+
+def ll_a2a_max(threshold: int | None, ll_slot_bytes: int, ll_allowed: bool = True, any_net: bool = False,
+               nranks: int = 8, has_p2p: bool = True) -> int:
+    """vcclLLA2aMax: the per-pair limit of the one-hop LL all-to-all as a comm
+    takes it (None: VCCL_LL_A2A_THRESHOLD from the environment; 0 = off)."""
+    eff = ctypes.c_int64()
+    check(lib().vcclLLA2aMax(-1 if threshold is None else threshold, ll_slot_bytes, int(ll_allowed), int(any_net),
+                             nranks, int(has_p2p), ctypes.byref(eff)), "vcclLLA2aMax")
+    return eff.value
+
+
+def ll_a2a_plan(nranks: int, rank: int, send_bytes, recv_bytes, uniform: bool, ll_a2a_max: int,
+                lines_per_slot: int) -> dict:
+    """vcclLLA2aPlan: one all-to-all(v) call's split between the LL launch and
+    the FIFO launch as `rank` runs it.  Returns launch, send_ll / recv_ll (per
+    peer), stores / polls = [(peer, part, first line, end line)] (part 0 data,
+    -1 the zero arrival token), res_sends / res_recvs (peers left to the FIFOs)."""
+    n = nranks
+    arr = ctypes.c_size_t * n
+    ci = ctypes.c_int * n
+    sll, rll, rs, rr = ci(), ci(), ci(), ci()
+    st, po = (ctypes.c_int64 * (4 * n))(), (ctypes.c_int64 * (4 * n))()
+    launch, nrs, nrr = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(lib().vcclLLA2aPlan(n, rank, arr(*send_bytes), arr(*recv_bytes), int(uniform), ll_a2a_max, lines_per_slot,
+                              sll, rll, ctypes.byref(launch), st, po, ctypes.byref(nrs), rs, ctypes.byref(nrr), rr),
+          "vcclLLA2aPlan")
+    k = n - 1 if launch.value else 0
+    return {"launch": bool(launch.value), "send_ll": [bool(x) for x in sll], "recv_ll": [bool(x) for x in rll],
+            "stores": [tuple(st[4 * i:4 * i + 4]) for i in range(k)],
+            "polls": [tuple(po[4 * i:4 * i + 4]) for i in range(k)],
+            "res_sends": list(rs[:nrs.value]), "res_recvs": list(rr[:nrr.value])}
 
 
 P2P_SEND, P2P_RECV, P2P_COPY = 0, 1, 2
@@ -519,6 +561,21 @@ class Comm:
         arr = ctypes.c_size_t * n
         check(lib().ncclAllToAllv(send, arr(*sendcounts), arr(*sdispls), recv, arr(*recvcounts), arr(*rdispls),
                                   dtype, self.handle, stream), "ncclAllToAllv")
+
+    def a2a_stats(self) -> tuple[int, int, int]:
+        """vcclCommA2aStats: (LL all-to-all launches, sends + recvs of this
+        comm's all-to-alls that went by LL, ... that went to the p2p FIFOs)."""
+        a, b, c = ctypes.c_ulonglong(), ctypes.c_ulonglong(), ctypes.c_ulonglong()
+        check(lib().vcclCommA2aStats(self.handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
+              "vcclCommA2aStats")
+        return a.value, b.value, c.value
+
+    def set_a2a_threshold(self, nbytes: int) -> int:
+        """vcclCommSetA2aThreshold: the per-pair LL all-to-all limit for later
+        calls (every rank alike); returns the effective limit."""
+        eff = ctypes.c_int64()
+        check(lib().vcclCommSetA2aThreshold(self.handle, nbytes, ctypes.byref(eff)), "vcclCommSetA2aThreshold")
+        return eff.value
 
     def coll_algo(self, coll: int, count: int, dtype: int) -> str:
         """vcclCommCollAlgo: "ring" | "ll" | "direct" | "ll128" | "one_rank" (coll 0 AR, 1 RS, 2 AG, 3 broadcast, 4 reduce)."""
