@@ -311,6 +311,7 @@ static CbdLite rs_cbd(const Task& t, int proto) {
 static int64_t ll_lines_of(const Task& t) {
   return ((int64_t)t.count * type_size(t.datatype) + 7) / 8;
 }
+static int64_t ll_lines_of(int64_t bytes) { return (bytes + 7) / 8; }  // ... of a payload given in bytes
 // A bounded grid (256-thread workgroups, each thread looping over lines):
 // one workgroup per 256 lines, within the comm's CTA bounds (minCTAs /
 // maxCTAs, default 1 / 128), and never above VCCL_LL_MAX_BLOCKS (256): every
@@ -650,6 +651,24 @@ ncclResult_t p2p_usable(const ncclComm* c, const char* api) {
   return ncclInvalidUsage;
 }
 
+// p2p_plan's rule: the k-th send to self needs the k-th recv from self, of the same length.
+static ncclResult_t check_self_pairs(const ncclComm* comm, const std::vector<Task>& ts) {
+  const int me = comm->rank;
+  std::vector<int64_t> selfSends, selfRecvs;
+  for (const Task& t : ts) {
+    if (t.coll == kTaskA2a) {
+      selfSends.push_back(t.a2a->sendBytes[me]);
+      selfRecvs.push_back(t.a2a->recvBytes[me]);
+    } else if (t.root == me) {
+      (t.coll == kTaskSend ? selfSends : selfRecvs).push_back((int64_t)t.count * type_size(t.datatype));
+    }
+  }
+  if (selfSends == selfRecvs) return ncclSuccess;
+  VWARN("ncclGroupEnd : a send to self needs its recv from self of the same length in the same group (rank %d); "
+        "none of this communicator's sends and recvs were launched", me);
+  return ncclInvalidUsage;
+}
+
 // The sends and recvs of one comm's group (call order), as 1 .. launches of
 // the p2p kernel on the first task's stream, the other tasks' streams joined
 // around them exactly as launch_runs does.
@@ -673,12 +692,8 @@ static ncclResult_t launch_p2p(const std::vector<Task>& ts) {
   int gCap = std::max(1, comm->maxCTAs / 2);
   if (comm->shareBlockCap > 0) gCap = std::max(1, std::min(gCap, comm->shareBlockCap / 2));
   P2pPlanOut plan;
-  const ncclResult_t pr = p2p_plan(comm->rank, n, calls, geo, (comm->minCTAs + 1) / 2, gCap, kP2pMaxWorks, &plan);
-  if (pr != ncclSuccess) {
-    VWARN("ncclGroupEnd : a send to self needs its recv from self of the same length in the same group (rank %d); "
-          "none of this communicator's sends and recvs were launched", comm->rank);
-    return pr;
-  }
+  NCCLCHECK(check_self_pairs(comm, ts));  // the one refusal p2p_plan has
+  NCCLCHECK(p2p_plan(comm->rank, n, calls, geo, (comm->minCTAs + 1) / 2, gCap, kP2pMaxWorks, &plan));
   if (plan.items.empty()) return ncclSuccess;  // zero-byte messages and in-place self pairs only
   DeviceGuard dev(comm->device);
   HIPCHECK(dev.status);
@@ -766,7 +781,7 @@ static ncclResult_t launch_ll_a2a(const Task& t, const LLA2aPlanOut& plan) {
     w.sendLine0[k] = sl;
     w.recvLine0[k] = rl;
     if (k == 0) continue;  // the self block is not part of the flattening
-    const int64_t s = e.sendLL ? (e.sendBytes + 7) / 8 : 0, r = e.recvLL ? (e.recvBytes + 7) / 8 : 0;
+    const int64_t s = e.sendLL ? ll_lines_of(e.sendBytes) : 0, r = e.recvLL ? ll_lines_of(e.recvBytes) : 0;
     if (s > comm->llLines || r > comm->llLines) return ncclInternalError;
     sl += s;
     rl += r;
@@ -794,20 +809,8 @@ static ncclResult_t launch_comm_p2p(const std::vector<Task>& mine) {
     return launch_p2p(mine);
   ncclComm* comm = mine[0].comm;
   const int n = comm->nRanks, me = comm->rank;
-  // launch_p2p's refusal (an unmatched self send or recv), before any LL
-  // launch: a refused group launches nothing
-  std::vector<int64_t> selfSends, selfRecvs;
-  for (const Task& t : mine) {
-    if (t.coll == kTaskA2a) {
-      selfSends.push_back(t.a2a->sendBytes[me]);
-      selfRecvs.push_back(t.a2a->recvBytes[me]);
-    } else if (t.root == me) {
-      (t.coll == kTaskSend ? selfSends : selfRecvs).push_back((int64_t)t.count * type_size(t.datatype));
-    }
-  }
-  if (selfSends != selfRecvs) {
-    VWARN("ncclGroupEnd : a send to self needs its recv from self of the same length in the same group (rank %d); "
-          "none of this communicator's sends and recvs were launched", me);
+  // launch_p2p's refusal, before any LL launch: a refused group launches nothing
+  if (check_self_pairs(comm, mine) != ncclSuccess) {
     comm->opCount += mine.size();
     return ncclInvalidUsage;
   }
