@@ -194,7 +194,12 @@ ncclResult_t pncclGroupEnd(void);
 
 /* ---- broadcast: the ring broadcast (src/device/broadcast.h), the byte-copy
  * ring of the all-gather from one root (torch's DDP broadcasts its module
- * state with it) ---- */
+ * state with it).  On a communicator created with
+ * VCCL_DIRECT_ROOTED_THRESHOLD=<bytes> (default 0 = off) a broadcast or reduce
+ * of at most that many bytes — above the rooted LL path and the LL128 window —
+ * takes two hops on every link of the xGMI mesh instead: scatter + all-gather
+ * from the root, reduce-scatter + gather to the root (the reduce bit-identical
+ * to the ring's); NCCL_ALGO=Direct then takes that path at any size. ---- */
 /* nccl.h.in:326-329 (in place) */
 ncclResult_t  ncclBcast(void* buff, size_t count, ncclDataType_t datatype, int root,
     ncclComm_t comm, hipStream_t stream);

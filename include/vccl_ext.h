@@ -120,6 +120,46 @@
  *                     ranks.  A broadcast or reduce of at most that many
  *                     bytes takes vcclAlgoLL (automatic or forced LL); with 0
  *                     every call takes what vcclGroupPlanEx's policy gives it.
+ *   vcclRootedAlgoEx   vcclRootedAlgo plus the rooted direct threshold (host
+ *                     only): directThreshold = the comm's
+ *                     VCCL_DIRECT_ROOTED_THRESHOLD in bytes (negative: read it
+ *                     from the environment; default 0 = off); directAllowed =
+ *                     the NCCL_ALGO list leaves Direct.  *directEffective (may
+ *                     be NULL) = the threshold as the comm takes it: 0 without
+ *                     mapped inboxes (policy[7]), with Direct excluded, with a
+ *                     net peer or above 8 ranks.  A broadcast or reduce takes,
+ *                     in this order, vcclAlgoLL (as vcclRootedAlgo), the LL128
+ *                     window, vcclAlgoDirect up to that many bytes, the ring;
+ *                     forced Direct (policy[0] = 3) takes vcclAlgoDirect at any
+ *                     size, but only with a non-zero effective threshold: with
+ *                     0 every call takes what vcclRootedAlgo gives it.
+ *   vcclDirectRootedPlan  one direct broadcast / reduce (root `root`, `count`
+ *                     elements of `datatype`) on inbox regions of regionBytes,
+ *                     as rank `rank` runs it (host only).
+ *                     geometry[4] = elements per chunk (a broadcast: bytes),
+ *                     chunks, the shard length of chunk `chunk`, shards;
+ *                     owners[shards] (may be NULL) = the owner of each shard
+ *                     (a reduce: n shards, shard o at rank o; a broadcast:
+ *                     n - 1 shards of whole 16-byte units, shard j at rank
+ *                     (root + 1 + j) mod n); steps = the ordered steps of
+ *                     chunk `chunk` (chunk < 0: none), 8 words each {kind,
+ *                     phase, peer, region, region offset, user offset, bytes,
+ *                     src}, offsets and lengths in bytes, the kernels' phase
+ *                     order (device/direct.hpp):
+ *                       kind 0 wait   flag (phase, peer) in my flag array;
+ *                       kind 1 store  into inbox region (phase, region = me)
+ *                              of `peer`, from src 0 sendbuff at the user
+ *                              offset, 1 my own region (0, root) (the
+ *                              broadcast's forward), 2 the fold of my shard
+ *                              (my input at the user offset and my regions
+ *                              (0, q), in the ring reduce's order);
+ *                       kind 2 read   my region (phase, region) -> recvbuff at
+ *                              the user offset;
+ *                       kind 3 post   my flag of `phase` at every peer;
+ *                       kind 4 local  src 0 sendbuff -> recvbuff (the
+ *                              broadcast root, out of place), src 2 the
+ *                              root's own shard folded into recvbuff.
+ *                     ncclInvalidArgument when the step count exceeds cap.
  *   vcclLLRootedPlan   the line layout of one rooted LL launch (broadcast or
  *                     reduce, 1..16 parts with a root and a byte count each) as
  *                     rank `rank` sees it (host only): line0[i]
@@ -192,7 +232,8 @@ typedef enum {
   vcclAlgoRing = 0,     /* SIMPLE ring over arc-balanced ring sets */
   vcclAlgoLL = 1,       /* one-hop LL: all-reduce (chain-tree fold), RS / AG, opt-in broadcast / reduce
                            (the opt-in LL all-to-all is per pair, not a vcclAlgo_t: vcclCommA2aStats) */
-  vcclAlgoDirect = 2,   /* two-shot direct all-reduce over the full mesh */
+  vcclAlgoDirect = 2,   /* direct over the full mesh: two-shot all-reduce, one-hop RS / AG, opt-in
+                           two-hop broadcast (scatter + all-gather) / reduce (reduce-scatter + gather) */
   vcclAlgoOneRank = 3,  /* nRanks == 1: copy / PreMulSum kernel */
   vcclAlgoLL128 = 4     /* ring over LL128 FIFOs (64-byte lines by default, in-line flags) */
 } vcclAlgo_t;
@@ -230,6 +271,12 @@ ncclResult_t vcclGroupPlanEx(int nCalls, const int* colls, const size_t* counts,
 ncclResult_t vcclAlgoSelection(const char* algo, const char* proto, int* force, int* allowed);
 ncclResult_t vcclRootedAlgo(int coll, size_t count, ncclDataType_t datatype, int nRanks, const int64_t* policy,
                             int64_t threshold, int llAllowed, int anyNet, int64_t* effective, int* algo);
+ncclResult_t vcclRootedAlgoEx(int coll, size_t count, ncclDataType_t datatype, int nRanks, const int64_t* policy,
+                              int64_t threshold, int llAllowed, int anyNet, int64_t directThreshold,
+                              int directAllowed, int64_t* effective, int64_t* directEffective, int* algo);
+ncclResult_t vcclDirectRootedPlan(int coll, int nRanks, int rank, int root, size_t count, ncclDataType_t datatype,
+                                  int64_t regionBytes, int chunk, int cap, int64_t* geometry, int* owners,
+                                  int* nSteps, int64_t* steps);
 ncclResult_t vcclLLRootedPlan(int coll, int nRanks, int rank, int nParts, const int* roots, const size_t* bytes,
                               int64_t linesPerSlot, int cap, int64_t* line0, int* nStores, int64_t* stores,
                               int* nPolls, int64_t* polls);

@@ -313,6 +313,59 @@ int main() {
     rooted++;
   }
   unsetenv("VCCL_LL_ROOTED_THRESHOLD");
+  // the rooted direct selection (vcclRootedAlgoEx) and one call's geometry and
+  // steps (vcclDirectRootedPlan) on random policies, thresholds, regions and caps
+  long directRooted = 0;
+  for (int trial = 0; trial < 20000; trial++) {
+    const int n = (int)pick({0, 1, 2, 3, 4, 8, 9, 64, 65});
+    const int64_t pol[10] = {pick({0, 0, 1, 2, 3, 4, 5}), pick({0, 4096, 1 << 20, -1}), pick({0, 1 << 20}),
+                             pick({0, 4 << 20}), pick({0, 1}), 64 << 10, pick({0, 1 << 20}), pick({0, 1}),
+                             pick({0, 8 << 20}), pick({0, 64 << 20})};
+    if (rng() % 4 == 0) setenv("VCCL_DIRECT_ROOTED_THRESHOLD", junk[rng() % 11], 1);
+    else if (rng() % 2) setenv("VCCL_DIRECT_ROOTED_THRESHOLD", "65536", 1);
+    else unsetenv("VCCL_DIRECT_ROOTED_THRESHOLD");
+    int64_t eff = -7, deff = -7;
+    int algo = -7;
+    const int64_t dthr = pick({-1, 0, 1, 4096, 8 << 20, 1ll << 40});
+    const ncclResult_t r = vcclRootedAlgoEx((int)(rng() % 7) - 1, (size_t)pick({0, 1, 8, 4097, 1 << 20, 1 << 24}),
+                                            (ncclDataType_t)dts[rng() % 10], n, rng() % 16 ? pol : nullptr,
+                                            pick({-1, 0, 4096}), (int)(rng() % 2), (int)(rng() % 2), dthr,
+                                            (int)(rng() % 2), rng() % 2 ? &eff : nullptr, rng() % 2 ? &deff : nullptr,
+                                            rng() % 16 ? &algo : nullptr);
+    EXPECT(r == ncclSuccess || r == ncclInvalidArgument);
+    if (r == ncclSuccess) {
+      EXPECT(algo == vcclAlgoRing || algo == vcclAlgoLL || algo == vcclAlgoDirect || algo == vcclAlgoLL128);
+      EXPECT(deff == -7 || deff >= 0);
+      EXPECT(deff <= 0 || (pol[7] != 0 && n <= 8));
+    }
+    const int nr = (int)pick({1, 2, 3, 5, 8, 9}), coll = (int)pick({3, 4, 4, 3, 2});
+    const int64_t region = pick({0, 16, 32, 272, 8448, 2097408, 1ll << 41});
+    const size_t count = (size_t)pick({0, 1, 15, 4099, 100003, 1 << 22}) << (rng() % 64 == 0 ? 40 : 0);
+    const int chunk = (int)pick({-1, 0, 0, 1, 2, 1000});
+    const int cap = (int)pick({0, 1, 8, 4 * nr + 8, 200});
+    int64_t geo[4] = {-1, -1, -1, -1};
+    std::vector<int> own(9, -1);
+    std::vector<int64_t> st(8 * (size_t)cap + 1, -1);
+    int ns = -1;
+    const ncclResult_t q = vcclDirectRootedPlan(coll, nr, (int)(rng() % (nr + 1)), (int)(rng() % (nr + 1)), count,
+                                                (ncclDataType_t)dts[rng() % 10], region, chunk, cap,
+                                                rng() % 16 ? geo : nullptr, rng() % 4 ? own.data() : nullptr, &ns,
+                                                rng() % 8 ? st.data() : nullptr);
+    EXPECT(q == ncclSuccess || q == ncclInvalidArgument);
+    if (q == ncclSuccess) {
+      EXPECT(geo[0] >= 1 && geo[1] >= 1 && geo[3] == (coll == 4 ? nr : nr - 1) && ns >= 0 && ns <= cap);
+      EXPECT(chunk < 0 ? ns == 0 : geo[2] >= 1);
+      for (int i = 0; i < ns; i++) {
+        const int64_t* x = &st[8 * (size_t)i];
+        EXPECT(x[0] >= 0 && x[0] <= 4 && x[1] >= 0 && x[1] <= 1 && x[2] >= 0 && x[2] < nr && x[3] >= 0 && x[3] < nr);
+        EXPECT(x[4] == 0 && x[5] >= 0 && x[6] >= 0 && x[7] >= 0 && x[7] <= 2);
+        if (x[0] == 1 || x[0] == 2) EXPECT(x[6] <= region - 16);
+      }
+    }
+    EXPECT(st[8 * (size_t)cap] == -1 && own[8] == -1);  // nothing past cap steps or the shard count
+    directRooted++;
+  }
+  unsetenv("VCCL_DIRECT_ROOTED_THRESHOLD");
   // the LL all-to-all limit (vcclLLA2aMax) and one call's split (vcclLLA2aPlan)
   // on random byte matrices, limits, slots and invalid arguments
   long a2a = 0;
@@ -373,6 +426,7 @@ int main() {
   EXPECT(vcclCommSetA2aThreshold(nullptr, 4096, nullptr) == ncclInvalidArgument);
   printf("host_api_check: %ld all-to-all limits and plans\n", a2a);
   printf("host_api_check: %ld rooted selections and layouts\n", rooted);
+  printf("host_api_check: %ld rooted direct selections and plans\n", directRooted);
   printf("host_api_check: %ld p2p plans\n", p2pPlans);
   printf("host_api_check: %ld groups (%ld calls), %ld partitions, %ld selection strings, %ld setups (%ld refused), "
          "%d failures\n", groups, calls, parts, strs, setups, refusals, g_fail);

@@ -5,7 +5,11 @@ one-hop LL path alternating on ONE communicator (vcclCommSetAlgo), every row
 checked.  Per row: min and median us per call over --steps calls (default 50)
 after warm-up, each call timed by its own event pair, the max over ranks.
 
-    python tools/rooted_sweep.py [--min-bytes N] [--max-bytes N] [--steps K] [--ranks 2,4,8]
+    python tools/rooted_sweep.py [--min-bytes N] [--max-bytes N] [--steps K] [--ranks 2,4,8] [--direct]
+
+--direct: the ring against the two-hop direct path instead,
+128 KiB - 64 MiB by default, 20 calls per row, VCCL_DIRECT_ROOTED_THRESHOLD set
+to --max-bytes and VCCL_LL_ROOTED_THRESHOLD left unset.
 
 The parent spawns the rank processes (bench.py's launcher; ranks share a GPU
 when the box has fewer than ranks — then the rows are rehearsal rows: LL
@@ -27,9 +31,10 @@ def arg(name, default):
     return default
 
 
-MIN_BYTES = int(arg("--min-bytes", 8))
-MAX_BYTES = int(arg("--max-bytes", 128 << 10))
-STEPS = max(50, int(arg("--steps", 50)))
+DIRECT = "--direct" in sys.argv
+MIN_BYTES = int(arg("--min-bytes", 128 << 10 if DIRECT else 8))
+MAX_BYTES = int(arg("--max-bytes", 64 << 20 if DIRECT else 128 << 10))
+STEPS = max(20, int(arg("--steps", 20))) if DIRECT else max(50, int(arg("--steps", 50)))
 RANKS = [int(x) for x in arg("--ranks", "2,4,8").split(",")]
 WARMUP = 5
 
@@ -50,7 +55,9 @@ def parent():
     for n in RANKS:
         env = dict(os.environ)
         env.pop("WORLD_SIZE", None)
-        env["VCCL_LL_ROOTED_THRESHOLD"] = str(MAX_BYTES)
+        env.pop("VCCL_LL_ROOTED_THRESHOLD", None)
+        env.pop("VCCL_DIRECT_ROOTED_THRESHOLD", None)
+        env["VCCL_DIRECT_ROOTED_THRESHOLD" if DIRECT else "VCCL_LL_ROOTED_THRESHOLD"] = str(MAX_BYTES)
         env["ROOTED_SWEEP_CHILD"] = "1"
         env.setdefault("VCCL_SPIN_TIMEOUT_S", "30")
         plan = bench.rank_launch_plan(["--gpus", str(n)] + sys.argv[1:], env, script=os.path.abspath(__file__))
@@ -108,7 +115,7 @@ def child():
         x = ((torch.arange(cnt) * 7 + 13 * rank) % 11 + rank).float().cuda()  # small integers: any fold order is exact
         want = sum(((torch.arange(cnt) * 7 + 13 * r) % 11 + r).float() for r in range(world)).cuda()
         for op in ("broadcast", "reduce"):
-            for path in ("ring", "ll"):  # alternating on the one comm
+            for path in ("ring", "direct" if DIRECT else "ll"):  # alternating on the one comm
                 comm.set_algo(path)
                 coll, count, dt = (3, nb, U8) if op == "broadcast" else (4, cnt, F32)
                 algo = comm.coll_algo(coll, count, dt)

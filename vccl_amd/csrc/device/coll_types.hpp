@@ -125,6 +125,8 @@ struct DirectWork {
   // the direct path reproduces the ring's (= VCCL's) fold order exactly.
   CbdLite cbd;
   int64_t arChunk;
+  int root;              // broadcast / reduce: the root's rank
+  int pad;
 };
 
 // Shard length of a chunk of `cc` elements: ceil(cc / n) in 16-byte units.
@@ -135,10 +137,21 @@ struct DirectWork {
 __host__ __device__ __forceinline__ int64_t direct_shard_elts(int64_t cc, int n, int64_t eltAlign) {
   return ((cc + n - 1) / n + eltAlign - 1) / eltAlign * eltAlign;
 }
+// The rooted direct collectives (direct.hpp direct_broadcast_part /
+// direct_reduce_part; host/plan.cc direct_rooted_plan).  A reduce cuts a chunk
+// into n shards as the all-reduce does, shard o owned by rank o.  A broadcast
+// cuts it into n - 1 shards of whole 16-byte units, shard j owned by the j-th
+// rank after the root.
+__host__ __device__ __forceinline__ int direct_rooted_shards(bool reduce, int n) { return reduce ? n : n - 1; }
+__host__ __device__ __forceinline__ int direct_bcast_owner(int root, int j, int n) { return (root + 1 + j) % n; }
+__host__ __device__ __forceinline__ int direct_bcast_shard_of(int root, int rank, int n) {
+  return (rank - root - 1 + n) % n;  // rank != root
+}
 
 // Inbox: [2 phases][2 parities][nRanks sources][region]; flags likewise.
 // The all-reduce double-buffers its chunks by parity (direct.hpp); the
-// one-hop reduce-scatter / all-gather use parity 0.
+// one-hop reduce-scatter / all-gather and the rooted broadcast / reduce use
+// parity 0.
 constexpr int kDirectInboxRegions = 4;  // regions per source: phases x parities
 __host__ __device__ __forceinline__ size_t direct_region_off(int phase, int parity, int src, int nRanks,
                                                              int64_t regionBytes) {
@@ -159,7 +172,7 @@ struct DirectPart {
   void* recvbuff;
   uint64_t count;
   int nChunks;
-  int pad;
+  int root;              // broadcast / reduce: the part's root (roots may differ per part)
   int64_t chunkElts, blkElts;
   CbdLite cbd;
   int64_t arChunk;
@@ -169,8 +182,10 @@ struct DirectBatch {
   int nParts;
   DirectPart more[kDirectMaxWorks - 1];
 };
+// hipModuleLaunchKernel's by-value argument segment is 4 KiB
+static_assert(sizeof(DirectBatch) <= 4096, "DirectBatch must fit the kernel-argument budget");
 __host__ __device__ inline DirectPart direct_part_of(const DirectWork& w) {
-  return DirectPart{w.sendbuff, w.recvbuff, w.count, w.nChunks, 0, w.chunkElts, w.blkElts, w.cbd,
+  return DirectPart{w.sendbuff, w.recvbuff, w.count, w.nChunks, w.root, w.chunkElts, w.blkElts, w.cbd,
                     w.arChunk};
 }
 __host__ __device__ inline DirectWork direct_work_with(DirectWork w, const DirectPart& p) {
@@ -178,6 +193,7 @@ __host__ __device__ inline DirectWork direct_work_with(DirectWork w, const Direc
   w.recvbuff = p.recvbuff;
   w.count = p.count;
   w.nChunks = p.nChunks;
+  w.root = p.root;
   w.chunkElts = p.chunkElts;
   w.blkElts = p.blkElts;
   w.cbd = p.cbd;

@@ -42,11 +42,53 @@
 //    the readers' flags of chunk c were awaited;
 //  * the one-hop reduce-scatter / all-gather use parity 0 only and guard
 //    reuse with explicit acknowledgements (phase 3 below);
+//  * the rooted broadcast / reduce (direct_broadcast_part, direct_reduce_part)
+//    use parity 0 only and close every chunk with a flag round of phase 1;
 // and a region of one parity is rewritten by its writer's next chunk, part
 // or call only after its reader's flag for the previous use, so any of the
-// three kernels may follow any other on the same inbox (a peer one call
+// five kernels may follow any other on the same inbox (a peer one call
 // ahead writes only (0, *) regions, which the previous call has finished
 // reading before that peer could complete it).
+//
+// The reuse rule, which all five kernels obey:
+//   R1  a rank writes a (1, *) region or raises a (1, *) flag only after it
+//       has seen, in this call (this chunk), a phase-0 flag from every peer;
+//   R2  a rank leaves a call (a chunk) only after every peer has acknowledged
+//       reading what it wrote: it has seen every peer's (1, *) flag of that
+//       chunk, which the peer raises after its last read of its (0, *) regions.
+// Why that suffices, on one inbox, in any order of kernels.  Flags are per
+// (phase, parity, writer, block) and carry one epoch per chunk, the same
+// count in every kernel, so "chunk" below is a position in the comm's epoch
+// sequence, whichever kernel runs it.
+//  * (0, *) regions and flags of chunk k+1 are written by r at p only after r
+//    left chunk k (R2): p has read region (0, r) and seen flag (0, r) of chunk
+//    k (it raises its phase-1 flag after both).  [The all-reduce issues chunk
+//    k+1's scatter one parity over, before chunk k's gather: parity p's
+//    previous use is chunk k-1, left in the iteration before.]
+//  * (1, *) regions and flags of chunk k+1 are written by r at p only after r
+//    saw p's phase-0 flag of chunk k+1 (R1), which p raises after it left
+//    chunk k — after its last read of a (1, *) region (the all-reduce's
+//    gather, the reduce root's collect: both precede the rank's next post,
+//    whose barrier follows every wave's drained loads) and after it saw flag
+//    (1, r) of chunk k.
+//  Kernel by kernel:
+//    all-reduce      R1: fold + broadcast follow direct_wait(0); R2: the
+//                    gather's direct_wait(1) closes the chunk;
+//    reduce-scatter  writes no (1, *) region; its acknowledgement (1, me)
+//    / all-gather    follows direct_wait(0) (R1) and direct_wait(1) closes (R2);
+//    broadcast       the ROOT waits for no data, a non-root forwards after the
+//                    root's flag alone: what keeps either from running ahead
+//                    is the gather's direct_wait(0) on every peer before the
+//                    acknowledgement (R1) and the closing direct_wait(1) (R2).
+//                    A forward writes region (0, o) at q: q's previous read of
+//                    it was acknowledged in the previous chunk (R2);
+//    reduce          an owner writes region (1, o) AT THE ROOT and raises
+//                    (1, o) after direct_wait(0) (R1) — the root's phase-0
+//                    flag of this chunk follows its collect of the previous
+//                    one; direct_wait(1) closes the chunk on every rank (R2),
+//                    non-roots included, although they wait for no data.
+// In the LL protocol the job of the closing round needed the arrival token of
+// the rooted LL kernels (ll.hpp); here the closing flag round does it.
 #pragma once
 #include "coll_types.hpp"
 #include "ll.hpp"
@@ -241,12 +283,14 @@ __device__ __forceinline__ void direct_bcast(const char* src, char* const (&dst)
   }
 }
 
-// Wait until every peer's flag (phase, parity, peer, b) in MY flag array
-// equals e.  Lane p of wave 0 polls peer p; bounded like RingCtx::spin_ge.
-__device__ __forceinline__ bool direct_wait(const DirectWork& w, const char* myFlags, int phase,
-                                            int parity, int b, uint32_t e, int* shFail) {
+// Wait until the flag (phase, parity, peer, b) in MY flag array of every peer
+// in `mask` (bit p = rank p) equals e.  Lane p of wave 0 polls peer p; bounded
+// like RingCtx::spin_ge.  The masked form serves the direct broadcast, whose
+// owners wait for the root alone before they forward.
+__device__ __forceinline__ bool direct_wait_mask(const DirectWork& w, const char* myFlags, int phase,
+                                                 int parity, int b, uint32_t e, int* shFail, uint32_t mask) {
   const int t = threadIdx.x;
-  if (t < w.nRanks && t != w.rank) {
+  if (t < w.nRanks && t != w.rank && (mask >> t & 1u)) {
     const uint32_t* f = (const uint32_t*)(myFlags + direct_flag_off(phase, parity, t, b));
     const DevComm* comm = w.comm;
     uint64_t spins = 0, start = 0;
@@ -273,6 +317,11 @@ __device__ __forceinline__ bool direct_wait(const DirectWork& w, const char* myF
   }
   __syncthreads();
   return *shFail == 0;
+}
+// ... every peer's.
+__device__ __forceinline__ bool direct_wait(const DirectWork& w, const char* myFlags, int phase,
+                                            int parity, int b, uint32_t e, int* shFail) {
+  return direct_wait_mask(w, myFlags, phase, parity, b, e, shFail, ~0u);
 }
 
 // Every storing wave drains, then lane k of wave 0 raises flag (phase,
@@ -587,6 +636,232 @@ __device__ __forceinline__ void direct_allgather_part(const DirectWork& w, uint3
     }
     direct_post(w, P, 1, 0, b, e);
     (void)direct_wait(w, myFlags, 1, 0, b, e, &shFail);
+  }
+}
+
+// ----------------------------------------------------------------- broadcast
+// Two-hop broadcast over the full mesh: scatter from the root, all-gather
+// among the others, so every root link and then every peer link carries
+// S / (n - 1) instead of one link carrying S through n - 1 ring hand-offs.
+// Byte copies (the K_U8 unit), count = bytes.  A chunk is cut into n - 1
+// shards of whole 16-byte units (direct_shard_elts on n - 1); shard j is owned
+// by rank (root + 1 + j) mod n and fits one region.  Per chunk — the step list
+// of host/plan.cc direct_rooted_plan, kept side by side with this order:
+//   phase 1 (scatter): the root writes block b of shard j into region
+//            (0, root) of owner j, then raises (0, root, b) at every peer;
+//   phase 2 (forward): owner o waits for the ROOT's flag alone, writes its
+//            block from its own region (0, root) into region (0, o) of every
+//            other non-root (one read, n - 2 aligned stores) and, in a pass of
+//            its own, into its output (any alignment: the engine keeps 16-byte
+//            packs only when all destinations share one misalignment), then
+//            raises (0, o, b) at every peer, the root included;
+//   phase 3 (gather):  every rank waits for (0, *, b); a non-root copies the
+//            other owners' blocks from its regions (0, o) into its output, the
+//            root copies send -> recv locally when they differ;
+//   phase 4 (ack):     every rank raises (1, me, b) at every peer and waits for
+//            the n - 1 acknowledgements before the next chunk, part or call.
+// A non-root never dereferences sendbuff.  At n = 2 the single owner forwards
+// to nobody: one hop.  Regions and flags of parity 0 only.
+__device__ __forceinline__ void direct_broadcast_part(const DirectWork& w, uint32_t& e, int& shFail) {
+  using Fn = FnCopy<uint8_t>;
+  const Fn fn(0);
+  const DirectPeers& P = *w.peers;
+  const int n = w.nRanks, me = w.rank, root = w.root, b = blockIdx.x;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int64_t count = (int64_t)w.count;
+  char* myBuf = P.buf[me];
+  const char* myFlags = P.flags[me];
+  const int64_t rOff = (int64_t)b * w.blkElts;  // block offset in a region
+  const bool isRoot = me == root;
+  const int dr = root - me + (root < me ? n : 0);  // the root's distance after me (non-root: 1 .. n-1)
+  for (int c = 0; c < w.nChunks; c++) {
+    e = epoch_after(e);
+    if (shFail) continue;
+    const int64_t c0 = (int64_t)c * w.chunkElts;
+    const int64_t cc = count - c0 < w.chunkElts ? count - c0 : w.chunkElts;
+    const int64_t shardElts = direct_shard_elts(cc, n - 1, 16);
+    auto block_of = [&](int j, int64_t* off, int64_t* len) {  // block b of shard j, chunk-relative
+      int64_t shardEnd = (int64_t)(j + 1) * shardElts;
+      shardEnd = shardEnd < cc ? shardEnd : cc;
+      const int64_t lo = (int64_t)j * shardElts + rOff;
+      const int64_t hi = lo + w.blkElts < shardEnd ? lo + w.blkElts : shardEnd;
+      *off = lo;
+      *len = hi > lo ? hi - lo : 0;
+    };
+    char* out = (char*)w.recvbuff + c0;
+    if (isRoot) {
+      // Phase 1: scatter (workgroup b starts at shard b mod (n-1), so the
+      // root's workgroups feed all n-1 outgoing links).
+      const char* in = (const char*)w.sendbuff + c0;
+      for (int i = 0; i < n - 1; i++) {
+        const int j = (b + i) % (n - 1);
+        int64_t off, len;
+        block_of(j, &off, &len);
+        const char* s[kDirectMaxRanks] = {in + off};
+        char* d[kDirectMaxRanks] = {P.buf[direct_bcast_owner(root, j, n)] +
+                                    direct_region_off(0, 0, root, n, w.regionBytes) + rOff};
+        direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+      }
+    } else if (direct_wait_mask(w, myFlags, 0, 0, b, e, &shFail, 1u << root)) {
+      // Phase 2: forward my block to the other non-roots, then to my output.
+      int64_t off, len;
+      block_of(direct_bcast_shard_of(root, me, n), &off, &len);
+      const char* s[kDirectMaxRanks] = {myBuf + direct_region_off(0, 0, root, n, w.regionBytes) + rOff};
+      if (n > 2) {
+        char* d[kDirectMaxRanks];
+#pragma unroll
+        for (int j = 0; j < kDirectMaxRanks; j++) {
+          int k = j + 1;          // the j-th rank after me, the root skipped
+          k += k >= dr ? 1 : 0;
+          const int q = me + k < n ? me + k : me + k - n;
+          d[j] = j < n - 2 ? P.buf[q < n ? q : me] + direct_region_off(0, 0, me, n, w.regionBytes) + rOff : nullptr;
+        }
+        direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, n - 2, len, tid, nt);
+      }
+      char* d1[kDirectMaxRanks] = {out + off};
+      direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d1, 1, len, tid, nt);
+    }
+    direct_post(w, P, 0, 0, b, e);
+    // Phase 3: gather.
+    if (direct_wait(w, myFlags, 0, 0, b, e, &shFail)) {
+      if (isRoot) {
+        const char* in = (const char*)w.sendbuff + c0;
+        if (in != out) {
+          for (int j = 0; j < n - 1; j++) {
+            int64_t off, len;
+            block_of(j, &off, &len);
+            const char* s[kDirectMaxRanks] = {in + off};
+            char* d[kDirectMaxRanks] = {out + off};
+            direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+          }
+        }
+      } else {
+        for (int k = 1; k < n; k++) {
+          const int o = me + k < n ? me + k : me + k - n;
+          if (o == root) continue;
+          int64_t off, len;
+          block_of(direct_bcast_shard_of(root, o, n), &off, &len);
+          const char* s[kDirectMaxRanks] = {myBuf + direct_region_off(0, 0, o, n, w.regionBytes) + rOff};
+          char* d[kDirectMaxRanks] = {out + off};
+          direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+        }
+      }
+    }
+    // Phase 4: the closing acknowledgement round (reuse rule, header).
+    direct_post(w, P, 1, 0, b, e);
+    (void)direct_wait(w, myFlags, 1, 0, b, e, &shFail);
+  }
+}
+
+// -------------------------------------------------------------------- reduce
+// Two-hop reduce over the full mesh: reduce-scatter, then gather to the root,
+// so every link carries S / n in either step instead of one link into the
+// root carrying S.  A chunk is cut into n shards as the all-reduce cuts it
+// (direct_shard_elts), shard o owned by rank o, the root included.  Per chunk
+// — the step list of host/plan.cc direct_rooted_plan, kept side by side with
+// this order:
+//   phase 1 (scatter): rank r writes block b of its input for every foreign
+//            shard p into region (0, r) at p, then raises (0, r, b) at every
+//            peer;
+//   phase 2 (fold):    owner o waits for the n-1 flags (0, *, b) and folds its
+//            block from the n-1 regions and its own input in the ring reduce's
+//            order (reduce.h:12-55): an element's channel comes from the
+//            call's own cbd partition under SIMPLE, ringAt[ch mod nRings] is
+//            its ring, the fold starts at the root's successor on that ring
+//            and ends at the root, preOp on every input, postOp once (the
+//            root's rsOrder is known on the root only, so every owner derives
+//            the order from ringAt and the root's position).  The root folds
+//            straight into recvbuff, any other owner into region (1, o) OF THE
+//            ROOT.  Every owner then raises (1, o, b) at every peer — also the
+//            acknowledgement that o has finished reading its (0, *) regions;
+//   phase 3 (collect): every rank waits for (1, *, b); the root copies the
+//            blocks from its regions (1, o) into recvbuff (any alignment).
+// A non-root never writes recvbuff.  Regions and flags of parity 0 only.
+template <class Fn>
+__device__ void direct_reduce_part(const DirectWork& w, uint32_t& e, int& shFail) {
+  using T = typename Fn::EltType;
+  constexpr int64_t esz = (int64_t)sizeof(T);
+  const Fn fn(load_op_arg(w.redArgPtr, w.redArgBytes, w.redArg));
+  const DirectPeers& P = *w.peers;
+  const int n = w.nRanks, me = w.rank, root = w.root, b = blockIdx.x;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int64_t eltAlign = 16 / sizeof(T) ? 16 / sizeof(T) : 1;
+  const int64_t count = (int64_t)w.count;
+  char* myBuf = P.buf[me];
+  const char* myFlags = P.flags[me];
+  const int64_t inOff = (int64_t)b * w.blkElts * esz;  // block offset in a region
+  for (int c = 0; c < w.nChunks; c++) {
+    e = epoch_after(e);
+    if (shFail) continue;
+    const int64_t c0 = (int64_t)c * w.chunkElts;
+    const int64_t cc = count - c0 < w.chunkElts ? count - c0 : w.chunkElts;
+    const int64_t shardElts = direct_shard_elts(cc, n, eltAlign);
+    auto block_of = [&](int o, int64_t* off, int64_t* len) {  // block b of shard o, chunk-relative
+      int64_t shardEnd = (int64_t)(o + 1) * shardElts;
+      shardEnd = shardEnd < cc ? shardEnd : cc;
+      const int64_t lo = (int64_t)o * shardElts + (int64_t)b * w.blkElts;
+      const int64_t hi = lo + w.blkElts < shardEnd ? lo + w.blkElts : shardEnd;
+      *off = lo;
+      *len = hi > lo ? hi - lo : 0;
+    };
+    const char* in = (const char*)w.sendbuff + c0 * esz;
+    // Phase 1: scatter (workgroup b starts at peer offset 1 + b mod (n-1)).
+    for (int i = 0; i < n - 1; i++) {
+      const int k = 1 + (b + i) % (n - 1);
+      const int p = me + k < n ? me + k : me + k - n;
+      int64_t off, len;
+      block_of(p, &off, &len);
+      const char* s[kDirectMaxRanks] = {in + off * esz};
+      char* d[kDirectMaxRanks] = {P.buf[p] + direct_region_off(0, 0, me, n, w.regionBytes) + inOff};
+      direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+    }
+    direct_post(w, P, 0, 0, b, e);
+    // Phase 2: fold my block per channel part, in the order of the ring
+    // reduce to `root` on that part's ring.
+    if (direct_wait(w, myFlags, 0, 0, b, e, &shFail)) {
+      int64_t off, len;
+      block_of(me, &off, &len);
+      for (int64_t cur = 0; cur < len;) {
+        int64_t end;
+        const int ch = cbd_channel_of(w.cbd, c0 + off + cur, &end);
+        end -= c0 + off;
+        end = end < len ? end : len;
+        const int8_t* R = w.comm->ringAt[ch % w.comm->nRings];
+        int k = 0;  // the root's position on this ring
+#pragma unroll
+        for (int p = 0; p < kDirectMaxRanks; p++)
+          if (p < n && R[p] == root) k = p;
+        k = __builtin_amdgcn_readfirstlane(k);
+        const char* s[kDirectMaxRanks];
+        char* d[kDirectMaxRanks] = {
+            me == root ? (char*)w.recvbuff + (c0 + off + cur) * esz
+                       : P.buf[root] + direct_region_off(1, 0, me, n, w.regionBytes) + inOff + cur * esz};
+#pragma unroll
+        for (int j = 0; j < kDirectMaxRanks; j++) {
+          int pos = k + 1 + j;
+          pos = pos >= n ? pos - n : pos;
+          pos = pos >= n ? pos - n : pos;
+          const int q = j < n ? __builtin_amdgcn_readfirstlane(R[pos]) : me;
+          s[j] = q == me ? in + (off + cur) * esz
+                         : myBuf + direct_region_off(0, 0, q, n, w.regionBytes) + inOff + cur * esz;
+        }
+        direct_rc<Fn, kDirectUnroll, kSys, kSys, kSys>(fn, s, n, w.preOp ? n : 0, true, d, 1, end - cur,
+                                                       tid, nt);
+        cur = end;
+      }
+    }
+    direct_post(w, P, 1, 0, b, e);
+    // Phase 3: collect (the flag round closes the chunk on every rank).
+    if (direct_wait(w, myFlags, 1, 0, b, e, &shFail) && me == root) {
+      for (int k = 1; k < n; k++) {
+        const int o = me + k < n ? me + k : me + k - n;
+        int64_t off, len;
+        block_of(o, &off, &len);
+        const char* s[kDirectMaxRanks] = {myBuf + direct_region_off(1, 0, o, n, w.regionBytes) + inOff};
+        char* d[kDirectMaxRanks] = {(char*)w.recvbuff + (c0 + off) * esz};
+        direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+      }
+    }
   }
 }
 

@@ -3,8 +3,9 @@
 // hand-off — separate objects, built in parallel):
 // per reduction functor the ring all-reduce / reduce-scatter / reduce (one workgroup
 // per channel, enqueue.cc:1576-1666), the one-shot LL and the direct
-// (two-shot all-reduce, one-hop reduce-scatter) kernels; in the K_U8 unit
-// also the type-agnostic all-gathers (ring, LL, direct).
+// (two-shot all-reduce, one-hop reduce-scatter, two-hop reduce) kernels; in
+// the K_U8 unit also the type-agnostic all-gathers and broadcasts (ring, LL,
+// direct).
 #include <hip/hip_runtime.h>
 
 #include "dispatch.hpp"
@@ -208,13 +209,23 @@ __global__ __launch_bounds__(kDirectThreads) void k_direct_allgather(DirectBatch
   direct_batch(b, [](const DirectWork& w, uint32_t& e, int& f) { direct_allgather_part(w, e, f); });
 }
 
+template <int K>  // the K_U8 unit only
+__global__ __launch_bounds__(kDirectThreads) void k_direct_broadcast(DirectBatch b) {
+  direct_batch(b, [](const DirectWork& w, uint32_t& e, int& f) { direct_broadcast_part(w, e, f); });
+}
+template <class Fn>
+__global__ __launch_bounds__(kDirectThreads) void k_direct_reduce(DirectBatch b) {
+  direct_batch(b, [](const DirectWork& w, uint32_t& e, int& f) { direct_reduce_part<Fn>(w, e, f); });
+}
+
 template <>
 hipError_t direct_launch<VCCL_KT>(int coll, int devOp, const DirectBatch& b, hipStream_t stream,
                                   hipEvent_t stop) {
   using T = typename KTypeOf<VCCL_KT>::T;
   const dim3 grid(b.w.nBlocks), block(kDirectThreads);
-  if (coll == kCollAllGather) {
+  if (coll == kCollAllGather || coll == kCollBroadcast) {
     if constexpr (VCCL_KT == K_U8) {
+      if (coll == kCollBroadcast) return launch_k(k_direct_broadcast<K_U8>, grid, block, stream, stop, b);
       return launch_k(k_direct_allgather<K_U8>, grid, block, stream, stop, b);
     }
     return hipErrorInvalidValue;
@@ -223,6 +234,7 @@ hipError_t direct_launch<VCCL_KT>(int coll, int devOp, const DirectBatch& b, hip
   dispatch_op<T>(devOp, [&]<class Fn>() {
     if constexpr (!std::is_same<Fn, FnCopy<T>>::value) {
       err = coll == kCollAllReduce ? launch_k(k_direct_allreduce<Fn>, grid, block, stream, stop, b)
+            : coll == kCollReduce  ? launch_k(k_direct_reduce<Fn>, grid, block, stream, stop, b)
                                    : launch_k(k_direct_reducescatter<Fn>, grid, block, stream, stop, b);
     }
   });

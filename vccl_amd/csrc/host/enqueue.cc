@@ -610,6 +610,57 @@ VCCL_EXPORT ncclResult_t vcclRootedAlgo(int coll, size_t count, ncclDataType_t d
   return ncclSuccess;
 }
 
+// vccl_ext.h: vcclRootedAlgo plus the rooted direct threshold (host only).
+VCCL_EXPORT ncclResult_t vcclRootedAlgoEx(int coll, size_t count, ncclDataType_t datatype, int nRanks,
+                                          const int64_t* policy, int64_t threshold, int llAllowed, int anyNet,
+                                          int64_t directThreshold, int directAllowed, int64_t* effective,
+                                          int64_t* directEffective, int* algo) {
+  if (!policy || !algo || coll < kAllReduce || coll > kReduce || type_size(datatype) < 1 || nRanks < 1 ||
+      nRanks > kMaxRanks || policy[0] < 0 || policy[0] > 4 || policy[1] < 0)
+    return ncclInvalidArgument;
+  const int64_t* q = policy;
+  AlgoPolicy pol{nRanks, (int)q[0], q[1], (uint64_t)q[2], (uint64_t)q[3], q[4] != 0, (uint64_t)q[5],
+                 (uint64_t)q[6], q[7] != 0, (uint64_t)q[8], (uint64_t)q[9]};
+  if (threshold < 0) threshold = param_int("LL_ROOTED_THRESHOLD", 0);
+  if (directThreshold < 0) directThreshold = param_int("DIRECT_ROOTED_THRESHOLD", 0);
+  pol.llRootedMax = ll_rooted_max(threshold, pol.llSlotBytes, llAllowed != 0, anyNet != 0, nRanks);
+  pol.directRootedMax = direct_rooted_max(directThreshold, pol.direct, directAllowed != 0, anyNet != 0, nRanks);
+  if (effective) *effective = (int64_t)pol.llRootedMax;
+  if (directEffective) *directEffective = (int64_t)pol.directRootedMax;
+  const CallSize sz = call_size(coll, count, datatype);
+  *algo = public_algo(select_algo(pol, coll, sz.eltSize, sz.count));
+  return ncclSuccess;
+}
+
+// vccl_ext.h: one rooted direct call's geometry and the steps of one chunk
+// as `rank` runs it (host only).
+VCCL_EXPORT ncclResult_t vcclDirectRootedPlan(int coll, int nRanks, int rank, int root, size_t count,
+                                              ncclDataType_t datatype, int64_t regionBytes, int chunk, int cap,
+                                              int64_t* geometry, int* owners, int* nSteps, int64_t* steps) {
+  if ((coll != kBroadcast && coll != kReduce) || nRanks < 2 || nRanks > kDirectMaxRanks || rank < 0 ||
+      rank >= nRanks || root < 0 || root >= nRanks || type_size(datatype) < 1 || count == 0 ||
+      count > (size_t)1 << 56 || regionBytes < 32 || regionBytes > (int64_t)1 << 40 || !geometry || !nSteps ||
+      cap < 0 || (cap && !steps))
+    return ncclInvalidArgument;
+  const CallSize sz = call_size(coll, count, datatype);
+  DirectRootedPlanOut out;
+  NCCLCHECK(direct_rooted_plan(coll, nRanks, rank, root, sz.count, sz.eltSize, regionBytes, chunk, &out));
+  geometry[0] = out.chunkElts;
+  geometry[1] = out.nChunks;
+  geometry[2] = out.shardElts;
+  geometry[3] = (int64_t)out.owner.size();
+  if (owners)
+    for (size_t j = 0; j < out.owner.size(); j++) owners[j] = out.owner[j];
+  *nSteps = (int)out.steps.size();
+  if (*nSteps > cap) return ncclInvalidArgument;
+  for (size_t k = 0; k < out.steps.size(); k++) {
+    const DirectStep& d = out.steps[k];
+    const int64_t v[8] = {d.kind, d.phase, d.peer, d.region, d.regionOff, d.userOff, d.bytes, d.src};
+    for (int j = 0; j < 8; j++) steps[8 * k + j] = v[j];
+  }
+  return ncclSuccess;
+}
+
 // vccl_ext.h: the line layout of one rooted LL launch (host only).
 VCCL_EXPORT ncclResult_t vcclLLRootedPlan(int coll, int nRanks, int rank, int nParts, const int* roots,
                                           const size_t* bytes, int64_t linesPerSlot, int cap, int64_t* line0,

@@ -181,7 +181,8 @@ AlgoPolicy policy_of(const ncclComm* c) {
                     .llMax = c->llMaxBytes, .llRsAgMax = c->llRsAgMaxBytes,
                     .ll128 = c->ll128Buf != nullptr, .ll128Min = c->ll128MinBytes, .ll128Max = c->ll128MaxBytes,
                     .direct = c->dPeers != nullptr, .directMax = c->directMaxBytes,
-                    .directRsAgMax = c->directRsAgMaxBytes, .llRootedMax = c->llRootedMaxBytes};
+                    .directRsAgMax = c->directRsAgMaxBytes, .llRootedMax = c->llRootedMaxBytes,
+                    .directRootedMax = c->directRootedMaxBytes};
 }
 
 int kernel_type_of_call(int coll, int devOp, ncclDataType_t datatype) {
@@ -380,13 +381,16 @@ static ncclResult_t launch_ll(const Task* ts, int nTasks, hipEvent_t stop) {
 }
 
 // The direct work of one call (direct.hpp): two-shot all-reduce, one-hop
-// reduce-scatter / all-gather.  `blkForce` > 0 imposes the block length (a
-// fused batch's common geometry, launch_direct).
+// reduce-scatter / all-gather, two-hop broadcast / reduce (chunk and shard
+// from plan.cc direct_rooted_plan, whose step list is the kernels' phase
+// order).  `blkForce` > 0 imposes the block length (a fused batch's common
+// geometry, launch_direct).
 static ncclResult_t direct_work_of(const Task& t, DirectWork* out, int* ktOut, int* devOpOut, int64_t blkForce = 0) {
   ncclComm* comm = t.comm;
   const int n = comm->nRanks;
-  const bool ag = t.coll == kAllGather;
-  const auto [count, esz] = call_size(t.coll, t.count, t.datatype);  // all-gather: bytes
+  const bool ag = is_copy_coll(t.coll);
+  const bool rooted = t.coll == kBroadcast || t.coll == kReduce;
+  const auto [count, esz] = call_size(t.coll, t.count, t.datatype);  // all-gather / broadcast: bytes
   const int64_t eltAlign = std::max<int64_t>(1, 16 / esz);
   auto align_up = [](int64_t x, int64_t a) { return (x + a - 1) / a * a; };
   DirectWork w{};
@@ -396,9 +400,19 @@ static ncclResult_t direct_work_of(const Task& t, DirectWork* out, int* ktOut, i
   w.recvbuff = t.recvbuff;
   w.count = (uint64_t)count;
   w.rank = comm->rank;
+  w.root = rooted ? t.root : 0;
   const int64_t regionElts = (comm->dRegionBytes - 16) / esz;
   int64_t shard0;
-  if (t.coll == kAllReduce) {
+  if (rooted) {
+    if (n < 2 || t.root < 0 || t.root >= n) return ncclInternalError;
+    DirectRootedPlanOut rp;
+    if (direct_rooted_plan(t.coll, n, comm->rank, t.root, count, esz, comm->dRegionBytes, -1, &rp) != ncclSuccess)
+      return ncclInternalError;
+    w.chunkElts = rp.chunkElts;
+    shard0 = direct_shard_elts(w.chunkElts, (int)rp.owner.size(), eltAlign);
+    // reduce: the call's own partition under SIMPLE, as the ring reduce folds it
+    if (t.coll == kReduce) w.cbd = rs_cbd(t, kProtoSimple);
+  } else if (t.coll == kAllReduce) {
     // Chunk: as many elements as fit one shard per inbox region, a multiple
     // of n x 16 bytes; the shard of the largest chunk is cut into blocks.
     const int64_t chunkMax = regionElts * n / (n * eltAlign) * (n * eltAlign);

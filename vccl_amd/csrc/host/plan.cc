@@ -247,7 +247,10 @@ CbdPlan cbd_schedule(int coll, int64_t count, int64_t eltSize, int nRanks, int c
 // where the mesh has it; LL128 -> the LL128 ring where its FIFOs exist;
 // anything that does not fit falls through to the ring.  Broadcast and reduce
 // take their rings unless the comm opted into the one-hop rooted LL kernels
-// (llRootedMax, VCCL_LL_ROOTED_THRESHOLD; 0 = off).  A pure function of
+// (llRootedMax, VCCL_LL_ROOTED_THRESHOLD; 0 = off) or the two-hop rooted direct
+// kernels (directRootedMax, VCCL_DIRECT_ROOTED_THRESHOLD; 0 = off), in the
+// order of the other collectives: LL, the LL128 window, direct, ring; forced
+// Direct takes any size on a comm that opted in.  A pure function of
 // the comm's thresholds (AlgoPolicy), so the group planner can ask it for an
 // aggregate of calls as ncclPrepareTasks asks getAlgoInfo (enqueue.cc:398).
 // count in elements of eltSize (all-gather: any element type, or bytes)
@@ -262,8 +265,13 @@ int select_algo(const AlgoPolicy& p, int coll, int64_t eltSize, int64_t count) {
     if (p.llRootedMax > 0 && p.llSlotBytes > 0 && p.nRanks <= kOrderMaxRanks && bytes <= p.llRootedMax &&
         bytes <= (uint64_t)p.llSlotBytes && (p.algoForce == 0 || p.algoForce == 2))
       return kAlgoLL;
+    // the two-hop direct kernels, when the comm opted in (directRootedMax, off
+    // by default): forced Direct at any size, else behind the LL128 window
+    const bool directOk = p.directRootedMax > 0 && p.direct && p.nRanks <= kDirectMaxRanks;
+    if (directOk && p.algoForce == 3) return kAlgoDirect;
     // the rings of broadcast.h / reduce.h: SIMPLE or the LL128 window
-    return p.ll128 && p.ll128Max && bytes >= p.ll128Min && bytes <= p.ll128Max ? kAlgoRingLL128 : kAlgoRing;
+    if (p.ll128 && p.ll128Max && bytes >= p.ll128Min && bytes <= p.ll128Max) return kAlgoRingLL128;
+    return directOk && p.algoForce == 0 && bytes <= p.directRootedMax ? kAlgoDirect : kAlgoRing;
   }
   const uint64_t block = (uint64_t)(count * eltSize);
   // Reduce-scatter / all-gather: one rank's block must fit an LL slot; the
@@ -290,6 +298,10 @@ int select_algo(const AlgoPolicy& p, int coll, int64_t eltSize, int64_t count) {
 uint64_t ll_rooted_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks) {
   if (threshold <= 0 || llSlotBytes <= 0 || !llAllowed || anyNet || nRanks > kOrderMaxRanks) return 0;
   return (uint64_t)std::min(threshold, llSlotBytes);
+}
+uint64_t direct_rooted_max(int64_t threshold, bool inbox, bool directAllowed, bool anyNet, int nRanks) {
+  if (threshold <= 0 || !inbox || !directAllowed || anyNet || nRanks > kDirectMaxRanks) return 0;
+  return (uint64_t)threshold;
 }
 // The protocol VCCL runs a path's calls with: the one-hop LL stands in for
 // VCCL's LL (tree for the all-reduce, ring otherwise), the direct path for a
@@ -471,6 +483,75 @@ ncclResult_t ll_rooted_plan(int coll, int nRanks, int rank, const std::vector<in
     if (root0 < 0 || !ll_rooted_line0_is_data(reduce, rank, peer, root0)) out->stores.push_back(LLRange{peer, -1, 0, 1});
     if (root0 < 0 || !ll_rooted_line0_is_data(reduce, peer, rank, root0)) out->polls.push_back(LLRange{peer, -1, 0, 1});
   }
+  return ncclSuccess;
+}
+
+// ------------------------------------------------------------ rooted direct
+// The steps below are direct.hpp's phase order (direct_broadcast_part: scatter,
+// forward, gather, ack; direct_reduce_part: scatter, fold, collect), rank by
+// rank; the peer loops run in the kernels' rotation, (rank + k) mod n.
+ncclResult_t direct_rooted_plan(int coll, int nRanks, int rank, int root, int64_t count, int64_t eltSize,
+                                int64_t regionBytes, int chunk, DirectRootedPlanOut* out) {
+  const bool reduce = coll == kReduce;
+  const int n = nRanks, nShards = direct_rooted_shards(reduce, n);
+  const int64_t esz = eltSize, eltAlign = std::max<int64_t>(1, 16 / esz);
+  const int64_t regionElts = (regionBytes - 16) / esz / eltAlign * eltAlign;  // whole 16-byte units
+  if (regionElts < eltAlign || nShards < 1) return ncclInvalidArgument;
+  out->owner.clear();
+  out->steps.clear();
+  out->chunkElts = std::min<int64_t>(count, regionElts * nShards);
+  const int64_t nChunks = out->chunkElts > 0 ? (count + out->chunkElts - 1) / out->chunkElts : 0;
+  if (nChunks > INT32_MAX) return ncclInvalidArgument;
+  out->nChunks = (int)nChunks;
+  out->shardElts = 0;
+  for (int j = 0; j < nShards; j++) out->owner.push_back(reduce ? j : direct_bcast_owner(root, j, n));
+  if (chunk < 0) return ncclSuccess;
+  if (chunk >= out->nChunks) return ncclInvalidArgument;
+  const int64_t c0 = (int64_t)chunk * out->chunkElts, cc = std::min(out->chunkElts, count - c0);
+  const int64_t shard = direct_shard_elts(cc, nShards, eltAlign);
+  out->shardElts = shard;
+  auto off_of = [&](int j) { return (c0 + std::min((int64_t)j * shard, cc)) * esz; };          // user offset, bytes
+  auto len_of = [&](int j) { return (std::min((int64_t)(j + 1) * shard, cc) - std::min((int64_t)j * shard, cc)) * esz; };
+  auto& st = out->steps;
+  auto peers = [&](auto f) {
+    for (int k = 1; k < n; k++) f((rank + k) % n);
+  };
+  if (!reduce) {
+    if (rank == root) {
+      for (int j = 0; j < nShards; j++)  // scatter
+        st.push_back(DirectStep{kDStepStore, 0, out->owner[j], root, 0, off_of(j), len_of(j), kDSrcSend});
+    } else {
+      const int mine = direct_bcast_shard_of(root, rank, n);
+      st.push_back(DirectStep{kDStepWait, 0, root, 0, 0, 0, 0, 0});  // the root alone
+      peers([&](int q) {  // forward
+        if (q != root) st.push_back(DirectStep{kDStepStore, 0, q, rank, 0, off_of(mine), len_of(mine), kDSrcRegion});
+      });
+      st.push_back(DirectStep{kDStepRead, 0, rank, root, 0, off_of(mine), len_of(mine), 0});
+    }
+    st.push_back(DirectStep{kDStepPost, 0, 0, 0, 0, 0, 0, 0});
+    peers([&](int q) { st.push_back(DirectStep{kDStepWait, 0, q, 0, 0, 0, 0, 0}); });  // gather
+    if (rank == root) {
+      st.push_back(DirectStep{kDStepLocal, 0, rank, 0, 0, c0 * esz, cc * esz, kDSrcSend});
+    } else {
+      peers([&](int o) {
+        if (o == root) return;
+        const int j = direct_bcast_shard_of(root, o, n);
+        st.push_back(DirectStep{kDStepRead, 0, rank, o, 0, off_of(j), len_of(j), 0});
+      });
+    }
+    st.push_back(DirectStep{kDStepPost, 1, 0, 0, 0, 0, 0, 0});  // ack
+    peers([&](int q) { st.push_back(DirectStep{kDStepWait, 1, q, 0, 0, 0, 0, 0}); });
+    return ncclSuccess;
+  }
+  peers([&](int p) { st.push_back(DirectStep{kDStepStore, 0, p, rank, 0, off_of(p), len_of(p), kDSrcSend}); });  // scatter
+  st.push_back(DirectStep{kDStepPost, 0, 0, 0, 0, 0, 0, 0});
+  peers([&](int q) { st.push_back(DirectStep{kDStepWait, 0, q, 0, 0, 0, 0, 0}); });  // fold
+  if (rank == root) st.push_back(DirectStep{kDStepLocal, 0, rank, 0, 0, off_of(rank), len_of(rank), kDSrcFold});
+  else st.push_back(DirectStep{kDStepStore, 1, root, rank, 0, off_of(rank), len_of(rank), kDSrcFold});
+  st.push_back(DirectStep{kDStepPost, 1, 0, 0, 0, 0, 0, 0});
+  peers([&](int q) { st.push_back(DirectStep{kDStepWait, 1, q, 0, 0, 0, 0, 0}); });  // collect
+  if (rank == root)
+    peers([&](int o) { st.push_back(DirectStep{kDStepRead, 1, rank, o, 0, off_of(o), len_of(o), 0}); });
   return ncclSuccess;
 }
 

@@ -84,11 +84,16 @@ struct AlgoPolicy {
   bool direct = false;                     // every peer's inbox mapped
   uint64_t directMax = 0, directRsAgMax = 0;
   uint64_t llRootedMax = 0;                // largest broadcast / reduce on the one-hop LL path (0 = off)
+  uint64_t directRootedMax = 0;            // largest broadcast / reduce on the two-hop direct path (0 = off)
 };
 // A comm's VCCL_LL_ROOTED_THRESHOLD as it takes effect: clamped to what one
 // LL slot holds; 0 without LL buffers, with LL excluded by NCCL_PROTO, with a
 // peer behind the net proxy, or with more ranks than the fold-order tables.
 uint64_t ll_rooted_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks);
+// A comm's VCCL_DIRECT_ROOTED_THRESHOLD as it takes effect: 0 without mapped
+// inboxes, with Direct excluded by NCCL_ALGO, with a peer behind the net
+// proxy, or above kDirectMaxRanks ranks.
+uint64_t direct_rooted_max(int64_t threshold, bool inbox, bool directAllowed, bool anyNet, int nRanks);
 int select_algo(const AlgoPolicy& p, int coll, int64_t eltSize, int64_t count);
 int proto_of_algo(int algo);
 
@@ -141,6 +146,44 @@ struct LLRootedPlanOut {
 };
 ncclResult_t ll_rooted_plan(int coll, int nRanks, int rank, const std::vector<int>& roots,
                             const std::vector<int64_t>& bytes, int64_t linesPerSlot, LLRootedPlanOut* out);
+
+// ------------------------------------------------------------ rooted direct
+// One direct broadcast / reduce (device/direct.hpp direct_broadcast_part /
+// direct_reduce_part) as `rank` runs it: the chunk length, the shards of chunk
+// `chunk` and their owners, and the ordered steps of that chunk.  The step
+// order IS the kernel's phase order — the two are kept side by side and name
+// each other; host/launch.cc direct_work_of takes its geometry from here.
+// Lengths and offsets in bytes; a step covers a whole shard (workgroup b moves
+// bytes [b * blk, (b + 1) * blk) of it, so region offsets are 0).
+//   kDStepWait   {phase, peer = from}
+//   kDStepStore  {peer, phase, region = the writer's, regionOff, userOff, bytes, src}
+//                src kDSrcSend: sendbuff[userOff ..]; kDSrcRegion: my own region
+//                (0, root) (the broadcast's forward); kDSrcFold: the fold of my
+//                shard, my input at userOff and my regions (0, q) (the reduce)
+//   kDStepRead   {phase, region = the source's, regionOff, userOff, bytes}:
+//                my region -> recvbuff[userOff ..]
+//   kDStepPost   {phase}: my flag at every peer
+//   kDStepLocal  {userOff, bytes, src}: kDSrcSend: sendbuff -> recvbuff (the
+//                broadcast root, out of place); kDSrcFold: the root's own
+//                shard folded straight into recvbuff
+enum { kDStepWait = 0, kDStepStore = 1, kDStepRead = 2, kDStepPost = 3, kDStepLocal = 4 };
+enum { kDSrcSend = 0, kDSrcRegion = 1, kDSrcFold = 2 };
+struct DirectStep {
+  int kind, phase, peer, region;
+  int64_t regionOff, userOff, bytes;
+  int src;
+};
+struct DirectRootedPlanOut {
+  int64_t chunkElts = 0;   // elements per chunk (the last one shorter)
+  int nChunks = 0;
+  int64_t shardElts = 0;   // of chunk `chunk`
+  std::vector<int> owner;  // per shard
+  std::vector<DirectStep> steps;
+};
+// count in elements of eltSize (a broadcast: bytes, eltSize 1).  chunk < 0:
+// the geometry only.  ncclInvalidArgument when a region cannot hold 16 bytes.
+ncclResult_t direct_rooted_plan(int coll, int nRanks, int rank, int root, int64_t count, int64_t eltSize,
+                                int64_t regionBytes, int chunk, DirectRootedPlanOut* out);
 
 // ------------------------------------------------------------ LL all-to-all
 // A comm's VCCL_LL_A2A_THRESHOLD (bytes per ordered pair) as it takes effect:

@@ -14,7 +14,7 @@
 #include "../device/coll_types.hpp"
 #include "../device/ring_launch.hpp"  // kRingMaxThreads
 #include "core.h"                     // VWARN / VINFO / param_int
-#include "plan.h"                     // ll_rooted_max
+#include "plan.h"                     // ll_rooted_max, direct_rooted_max
 
 namespace vccl {
 
@@ -372,6 +372,10 @@ ncclResult_t setup_local(int n, int minCTAs, int maxCTAs, CommSetup* s, SetupSiz
   // reference runs both on its ring under LL: protocol LL with Tree or Ring.
   s->llRootedMaxBytes = (size_t)ll_rooted_max(param_int("LL_ROOTED_THRESHOLD", 0), (int64_t)s->llLines * 8,
                                               (s->algoAllowed & kAllowLLRsAg) != 0, false, n);
+  // Rooted direct (ncclBroadcast / ncclReduce in two hops on every link):
+  // opt-in the same way — no one-rank-per-GPU row exists to set a default.
+  s->directRootedMaxBytes = (size_t)direct_rooted_max(param_int("DIRECT_ROOTED_THRESHOLD", 0), s->dRegionBytes > 0,
+                                                      (s->algoAllowed & kAllowDirect) != 0, false, n);
   // LL all-to-all (the small pairs of ncclAllToAll(v) in one hop): opt-in the
   // same way, bytes per ordered pair; the pairs above it keep the p2p FIFOs
   s->llA2aMaxBytes = ll_a2a_max_of(*s, param_int("LL_A2A_THRESHOLD", 0), n, false, n > 1 && s->p2pOff == kP2pOn);
@@ -405,7 +409,7 @@ ncclResult_t setup_mesh(int rank, const std::vector<PeerId>& peers, CommSetup* s
     // (full xGMI mesh): all-reduce takes the ring.  Net channels move
     // through the proxy, a few are enough (NCCL's net defaults use 2-4).
     s->llMaxBytes = s->llRsAgMaxBytes = s->llRootedMaxBytes = s->llA2aMaxBytes = 0;
-    s->directMaxBytes = s->directRsAgMaxBytes = 0;
+    s->directMaxBytes = s->directRsAgMaxBytes = s->directRootedMaxBytes = 0;
     s->ll128MinBytes = s->ll128MaxBytes = 0;
     if (s->algoForce == 4) s->algoForce = 1;  // LL128 lines need the xGMI mesh: SIMPLE
     // ... so no LL128 FIFO is mapped: the local one is dropped too

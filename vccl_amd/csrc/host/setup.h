@@ -66,6 +66,10 @@ struct CommSetup {
   // (VCCL_LL_A2A_THRESHOLD, plan.h ll_a2a_max; default 0 = off; not part of
   // what vcclCommSetup reports either)
   size_t llA2aMaxBytes = 0;
+  // Largest ncclBroadcast / ncclReduce on the two-hop direct path
+  // (VCCL_DIRECT_ROOTED_THRESHOLD, plan.h direct_rooted_max; default 0 = off;
+  // not part of what vcclCommSetup reports either)
+  size_t directRootedMaxBytes = 0;
 };
 enum { kP2pOn = 0, kP2pOffEnv = 1, kP2pOffRanks = 2, kP2pOffNet = 3 };
 

@@ -50,6 +50,8 @@ EXPORTED = [
     "ncclSend", "ncclRecv", "ncclAllToAll", "ncclAllToAllv", "vcclP2pPlan",
     # one-hop LL broadcast / reduce: the selection with its threshold, and the launch's line layout
     "vcclRootedAlgo", "vcclLLRootedPlan",
+    # two-hop direct broadcast / reduce: the selection with both thresholds, and one call's geometry and steps
+    "vcclRootedAlgoEx", "vcclDirectRootedPlan",
     # one-hop LL all-to-all: the per-pair limit, one call's LL / FIFO split, the counters, the live knob
     "vcclLLA2aMax", "vcclLLA2aPlan", "vcclCommA2aStats", "vcclCommSetA2aThreshold",
     # out of scope, exported so libnccl-linked binaries load: WARN + ncclInvalidUsage
@@ -168,6 +170,12 @@ def lib() -> ctypes.CDLL:
                                ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
         "vcclRootedAlgo": [c_int, c_size, c_int, c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, c_int, c_int,
                            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int)],
+        "vcclRootedAlgoEx": [c_int, c_size, c_int, c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, c_int, c_int,
+                             ctypes.c_int64, c_int, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                             ctypes.POINTER(c_int)],
+        "vcclDirectRootedPlan": [c_int, c_int, c_int, c_int, c_size, c_int, ctypes.c_int64, c_int, c_int,
+                                 ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                 ctypes.POINTER(ctypes.c_int64)],
         "vcclLLRootedPlan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_size),
                              ctypes.c_int64, c_int, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int),
                              ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_int64)],
@@ -334,6 +342,50 @@ def rooted_algo(coll: int, count: int, dtype: int, nranks: int, policy: dict, th
     check(lib().vcclRootedAlgo(coll, count, dtype, nranks, pol, -1 if threshold is None else threshold,
                                int(ll_allowed), int(any_net), ctypes.byref(eff), ctypes.byref(a)), "vcclRootedAlgo")
     return ALGO_NAMES[a.value], eff.value
+
+
+def rooted_algo_ex(coll: int, count: int, dtype: int, nranks: int, policy: dict, threshold: int | None = None,
+                   ll_allowed: bool = True, any_net: bool = False, direct_threshold: int | None = None,
+                   direct_allowed: bool = True) -> tuple[str, int, int]:
+    """vcclRootedAlgoEx: (path, effective LL threshold, effective direct
+    threshold) of one call on `policy` (POLICY_FIELDS) plus the rooted LL and
+    rooted direct thresholds in bytes as a comm would take them (None:
+    VCCL_LL_ROOTED_THRESHOLD / VCCL_DIRECT_ROOTED_THRESHOLD from the
+    environment)."""
+    pol = (ctypes.c_int64 * 10)(*[int(policy[k]) for k in POLICY_FIELDS])
+    eff, deff, a = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
+    check(lib().vcclRootedAlgoEx(coll, count, dtype, nranks, pol, -1 if threshold is None else threshold,
+                                 int(ll_allowed), int(any_net), -1 if direct_threshold is None else direct_threshold,
+                                 int(direct_allowed), ctypes.byref(eff), ctypes.byref(deff), ctypes.byref(a)),
+          "vcclRootedAlgoEx")
+    return ALGO_NAMES[a.value], eff.value, deff.value
+
+
+DIRECT_STEP_KINDS = ("wait", "store", "read", "post", "local")
+DIRECT_STEP_SRCS = ("send", "region", "fold")
+
+
+def direct_rooted_plan(coll: int, nranks: int, rank: int, root: int, count: int, dtype: int, region_bytes: int,
+                       chunk: int = -1):
+    """vcclDirectRootedPlan: one direct broadcast (coll 3) / reduce (coll 4) as
+    `rank` runs it on inbox regions of region_bytes.  Returns a dict: chunk_elts
+    (a broadcast: bytes), n_chunks, shard_elts (of `chunk`), owners (per shard)
+    and steps, the ordered steps of `chunk` (-1: none) as tuples (kind, phase,
+    peer, region, region offset, user offset, bytes, src) with kind from
+    DIRECT_STEP_KINDS, src from DIRECT_STEP_SRCS and offsets / lengths in bytes."""
+    cap = 4 * nranks + 8
+    geo = (ctypes.c_int64 * 4)()
+    owners = (ctypes.c_int * nranks)()
+    steps = (ctypes.c_int64 * (8 * cap))()
+    ns = ctypes.c_int()
+    check(lib().vcclDirectRootedPlan(coll, nranks, rank, root, count, dtype, region_bytes, chunk, cap, geo, owners,
+                                     ctypes.byref(ns), steps), "vcclDirectRootedPlan")
+    out = []
+    for i in range(ns.value):
+        k, ph, peer, reg, roff, uoff, nb, src = steps[8 * i:8 * i + 8]
+        out.append((DIRECT_STEP_KINDS[k], ph, peer, reg, roff, uoff, nb, DIRECT_STEP_SRCS[src]))
+    return {"chunk_elts": geo[0], "n_chunks": geo[1], "shard_elts": geo[2], "owners": list(owners[:geo[3]]),
+            "steps": out}
 
 
 def ll_rooted_plan(coll: int, nranks: int, rank: int, parts, lines_per_slot: int):
