@@ -276,8 +276,12 @@ ncclResult_t pncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, in
  * elements; in place (sendbuff == recvbuff) is ncclInvalidArgument.  On a
  * communicator created with VCCL_LL_A2A_THRESHOLD=<bytes per pair> (default 0
  * = off) every ordered pair of at most that many bytes travels in one one-hop
- * LL launch per call and only the larger pairs stay sends and recvs; plain
- * ncclSend / ncclRecv never take that path (they are not collective). */
+ * LL launch per call and only the larger pairs stay sends and recvs; with
+ * VCCL_DIRECT_A2A_THRESHOLD=<bytes per pair> (default 0 = off) every remaining
+ * pair of at most that many bytes (clamped to one inbox region) travels in one
+ * one-hop direct launch per call, behind the LL launch and ahead of the sends
+ * and recvs; plain ncclSend / ncclRecv never take either path (they are not
+ * collective). */
 ncclResult_t  ncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
     ncclComm_t comm, hipStream_t stream);
 ncclResult_t pncclAllToAll(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,

@@ -199,6 +199,37 @@
  *                     `bytes` (as VCCL_LL_A2A_THRESHOLD at init); *effective
  *                     (may be NULL) = the result.  A tuning / measurement knob:
  *                     every rank must call it alike, outside a group.
+ *   vcclDirectA2aMax   a comm's VCCL_DIRECT_A2A_THRESHOLD (bytes per ordered pair
+ *                     of an ncclAllToAll(v); negative: read it from the
+ *                     environment; default 0 = off) as it takes effect (host
+ *                     only): clamped to what one inbox region
+ *                     holds ((regionBytes - 16) rounded down to 16 bytes), 0
+ *                     without mapped inboxes (regionBytes 0), with Direct
+ *                     excluded, with a net peer, below 2 or above 8 ranks, or
+ *                     without point-to-point connections.
+ *   vcclDirectA2aPlan  vcclLLA2aPlan's three-way successor: how one call splits
+ *                     on a comm whose effective limits are llA2aMax and
+ *                     directA2aMax (host only).  The ordered pair of B bytes is
+ *                     an LL pair as above; else a direct pair iff directA2aMax
+ *                     > 0 and B <= directA2aMax (B = 0 included); else a FIFO
+ *                     pair.  *llLaunch as vcclLLA2aPlan's *launch; *directLaunch
+ *                     = a uniform call without an LL launch iff 0 < B <=
+ *                     directA2aMax, a v-call iff directA2aMax > 0 (every rank
+ *                     launches, pairs or not); a path without its launch takes
+ *                     no pair.  sendPath / recvPath[nRanks] = 0 FIFO, 1 LL, 2
+ *                     direct.  *nBlocks / *blkBytes = the direct launch's grid
+ *                     and block length (0 without one), the same on every rank
+ *                     of a call: from M = B (uniform) or directA2aMax (v),
+ *                     ceil(M / 16 KiB) clamped by maxCTAs / minCTAs, then by
+ *                     directMaxBlocks and 128; blkBytes = ceil(M / blocks)
+ *                     rounded up to 16.  resSends / resRecvs [<= nRanks] = the
+ *                     FIFO peers in peer order.  With directA2aMax 0 the LL
+ *                     bits, *llLaunch and the residuals are vcclLLA2aPlan's.
+ *   vcclCommA2aStatsEx vcclCommA2aStats plus the direct path: direct launches
+ *                     and the sends + recvs that went through the inbox (the
+ *                     LL and FIFO counts are those paths' alone in both).
+ *   vcclCommSetDirectA2aThreshold  vcclCommSetA2aThreshold for the direct
+ *                     limit (as VCCL_DIRECT_A2A_THRESHOLD at init).
  *   vcclAlgoSelection  how NCCL_ALGO / NCCL_PROTO strings select paths (the
  *                     reference's parseList, graph/tuning.cc:53-116: comma
  *                     lists, a leading '^' excludes): *force = 0 automatic,
@@ -231,7 +262,8 @@ typedef enum {
 typedef enum {
   vcclAlgoRing = 0,     /* SIMPLE ring over arc-balanced ring sets */
   vcclAlgoLL = 1,       /* one-hop LL: all-reduce (chain-tree fold), RS / AG, opt-in broadcast / reduce
-                           (the opt-in LL all-to-all is per pair, not a vcclAlgo_t: vcclCommA2aStats) */
+                           (the opt-in LL and direct all-to-alls are per pair, not a vcclAlgo_t:
+                           vcclCommA2aStatsEx) */
   vcclAlgoDirect = 2,   /* direct over the full mesh: two-shot all-reduce, one-hop RS / AG, opt-in
                            two-hop broadcast (scatter + all-gather) / reduce (reduce-scatter + gather) */
   vcclAlgoOneRank = 3,  /* nRanks == 1: copy / PreMulSum kernel */
@@ -289,6 +321,17 @@ ncclResult_t vcclLLA2aPlan(int nRanks, int rank, const size_t* sendBytes, const 
 ncclResult_t vcclCommA2aStats(ncclComm_t comm, unsigned long long* llLaunches, unsigned long long* llPairs,
                               unsigned long long* fifoPairs);
 ncclResult_t vcclCommSetA2aThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
+ncclResult_t vcclDirectA2aMax(int64_t threshold, int64_t regionBytes, int directAllowed, int anyNet, int nRanks,
+                              int hasP2p, int64_t* effective);
+ncclResult_t vcclDirectA2aPlan(int nRanks, int rank, const size_t* sendBytes, const size_t* recvBytes, int uniform,
+                               int64_t llA2aMax, int64_t directA2aMax, int64_t linesPerSlot, int minCTAs,
+                               int maxCTAs, int directMaxBlocks, int* sendPath, int* recvPath, int* llLaunch,
+                               int* directLaunch, int* nBlocks, int64_t* blkBytes, int* nResSends, int* resSends,
+                               int* nResRecvs, int* resRecvs);
+ncclResult_t vcclCommA2aStatsEx(ncclComm_t comm, unsigned long long* llLaunches, unsigned long long* llPairs,
+                                unsigned long long* directLaunches, unsigned long long* directPairs,
+                                unsigned long long* fifoPairs);
+ncclResult_t vcclCommSetDirectA2aThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
 /* What initialisation decides for rank `rank` of an nRanks communicator with
  * CTA bounds minCTAs / maxCTAs (a comm's defaults: 1 / 128), from the
  * environment as at init and each rank's identity pid[r], hostHash[r],

@@ -8,7 +8,13 @@ vcclCommA2aStats.  Per row: min and median us per call over --steps calls
 (default 50) after warm-up, each call timed by its own event pair, the max over
 ranks.
 
-    python tools/a2a_sweep.py [--min-bytes N] [--max-bytes N] [--steps K] [--ranks 2,4,8]
+    python tools/a2a_sweep.py [--min-bytes N] [--max-bytes N] [--steps K] [--ranks 2,4,8] [--direct]
+
+--direct sweeps the one-hop direct path instead (vcclCommSetDirectA2aThreshold,
+vcclCommA2aStatsEx): ncclAllToAll for 16 KiB up to the per-pair limit (what one
+inbox region holds, at most --max-bytes, default 2 MiB) and two ncclAllToAllv
+rows under the limit, one balanced and one skewed (a quarter of the pairs 16x
+the others), FIFO and direct alternating on the one communicator.
 
 The parent spawns the rank processes (bench.py's launcher; ranks share a GPU
 when the box has fewer than ranks — then the rows are rehearsal rows: LL
@@ -29,8 +35,9 @@ def arg(name, default):
     return default
 
 
-MIN_BYTES = int(arg("--min-bytes", 8))
-MAX_BYTES = int(arg("--max-bytes", 256 << 10))
+DIRECT = "--direct" in sys.argv
+MIN_BYTES = int(arg("--min-bytes", 16 << 10 if DIRECT else 8))
+MAX_BYTES = int(arg("--max-bytes", 2 << 20 if DIRECT else 256 << 10))
 STEPS = max(50, int(arg("--steps", 50)))
 RANKS = [int(x) for x in arg("--ranks", "2,4,8").split(",")]
 WARMUP = 5
@@ -117,17 +124,27 @@ def child():
                                                [np.zeros(1, np.uint8)])).cuda()
         want = torch.from_numpy(np.concatenate([pay(rc[p], p, rank, label) for p in range(n)] +
                                                [np.full(1, 0x5A, np.uint8)])).cuda()
-        for path, thr in (("fifo", 0), ("ll", limit)):
-            eff = comm.set_a2a_threshold(thr)
+        for path, thr in (("fifo", 0), ("direct" if DIRECT else "ll", limit)):
+            eff = comm.set_direct_a2a_threshold(thr) if DIRECT else comm.set_a2a_threshold(thr)
             out = torch.full_like(want, 0x5A)
             if op == "alltoall":
                 fn = lambda: comm.all_to_all(send.data_ptr(), out.data_ptr(), sc[0], U8, sp)  # noqa: E731
             else:
                 fn = lambda: comm.all_to_allv(send.data_ptr(), sc, sd, out.data_ptr(), rc, rd, U8, sp)  # noqa: E731
-            s0 = comm.a2a_stats()
+            s0 = comm.a2a_stats_ex() if DIRECT else comm.a2a_stats()
             us = timed(fn, torch.cuda.synchronize)
-            s1 = comm.a2a_stats()
+            s1 = comm.a2a_stats_ex() if DIRECT else comm.a2a_stats()
             calls = STEPS + WARMUP
+            if DIRECT:
+                pl = nccl.direct_a2a_plan(n, rank, sc, rc, op == "alltoall", 0, eff, 1)
+                fifo = len(pl["res_sends"]) + len(pl["res_recvs"])
+                ok = eff == thr and torch.equal(out, want) and [a - b for a, b in zip(s1, s0)] == \
+                    [0, 0, calls * int(pl["direct_launch"]), calls * (2 * n - fifo), calls * fifo]
+                good &= row(op=op, ranks=world, shared_gpu=shared, path=path,
+                            bytes_per_pair=label if op == "alltoall" else None,
+                            variant=None if op == "alltoall" else label_name[label], direct_pairs=2 * n - fifo,
+                            fifo_pairs=fifo, calls=STEPS, min_us=us[0], median_us=us[len(us) // 2], ok=ok)
+                continue
             pl = nccl.ll_a2a_plan(n, rank, sc, rc, op == "alltoall", eff, max(1, (1 << 20) // 8))
             fifo = len(pl["res_sends"]) + len(pl["res_recvs"])
             ok = eff == thr and torch.equal(out, want) and \
@@ -135,11 +152,28 @@ def child():
             good &= row(op=op, ranks=world, shared_gpu=shared, path=path, bytes_per_pair=label if op == "alltoall" else None,
                         variant=None if op == "alltoall" else label_name[label], ll_pairs=2 * n - fifo, fifo_pairs=fifo,
                         calls=STEPS, min_us=us[0], median_us=us[len(us) // 2], ok=ok)
-        comm.set_a2a_threshold(0)
+        comm.set_direct_a2a_threshold(0) if DIRECT else comm.set_a2a_threshold(0)
         return good
 
-    label_name = {1: "all_under_limit", 2: "quarter_over_limit"}
+    label_name = {1: "all_under_limit", 2: "quarter_over_limit", 3: "balanced", 4: "skewed"}
     good = True
+    if DIRECT:
+        limit = min(MAX_BYTES, comm.set_direct_a2a_threshold(1 << 40))  # what one region holds
+        comm.set_direct_a2a_threshold(0)
+        for nb in sizes(MIN_BYTES, limit):
+            good &= measure("alltoall", [[nb] * n for _ in range(n)], nb, limit)
+        rng = np.random.default_rng(2027 + n)
+        balanced = rng.integers(limit // 16, limit // 8 + 1, size=(n, n))
+        skewed = rng.integers(limit // 32, limit // 16 + 1, size=(n, n))
+        hot = rng.random((n, n)) < 0.25
+        hot[0, n - 1] = True
+        skewed[hot] *= 16
+        good &= measure("alltoallv", balanced, 3, limit)
+        good &= measure("alltoallv", skewed, 4, limit)
+        err = comm.async_error()
+        comm.destroy()
+        dist.destroy_process_group()
+        sys.exit(0 if good and not err else 1)
     for nb in sizes(MIN_BYTES, MAX_BYTES):
         good &= measure("alltoall", [[nb] * n for _ in range(n)], nb, MAX_BYTES)
     rng = np.random.default_rng(2026 + n)

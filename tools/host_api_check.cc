@@ -424,7 +424,74 @@ int main() {
   unsetenv("VCCL_LL_A2A_THRESHOLD");
   EXPECT(vcclCommA2aStats(nullptr, nullptr, nullptr, nullptr) == ncclInvalidArgument);
   EXPECT(vcclCommSetA2aThreshold(nullptr, 4096, nullptr) == ncclInvalidArgument);
+  // the direct all-to-all limit (vcclDirectA2aMax) and one call's three-way
+  // split (vcclDirectA2aPlan) on random byte matrices, limits, bounds and
+  // invalid arguments
+  long directA2a = 0;
+  for (int trial = 0; trial < 20000; trial++) {
+    if (rng() % 4 == 0) setenv("VCCL_DIRECT_A2A_THRESHOLD", junk[rng() % 11], 1);
+    else if (rng() % 2) setenv("VCCL_DIRECT_A2A_THRESHOLD", "98304", 1);
+    else unsetenv("VCCL_DIRECT_A2A_THRESHOLD");
+    const int64_t region = pick({0, 8, 16, 17, 4096, 131328, -1});
+    int64_t eff = -7;
+    const ncclResult_t r = vcclDirectA2aMax(pick({-1, 0, 1, 4096, 1 << 20, 1ll << 40}), region, (int)(rng() % 2),
+                                            (int)(rng() % 2), (int)pick({0, 1, 2, 8, 9, 64}), (int)(rng() % 2),
+                                            rng() % 16 ? &eff : nullptr);
+    EXPECT(r == ncclSuccess || r == ncclInvalidArgument);
+    if (r == ncclSuccess) EXPECT(eff >= 0 && eff <= (region > 16 ? region - 16 : 0));
+    const int n = (int)pick({1, 2, 3, 4, 5, 8, 8, 9}), rank = (int)(rng() % (n + 1)) - (rng() % 32 == 0);
+    const int64_t lps = pick({0, 1, 16, 512, 131072});
+    const int64_t lim = pick({0, 8, 100, lps * 8, lps * 8 + 1, -1});
+    const int64_t dlim = pick({0, 1, 16, 4097, 98304, 1 << 21, -1, 1ll << 41});
+    const int minC = (int)pick({-1, 0, 1, 4, 1000}), maxC = (int)pick({0, 1, 32, 64, 1000});
+    const int dmb = (int)pick({0, 1, 16, 64, 1000});
+    const int uniform = (int)(rng() % 3 == 0);
+    std::vector<size_t> sb(n + 1), rb(n + 1);
+    const size_t u = (size_t)pick({0, 1, 8, 4096, 4097, 98304});
+    for (int p = 0; p < n; p++) {
+      sb[p] = uniform && rng() % 16 ? u : (size_t)pick({0, 1, 7, 8, 9, 100, 4096, 4097, 98304, 1 << 21}) + rng() % 2;
+      rb[p] = uniform && rng() % 16 ? u : (size_t)pick({0, 1, 7, 8, 9, 100, 4096, 4097, 98304, 1 << 21}) + rng() % 2;
+      if (rng() % 256 == 0) sb[p] = ~(size_t)0;
+    }
+    std::vector<int> sp(n + 1, -1), rp(n + 1, -1), rs(n + 1, -1), rr(n + 1, -1);
+    int ll = -1, dl = -1, nb = -1, nrs = -1, nrr = -1;
+    int64_t blk = -1;
+    const ncclResult_t q = vcclDirectA2aPlan(n, rank, rng() % 32 ? sb.data() : nullptr, rb.data(), uniform, lim, dlim,
+                                             lps, minC, maxC, dmb, sp.data(), rng() % 32 ? rp.data() : nullptr, &ll,
+                                             &dl, rng() % 32 ? &nb : nullptr, &blk, &nrs, rs.data(), &nrr, rr.data());
+    EXPECT(q == ncclSuccess || q == ncclInvalidArgument);
+    if (q == ncclSuccess) {
+      EXPECT((ll == 0 || ll == 1) && (dl == 0 || dl == 1) && !(uniform && ll && dl));
+      EXPECT(nrs >= 0 && nrs <= n && nrr >= 0 && nrr <= n);
+      int nPath[3] = {0, 0, 0};
+      for (int p = 0; p < n; p++) {
+        EXPECT(sp[p] >= 0 && sp[p] <= 2 && rp[p] >= 0 && rp[p] <= 2);
+        if (!ll) EXPECT(sp[p] != 1 && rp[p] != 1);
+        if (!dl) EXPECT(sp[p] != 2 && rp[p] != 2);
+        if (sp[p] == 1) EXPECT((int64_t)sb[p] <= lim);
+        if (rp[p] == 1) EXPECT((int64_t)rb[p] <= lim);
+        if (sp[p] == 2) EXPECT((int64_t)sb[p] <= dlim);
+        if (rp[p] == 2) EXPECT((int64_t)rb[p] <= dlim);
+        nPath[sp[p]]++;
+        nPath[rp[p]]++;
+      }
+      EXPECT(nPath[0] == nrs + nrr && nPath[0] + nPath[1] + nPath[2] == 2 * n);
+      if (dl) {
+        const int64_t M = uniform ? (int64_t)sb[0] : dlim;
+        EXPECT(nb >= 1 && nb <= 128 && nb <= dmb && blk >= 16 && blk % 16 == 0);
+        EXPECT((int64_t)nb * blk >= M && (int64_t)(nb - 1) * blk < M);
+      } else {
+        EXPECT(nb == 0 && blk == 0);
+      }
+    }
+    EXPECT(sp[n] == -1 && rp[n] == -1 && rs[n] == -1 && rr[n] == -1);
+    directA2a++;
+  }
+  unsetenv("VCCL_DIRECT_A2A_THRESHOLD");
+  EXPECT(vcclCommA2aStatsEx(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == ncclInvalidArgument);
+  EXPECT(vcclCommSetDirectA2aThreshold(nullptr, 4096, nullptr) == ncclInvalidArgument);
   printf("host_api_check: %ld all-to-all limits and plans\n", a2a);
+  printf("host_api_check: %ld direct all-to-all limits and plans\n", directA2a);
   printf("host_api_check: %ld rooted selections and layouts\n", rooted);
   printf("host_api_check: %ld rooted direct selections and plans\n", directRooted);
   printf("host_api_check: %ld p2p plans\n", p2pPlans);

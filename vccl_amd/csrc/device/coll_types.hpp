@@ -150,8 +150,8 @@ __host__ __device__ __forceinline__ int direct_bcast_shard_of(int root, int rank
 
 // Inbox: [2 phases][2 parities][nRanks sources][region]; flags likewise.
 // The all-reduce double-buffers its chunks by parity (direct.hpp); the
-// one-hop reduce-scatter / all-gather and the rooted broadcast / reduce use
-// parity 0.
+// one-hop reduce-scatter / all-gather / all-to-all and the rooted broadcast /
+// reduce use parity 0.
 constexpr int kDirectInboxRegions = 4;  // regions per source: phases x parities
 __host__ __device__ __forceinline__ size_t direct_region_off(int phase, int parity, int src, int nRanks,
                                                              int64_t regionBytes) {
@@ -184,6 +184,31 @@ struct DirectBatch {
 };
 // hipModuleLaunchKernel's by-value argument segment is 4 KiB
 static_assert(sizeof(DirectBatch) <= 4096, "DirectBatch must fit the kernel-argument budget");
+// One-hop direct all-to-all(v) (direct.hpp direct_alltoall; host/plan.cc
+// direct_a2a_plan).  The table is ROTATED to the rank like LLA2aWork's: entry k
+// belongs to rank (rank + k) mod nRanks, entry 0 to the rank itself.  An
+// ordered pair whose "direct pair" bit is set moves its bytes as [0, bytes) of
+// region (0, 0, writer) at the reader; workgroup b moves bytes [b * blkBytes,
+// (b + 1) * blkBytes) of every pair.  Every other pair moves in the LL or FIFO
+// launch of the same call and only exchanges flags here.
+struct DirectA2aPeer {
+  const char* send;        // my block for this peer
+  char* recv;              // where this peer's block lands
+  int64_t sendBytes, recvBytes;
+  int32_t sendDirect, recvDirect;  // the "direct pair" bit of each direction
+};
+struct DirectA2aWork {
+  DevComm* comm;
+  const DirectPeers* peers;
+  int rank, nRanks;
+  int nBlocks;             // workgroups, the same on every rank of the call
+  int pad;
+  int64_t blkBytes;        // bytes per block, a multiple of 16
+  int64_t regionBytes;     // bytes per (phase, rank) inbox region
+  DirectA2aPeer peer[kDirectMaxRanks];
+};
+static_assert(sizeof(DirectA2aWork) <= 4096, "DirectA2aWork must fit the kernel-argument budget");
+
 __host__ __device__ inline DirectPart direct_part_of(const DirectWork& w) {
   return DirectPart{w.sendbuff, w.recvbuff, w.count, w.nChunks, w.root, w.chunkElts, w.blkElts, w.cbd,
                     w.arChunk};

@@ -40,17 +40,17 @@
 //  * the all-reduce double-buffers its chunks by parity (regions and flags,
 //    direct_allreduce_part): parity p is rewritten for chunk c+2 only after
 //    the readers' flags of chunk c were awaited;
-//  * the one-hop reduce-scatter / all-gather use parity 0 only and guard
-//    reuse with explicit acknowledgements (phase 3 below);
+//  * the one-hop reduce-scatter / all-gather / all-to-all use parity 0 only
+//    and guard reuse with explicit acknowledgements (phase 3 below);
 //  * the rooted broadcast / reduce (direct_broadcast_part, direct_reduce_part)
 //    use parity 0 only and close every chunk with a flag round of phase 1;
 // and a region of one parity is rewritten by its writer's next chunk, part
 // or call only after its reader's flag for the previous use, so any of the
-// five kernels may follow any other on the same inbox (a peer one call
+// six kernels may follow any other on the same inbox (a peer one call
 // ahead writes only (0, *) regions, which the previous call has finished
 // reading before that peer could complete it).
 //
-// The reuse rule, which all five kernels obey:
+// The reuse rule, which all six kernels obey:
 //   R1  a rank writes a (1, *) region or raises a (1, *) flag only after it
 //       has seen, in this call (this chunk), a phase-0 flag from every peer;
 //   R2  a rank leaves a call (a chunk) only after every peer has acknowledged
@@ -76,7 +76,14 @@
 //                    gather's direct_wait(1) closes the chunk;
 //    reduce-scatter  writes no (1, *) region; its acknowledgement (1, me)
 //    / all-gather    follows direct_wait(0) (R1) and direct_wait(1) closes (R2);
-//    broadcast       the ROOT waits for no data, a non-root forwards after the
+//    all-to-all      (direct_alltoall, a launch of its own: one chunk) as the
+//                    all-gather: it writes (0, me) regions only, and only for
+//                    its direct pairs, but posts and awaits EVERY peer's flags
+//                    in both rounds — the acknowledgement (1, me) follows
+//                    direct_wait(0) on all peers (R1), direct_wait(1) on all
+//                    peers closes the call (R2) — so it is one position of the
+//                    epoch sequence like any other chunk;
+//    broadcast      the ROOT waits for no data, a non-root forwards after the
 //                    root's flag alone: what keeps either from running ahead
 //                    is the gather's direct_wait(0) on every peer before the
 //                    acknowledgement (R1) and the closing direct_wait(1) (R2).
@@ -863,6 +870,84 @@ __device__ void direct_reduce_part(const DirectWork& w, uint32_t& e, int& shFail
       }
     }
   }
+}
+
+// ---------------------------------------------------------------- all-to-all
+// One-hop all-to-all(v) (byte copies): the all-gather above with its own
+// source block and length per peer.  The ordered pair (me -> p) of B bytes
+// occupies bytes [0, B) of region (0, 0, me) at p — for the pairs the host
+// marked "direct pair" (host/plan.cc direct_a2a_plan; both ends decide on the
+// same B and comm-wide limits).  The other pairs of a v-call travel in the LL
+// launch before or the FIFO launch behind this one, so a rank may have nothing
+// to say to a peer here: every workgroup of the grid still posts to and waits
+// for EVERY peer in both rounds, whatever it moves, so the launch obeys R1 / R2
+// like the all-gather.  One chunk, one epoch per launch (a pair above a region
+// is a FIFO pair):
+//   phase 1 (deliver): block b of my block for every direct peer p -> p's
+//            region (0, me), peers in rotated order from 1 + b mod (n-1); the
+//            self block is a local copy; raise (0, me, b) at every peer;
+//   phase 2 (collect): wait for (0, *, b); copy block b of every direct peer's
+//            region (0, q) into its place in the output (any alignment); raise
+//            the acknowledgement (1, me, b) at every peer;
+//   phase 3 (ack):     wait for (1, *, b) before the next call overwrites
+//            region (0, me) at the peers.
+// The per-peer table (rotated to me: entry k = rank me + k) sits in LDS, filled
+// through constant indices like ll_load_a2a.  Regions and flags of parity 0.
+__device__ __forceinline__ void direct_alltoall(const DirectA2aWork& w) {
+  using Fn = FnCopy<uint8_t>;
+  const Fn fn(0);
+  __shared__ DirectA2aPeer sh[kDirectMaxRanks];
+  __shared__ int shFail;
+#pragma unroll
+  for (int i = 0; i < kDirectMaxRanks; i++)
+    if ((int)threadIdx.x == i) sh[i] = w.peer[i];
+  if (threadIdx.x == 0) shFail = 0;
+  __syncthreads();
+  // what direct_wait / direct_post read of a DirectWork
+  DirectWork dw{};
+  dw.comm = w.comm;
+  dw.nRanks = w.nRanks;
+  dw.rank = w.rank;
+  const DirectPeers& P = *w.peers;
+  const int n = w.nRanks, me = w.rank, b = blockIdx.x;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  char* myBuf = P.buf[me];
+  const char* myFlags = P.flags[me];
+  const uint32_t e = epoch_after(__hip_atomic_load(&w.comm->dEpoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  const int64_t lo = (int64_t)b * w.blkBytes;  // block b: the same offset in user blocks and regions
+  auto len_of = [&](int64_t bytes) {
+    const int64_t hi = lo + w.blkBytes < bytes ? lo + w.blkBytes : bytes;
+    return hi > lo ? hi - lo : (int64_t)0;
+  };
+  // Phase 1: deliver (workgroup b starts at peer offset 1 + b mod (n-1)).
+  for (int i = 0; i < n - 1; i++) {
+    const int k = 1 + (b + i) % (n - 1);
+    const int p = me + k < n ? me + k : me + k - n;
+    if (!sh[k].sendDirect) continue;
+    const char* s[kDirectMaxRanks] = {sh[k].send + lo};
+    char* d[kDirectMaxRanks] = {P.buf[p] + direct_region_off(0, 0, me, n, w.regionBytes) + lo};
+    direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len_of(sh[k].sendBytes), tid, nt);
+  }
+  if (sh[0].sendDirect && sh[0].send != sh[0].recv) {  // the self block (nothing when already in place)
+    const char* s[kDirectMaxRanks] = {sh[0].send + lo};
+    char* d[kDirectMaxRanks] = {sh[0].recv + lo};
+    direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len_of(sh[0].sendBytes), tid, nt);
+  }
+  direct_post(dw, P, 0, 0, b, e);
+  // Phase 2: collect.
+  if (direct_wait(dw, myFlags, 0, 0, b, e, &shFail)) {
+    for (int k = 1; k < n; k++) {
+      const int q = me + k < n ? me + k : me + k - n;
+      if (!sh[k].recvDirect) continue;
+      const char* s[kDirectMaxRanks] = {myBuf + direct_region_off(0, 0, q, n, w.regionBytes) + lo};
+      char* d[kDirectMaxRanks] = {sh[k].recv + lo};
+      direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len_of(sh[k].recvBytes), tid, nt);
+    }
+  }
+  // Phase 3: the acknowledgement round (reuse rule, header).
+  direct_post(dw, P, 1, 0, b, e);
+  (void)direct_wait(dw, myFlags, 1, 0, b, e, &shFail);
+  epoch_retire(&w.comm->dEpoch, &w.comm->dDone, e);
 }
 
 // A batch (group aggregation, DirectBatch): the parts in order, one epoch

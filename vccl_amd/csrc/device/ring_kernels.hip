@@ -5,7 +5,7 @@
 // per channel, enqueue.cc:1576-1666), the one-shot LL and the direct
 // (two-shot all-reduce, one-hop reduce-scatter, two-hop reduce) kernels; in
 // the K_U8 unit also the type-agnostic all-gathers and broadcasts (ring, LL,
-// direct).
+// direct) and the one-hop all-to-alls (LL, direct).
 #include <hip/hip_runtime.h>
 
 #include "dispatch.hpp"
@@ -217,6 +217,13 @@ template <class Fn>
 __global__ __launch_bounds__(kDirectThreads) void k_direct_reduce(DirectBatch b) {
   direct_batch(b, [](const DirectWork& w, uint32_t& e, int& f) { direct_reduce_part<Fn>(w, e, f); });
 }
+
+#if VCCL_KT == 0  // K_U8: the byte-copy object also holds the one-hop direct all-to-all
+__global__ __launch_bounds__(kDirectThreads) void k_direct_alltoall(DirectA2aWork w) { direct_alltoall(w); }
+hipError_t direct_a2a_launch(const DirectA2aWork& w, hipStream_t stream, hipEvent_t stop) {
+  return launch_k(k_direct_alltoall, dim3(w.nBlocks), dim3(kDirectThreads), stream, stop, w);
+}
+#endif
 
 template <>
 hipError_t direct_launch<VCCL_KT>(int coll, int devOp, const DirectBatch& b, hipStream_t stream,

@@ -67,6 +67,10 @@ hipError_t ll_a2a_launch(const LLA2aWork& w, int grid, hipStream_t stream, hipEv
 template <int K>
 hipError_t direct_launch(int coll, int devOp, const DirectBatch& b, hipStream_t stream, hipEvent_t stop);
 
+// One-hop direct all-to-all(v) (direct.hpp direct_alltoall): a byte copy,
+// built once in the K_U8 unit; w.nBlocks workgroups of kDirectThreads threads.
+hipError_t direct_a2a_launch(const DirectA2aWork& w, hipStream_t stream, hipEvent_t stop);
+
 // hipLaunchKernelGGL, or with `stop` bound to the kernel's completion.
 template <class F, class... A>
 inline hipError_t launch_k(F kernel, dim3 grid, dim3 block, hipStream_t stream, hipEvent_t stop, A... args) {

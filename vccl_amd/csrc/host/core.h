@@ -164,9 +164,11 @@ struct ncclComm : vccl::CommSetup {
   uint64_t fusedLaunches = 0;         // group launches that carried > 1 collective
   int ringWave = 0;                   // SIMPLE ring launches take the per-wave hand-off (VCCL_RING_WAVE)
   uint64_t waveLaunches = 0;          // ring launches that ran the per-wave kernel
-  // ncclAllToAll(v) on this comm (vcclCommA2aStats): LL launches, and the
-  // sends + recvs (self block included) that went by LL / to the p2p FIFOs
+  // ncclAllToAll(v) on this comm (vcclCommA2aStats / vcclCommA2aStatsEx): LL
+  // and direct launches, and the sends + recvs (self block included) that went
+  // by LL / through the direct inbox / to the p2p FIFOs
   uint64_t a2aLLLaunches = 0, a2aLLPairs = 0, a2aFifoPairs = 0;
+  uint64_t a2aDirectLaunches = 0, a2aDirectPairs = 0;
   // CTA (workgroup) bounds of every collective launch: ncclConfig_t
   // minCTAs / maxCTAs or NCCL_MIN_CTAS / NCCL_MAX_CTAS (init.cc:1478-1540)
   int minCTAs = 1, maxCTAs = 64;

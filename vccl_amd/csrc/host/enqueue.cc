@@ -9,8 +9,9 @@
 // thread and launched at the outermost ncclGroupEnd (launch_group).  ncclSend /
 // ncclRecv (collectives.cc:160-186) take the same road as p2p tasks;
 // ncclAllToAll(v) is an internal group of them — or, on a comm that opted into
-// the one-hop LL all-to-all (VCCL_LL_A2A_THRESHOLD), one task of its own whose
-// small pairs take one LL launch (launch.cc launch_comm_p2p).  The vccl*
+// the one-hop LL or direct all-to-all (VCCL_LL_A2A_THRESHOLD,
+// VCCL_DIRECT_A2A_THRESHOLD), one task of its own whose small pairs take one LL
+// launch and whose mid-size pairs one direct launch (launch.cc launch_comm_p2p).  The vccl*
 // extension exports at the end are wrappers over plan.h and launch.h.
 #include <algorithm>
 #include <cstring>
@@ -192,9 +193,10 @@ VCCL_EXPORT ncclResult_t ncclRecv(void* recvbuff, size_t count, ncclDataType_t d
   return p2p_check(false, "Recv", recvbuff, count, datatype, peer, comm, stream);
 }
 
-// The all-to-all of a comm whose one-hop LL all-to-all is on (llA2aMaxBytes >
-// 0): ONE queued task (kTaskA2a) — launch_group splits its pairs between the LL
-// launch and the p2p launch.  The per-pair checks of the expansion below, in
+// The all-to-all of a comm whose one-hop LL or direct all-to-all is on
+// (llA2aMaxBytes > 0 || directA2aMaxBytes > 0): ONE queued task (kTaskA2a) —
+// launch_group splits its pairs between the LL launch, the direct launch and
+// the p2p launch.  The per-pair checks of the expansion below, in
 // its order; the rows live in tl_a2a until the group has launched.
 static thread_local std::deque<A2aArgs> tl_a2a;
 static ncclResult_t all_to_all_task(const char* name, const void* sendbuff, const size_t* sendcounts,
@@ -263,7 +265,8 @@ static ncclResult_t all_to_all(const char* name, const void* sendbuff, const siz
   }
   const size_t esz = (size_t)type_size(dt);
   const int n = comm->nRanks;
-  if (comm->llA2aMaxBytes > 0 && n <= kOrderMaxRanks)
+  static_assert(kDirectMaxRanks <= kOrderMaxRanks, "A2aArgs holds kOrderMaxRanks rows");
+  if ((comm->llA2aMaxBytes > 0 || comm->directA2aMaxBytes > 0) && n <= kOrderMaxRanks)
     return all_to_all_task(name, sendbuff, sendcounts, sdispls, recvbuff, recvcounts, rdispls, count, dt, comm, stream);
   ncclGroupStart();
   for (int p = 0; p < n && r == ncclSuccess; p++) {
@@ -736,11 +739,69 @@ VCCL_EXPORT ncclResult_t vcclLLA2aPlan(int nRanks, int rank, const size_t* sendB
   return ncclSuccess;
 }
 
+// vccl_ext.h: a comm's VCCL_DIRECT_A2A_THRESHOLD as it takes effect (host only).
+VCCL_EXPORT ncclResult_t vcclDirectA2aMax(int64_t threshold, int64_t regionBytes, int directAllowed, int anyNet,
+                                          int nRanks, int hasP2p, int64_t* effective) {
+  if (!effective || regionBytes < 0 || nRanks < 1) return ncclInvalidArgument;
+  if (threshold < 0) threshold = param_int("DIRECT_A2A_THRESHOLD", 0);
+  *effective =
+      (int64_t)direct_a2a_max(threshold, regionBytes, directAllowed != 0, anyNet != 0, nRanks, hasP2p != 0);
+  return ncclSuccess;
+}
+
+// vccl_ext.h: one all-to-all(v) call's three-way split between the LL launch,
+// the direct launch and the FIFO launch as `rank` runs it (host only).
+VCCL_EXPORT ncclResult_t vcclDirectA2aPlan(int nRanks, int rank, const size_t* sendBytes, const size_t* recvBytes,
+                                           int uniform, int64_t llA2aMax, int64_t directA2aMax, int64_t linesPerSlot,
+                                           int minCTAs, int maxCTAs, int directMaxBlocks, int* sendPath,
+                                           int* recvPath, int* llLaunch, int* directLaunch, int* nBlocks,
+                                           int64_t* blkBytes, int* nResSends, int* resSends, int* nResRecvs,
+                                           int* resRecvs) {
+  if (nRanks < 2 || nRanks > kDirectMaxRanks || rank < 0 || rank >= nRanks || !sendBytes || !recvBytes ||
+      llA2aMax < 0 || linesPerSlot < 0 || linesPerSlot > (int64_t)1 << 40 || llA2aMax > linesPerSlot * 8 ||
+      directA2aMax < 0 || directA2aMax > (int64_t)1 << 40 || minCTAs < 0 || maxCTAs < 1 || directMaxBlocks < 1 ||
+      !sendPath || !recvPath || !llLaunch || !directLaunch || !nBlocks || !blkBytes || !nResSends || !resSends ||
+      !nResRecvs || !resRecvs)
+    return ncclInvalidArgument;
+  int64_t sb[kOrderMaxRanks], rb[kOrderMaxRanks];
+  for (int p = 0; p < nRanks; p++) {
+    if (sendBytes[p] > (size_t)1 << 60 || recvBytes[p] > (size_t)1 << 60) return ncclInvalidArgument;
+    if (uniform && (sendBytes[p] != sendBytes[0] || recvBytes[p] != sendBytes[0])) return ncclInvalidArgument;
+    sb[p] = (int64_t)sendBytes[p];
+    rb[p] = (int64_t)recvBytes[p];
+  }
+  DirectA2aPlanOut out;
+  NCCLCHECK(direct_a2a_plan(nRanks, rank, sb, rb, uniform != 0, (uint64_t)llA2aMax, (uint64_t)directA2aMax,
+                            linesPerSlot, minCTAs, maxCTAs, directMaxBlocks, &out));
+  *llLaunch = out.llLaunch;
+  *directLaunch = out.directLaunch;
+  *nBlocks = out.nBlocks;
+  *blkBytes = out.blkBytes;
+  for (int p = 0; p < nRanks; p++) sendPath[p] = out.sendPath[p], recvPath[p] = out.recvPath[p];
+  *nResSends = (int)out.resSends.size();
+  *nResRecvs = (int)out.resRecvs.size();
+  std::copy(out.resSends.begin(), out.resSends.end(), resSends);
+  std::copy(out.resRecvs.begin(), out.resRecvs.end(), resRecvs);
+  return ncclSuccess;
+}
+
 VCCL_EXPORT ncclResult_t vcclCommA2aStats(ncclComm_t comm, unsigned long long* llLaunches, unsigned long long* llPairs,
                                           unsigned long long* fifoPairs) {
   NCCLCHECK(comm_check(comm, "vcclCommA2aStats"));
   if (llLaunches) *llLaunches = comm->a2aLLLaunches;
   if (llPairs) *llPairs = comm->a2aLLPairs;
+  if (fifoPairs) *fifoPairs = comm->a2aFifoPairs;
+  return ncclSuccess;
+}
+
+VCCL_EXPORT ncclResult_t vcclCommA2aStatsEx(ncclComm_t comm, unsigned long long* llLaunches,
+                                            unsigned long long* llPairs, unsigned long long* directLaunches,
+                                            unsigned long long* directPairs, unsigned long long* fifoPairs) {
+  NCCLCHECK(comm_check(comm, "vcclCommA2aStatsEx"));
+  if (llLaunches) *llLaunches = comm->a2aLLLaunches;
+  if (llPairs) *llPairs = comm->a2aLLPairs;
+  if (directLaunches) *directLaunches = comm->a2aDirectLaunches;
+  if (directPairs) *directPairs = comm->a2aDirectPairs;
   if (fifoPairs) *fifoPairs = comm->a2aFifoPairs;
   return ncclSuccess;
 }
@@ -753,6 +814,16 @@ VCCL_EXPORT ncclResult_t vcclCommSetA2aThreshold(ncclComm_t comm, int64_t bytes,
                                       comm->p2pConns != nullptr && comm->llBuf != nullptr &&
                                           (int)comm->llPeer.size() >= comm->nRanks);
   if (effective) *effective = (int64_t)comm->llA2aMaxBytes;
+  return ncclSuccess;
+}
+
+// Likewise for the direct all-to-all.
+VCCL_EXPORT ncclResult_t vcclCommSetDirectA2aThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective) {
+  NCCLCHECK(comm_check(comm, "vcclCommSetDirectA2aThreshold"));
+  if (bytes < 0) return ncclInvalidArgument;
+  comm->directA2aMaxBytes = direct_a2a_max_of(*comm, bytes, comm->nRanks, comm->p2pOff == kP2pOffNet,
+                                              comm->p2pConns != nullptr && comm->dPeers != nullptr);
+  if (effective) *effective = (int64_t)comm->directA2aMaxBytes;
   return ncclSuccess;
 }
 

@@ -814,16 +814,62 @@ static ncclResult_t launch_ll_a2a(const Task& t, const LLA2aPlanOut& plan) {
   return stream_mark(comm, t.stream, cs);
 }
 
+// ------------------------------------------------------ direct all-to-all
+// The direct launch of one ncclAllToAll(v) (direct.hpp direct_alltoall) on the
+// call's stream, ordered against the comm's other launches exactly like
+// launch_ll_a2a.  The table goes in rotated to this rank; the grid is the
+// plan's nBlocks, already under the co-residency caps the other direct kernels
+// take (directMaxBlocks, which ranks sharing a GPU lower; kDirectMaxBlocks).
+static ncclResult_t launch_direct_a2a(const Task& t, const DirectA2aPlanOut& plan) {
+  ncclComm* comm = t.comm;
+  const int n = comm->nRanks, me = comm->rank;
+  const A2aArgs& a = *t.a2a;
+  if (n > kDirectMaxRanks || !comm->dPeers || plan.nBlocks < 1 || plan.nBlocks > kDirectMaxBlocks ||
+      plan.blkBytes < 16 || plan.blkBytes % 16)
+    return ncclInternalError;
+  // what the grid covers, and what a region holds (the last block may be short)
+  const int64_t cover = std::min<int64_t>((int64_t)plan.nBlocks * plan.blkBytes, comm->dRegionBytes - 16);
+  DirectA2aWork w{};
+  w.comm = comm->devComm;
+  w.peers = comm->dPeers;
+  w.rank = me;
+  w.nRanks = n;
+  w.nBlocks = plan.nBlocks;
+  w.blkBytes = plan.blkBytes;
+  w.regionBytes = comm->dRegionBytes;
+  for (int k = 0; k < n; k++) {
+    const int p = (me + k) % n;
+    DirectA2aPeer& e = w.peer[k];
+    e.send = t.sendbuff ? (const char*)t.sendbuff + a.sendOff[p] : nullptr;
+    e.recv = t.recvbuff ? (char*)t.recvbuff + a.recvOff[p] : nullptr;
+    e.sendBytes = a.sendBytes[p];
+    e.recvBytes = a.recvBytes[p];
+    e.sendDirect = plan.sendPath[p] == kA2aDirect;
+    e.recvDirect = plan.recvPath[p] == kA2aDirect;
+    if ((e.sendDirect && e.sendBytes > cover) || (e.recvDirect && e.recvBytes > cover)) return ncclInternalError;
+  }
+  DeviceGuard dev(comm->device);
+  HIPCHECK(dev.status);
+  CaptureState cs{false, 0};
+  NCCLCHECK(stream_order(comm, t.stream, &cs));
+  const hipError_t e = direct_a2a_launch(w, t.stream, stop_event(comm, cs));
+  if (e != hipSuccess) {
+    VWARN("direct all-to-all kernel launch failed: %s", hipGetErrorString(e));
+    return ncclUnhandledCudaError;
+  }
+  return stream_mark(comm, t.stream, cs);
+}
+
 // One comm's sends, recvs and all-to-all tasks of a group (call order): each
-// all-to-all's LL launch in call order, then the one p2p launch with the
-// plain sends and recvs and the all-to-alls' pairs above the limit, in call
-// order per peer — so matching by sweep is what it was.
+// all-to-all's LL launch, then its direct launch, in call order, then the one
+// p2p launch with the plain sends and recvs and the all-to-alls' residual
+// pairs, in call order per peer — so matching by sweep is what it was.
 static ncclResult_t launch_comm_p2p(const std::vector<Task>& mine) {
   if (std::none_of(mine.begin(), mine.end(), [](const Task& t) { return t.coll == kTaskA2a; }))
     return launch_p2p(mine);
   ncclComm* comm = mine[0].comm;
   const int n = comm->nRanks, me = comm->rank;
-  // launch_p2p's refusal, before any LL launch: a refused group launches nothing
+  // launch_p2p's refusal, before any LL or direct launch: a refused group launches nothing
   if (check_self_pairs(comm, mine) != ncclSuccess) {
     comm->opCount += mine.size();
     return ncclInvalidUsage;
@@ -835,17 +881,30 @@ static ncclResult_t launch_comm_p2p(const std::vector<Task>& mine) {
       continue;
     }
     const A2aArgs& a = *t.a2a;
-    LLA2aPlanOut plan;
-    if (ll_a2a_plan(n, me, a.sendBytes, a.recvBytes, a.uniform, comm->llA2aMaxBytes, comm->llLines, &plan) !=
-        ncclSuccess)
+    DirectA2aPlanOut plan;
+    if (direct_a2a_plan(n, me, a.sendBytes, a.recvBytes, a.uniform, comm->llA2aMaxBytes, comm->directA2aMaxBytes,
+                        comm->llLines, comm->minCTAs, comm->maxCTAs, comm->directMaxBlocks, &plan) != ncclSuccess)
       return ncclInternalError;
     const size_t nFifo = plan.resSends.size() + plan.resRecvs.size();
-    comm->a2aLLPairs += 2 * (size_t)n - nFifo;
+    const size_t nDirect = (size_t)std::count(plan.sendPath.begin(), plan.sendPath.end(), (char)kA2aDirect) +
+                           (size_t)std::count(plan.recvPath.begin(), plan.recvPath.end(), (char)kA2aDirect);
+    comm->a2aLLPairs += 2 * (size_t)n - nFifo - nDirect;
+    comm->a2aDirectPairs += nDirect;
     comm->a2aFifoPairs += nFifo;
-    if (plan.launch) {
-      comm->opCount += 2 * (size_t)n - nFifo;  // as the FIFO path counts them; whatever the outcome
+    comm->opCount += 2 * (size_t)n - nFifo;  // as the FIFO path counts them; whatever the outcome
+    if (plan.llLaunch) {
+      LLA2aPlanOut ll;
+      ll.launch = true;
+      for (int p = 0; p < n; p++) {
+        ll.sendLL.push_back(plan.sendPath[p] == kA2aLL);
+        ll.recvLL.push_back(plan.recvPath[p] == kA2aLL);
+      }
       comm->a2aLLLaunches++;
-      NCCLCHECK(launch_ll_a2a(t, plan));
+      NCCLCHECK(launch_ll_a2a(t, ll));
+    }
+    if (plan.directLaunch) {
+      comm->a2aDirectLaunches++;
+      NCCLCHECK(launch_direct_a2a(t, plan));
     }
     for (int p = 0; p < n; p++) {  // the API's own expansion order: send p, recv p
       Task s{.coll = kTaskSend, .sendbuff = t.sendbuff ? (const char*)t.sendbuff + a.sendOff[p] : nullptr,
@@ -854,8 +913,8 @@ static ncclResult_t launch_comm_p2p(const std::vector<Task>& mine) {
       Task r{.coll = kTaskRecv, .sendbuff = nullptr,
              .recvbuff = t.recvbuff ? (char*)t.recvbuff + a.recvOff[p] : nullptr, .count = (size_t)a.recvBytes[p],
              .datatype = ncclUint8, .devOp = t.devOp, .root = p, .comm = comm, .stream = t.stream};
-      if (!plan.sendLL[p]) fifo.push_back(s);
-      if (!plan.recvLL[p]) fifo.push_back(r);
+      if (plan.sendPath[p] == kA2aFifo) fifo.push_back(s);
+      if (plan.recvPath[p] == kA2aFifo) fifo.push_back(r);
     }
   }
   return fifo.empty() ? ncclSuccess : launch_p2p(fifo);

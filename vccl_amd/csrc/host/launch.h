@@ -12,11 +12,12 @@ namespace vccl {
 // Task::coll of a point-to-point call (beside plan.h's Coll values).
 enum { kTaskSend = 5, kTaskRecv = 6 };
 inline bool is_p2p(int coll) { return coll == kTaskSend || coll == kTaskRecv; }
-// ... and of an ncclAllToAll(v) on a comm whose one-hop LL all-to-all is on
-// (llA2aMaxBytes > 0): one task; launch_group gives its pairs within the limit
-// to one LL launch and turns the rest into sends and recvs of the group's p2p
-// launch.  With the path off the API expands the call into sends and recvs
-// itself, as it always did.
+// ... and of an ncclAllToAll(v) on a comm whose one-hop LL or direct all-to-all
+// is on (llA2aMaxBytes > 0 || directA2aMaxBytes > 0): one task; launch_group
+// gives its pairs within the limits to one LL launch and one direct launch
+// (plan.h direct_a2a_plan) and turns the rest into sends and recvs of the
+// group's p2p launch.  With both paths off the API expands the call into sends
+// and recvs itself, as it always did.
 enum { kTaskA2a = 7 };
 struct A2aArgs {  // bytes; per peer (nRanks <= kOrderMaxRanks whenever the path is on)
   int64_t sendBytes[kOrderMaxRanks], recvBytes[kOrderMaxRanks];
@@ -52,8 +53,8 @@ int kernel_type_of_call(int coll, int devOp, ncclDataType_t datatype);
 // One call outside a group.
 ncclResult_t launch_task(const Task& t);
 // A group's calls, at the outermost ncclGroupEnd: per comm its collectives,
-// then each of its all-to-all tasks' LL launch, then its sends and recvs with
-// the all-to-alls' pairs above the LL limit (launch_p2p).
+// then each of its all-to-all tasks' LL launch and direct launch, then its
+// sends and recvs with the all-to-alls' residual pairs (launch_p2p).
 ncclResult_t launch_group(std::vector<Task>& tasks);
 // Why `comm` cannot send or receive (WARN + ncclInvalidUsage), else ncclSuccess.
 ncclResult_t p2p_usable(const ncclComm* comm, const char* api);

@@ -593,6 +593,55 @@ ncclResult_t ll_a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const i
   return ncclSuccess;
 }
 
+// -------------------------------------------------------- direct all-to-all
+uint64_t direct_a2a_max(int64_t threshold, int64_t regionBytes, bool directAllowed, bool anyNet, int nRanks,
+                        bool hasP2p) {
+  if (threshold <= 0 || regionBytes <= 16 || !directAllowed || anyNet || nRanks < 2 || nRanks > kDirectMaxRanks ||
+      !hasP2p)
+    return 0;
+  return (uint64_t)std::min(threshold, (regionBytes - 16) / 16 * 16);
+}
+
+ncclResult_t direct_a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const int64_t* recvBytes, bool uniform,
+                             uint64_t llA2aMax, uint64_t directA2aMax, int64_t linesPerSlot, int minCTAs, int maxCTAs,
+                             int directMaxBlocks, DirectA2aPlanOut* out) {
+  const int n = nRanks;
+  LLA2aPlanOut ll;
+  const ncclResult_t llRes = ll_a2a_plan(n, rank, sendBytes, recvBytes, uniform, llA2aMax, linesPerSlot, &ll);
+  if (llRes != ncclSuccess) return llRes;
+  out->llLaunch = ll.launch;
+  // uniform: every pair carries sendBytes[0]; all of them direct, or none
+  out->directLaunch = directA2aMax > 0 && (uniform ? !ll.launch && sendBytes[0] > 0 &&
+                                                         (uint64_t)sendBytes[0] <= directA2aMax
+                                                   : true);
+  out->sendPath.assign(n, kA2aFifo);
+  out->recvPath.assign(n, kA2aFifo);
+  out->resSends.clear();
+  out->resRecvs.clear();
+  for (int p = 0; p < n; p++) {
+    bool s = out->directLaunch && !ll.sendLL[p] && (uint64_t)sendBytes[p] <= directA2aMax;
+    bool r = out->directLaunch && !ll.recvLL[p] && (uint64_t)recvBytes[p] <= directA2aMax;
+    if (p == rank) s = r = s && r && sendBytes[p] == recvBytes[p];  // else the FIFO launch's copy (or its refusal)
+    out->sendPath[p] = ll.sendLL[p] ? kA2aLL : s ? kA2aDirect : kA2aFifo;
+    out->recvPath[p] = ll.recvLL[p] ? kA2aLL : r ? kA2aDirect : kA2aFifo;
+    if (out->sendPath[p] == kA2aFifo) out->resSends.push_back(p);
+    if (out->recvPath[p] == kA2aFifo) out->resRecvs.push_back(p);
+  }
+  out->nBlocks = 0;
+  out->blkBytes = 0;
+  if (out->directLaunch) {
+    // launch.cc direct_work_of's block formula on M bytes: CTA bounds first,
+    // then the co-residency caps last
+    const int64_t M = uniform ? sendBytes[0] : (int64_t)directA2aMax;
+    int64_t nb = (M + (16 << 10) - 1) / (16 << 10);
+    nb = std::max<int64_t>(std::min<int64_t>(nb, maxCTAs), minCTAs);
+    nb = std::max<int64_t>(1, std::min<int64_t>({nb, (int64_t)directMaxBlocks, (int64_t)kDirectMaxBlocks}));
+    out->blkBytes = ((M + nb - 1) / nb + 15) / 16 * 16;
+    out->nBlocks = (int)((M + out->blkBytes - 1) / out->blkBytes);
+  }
+  return ncclSuccess;
+}
+
 // ------------------------------------------------------------ point-to-point
 P2pSplit p2p_split(int64_t bytes, const P2pGeometry& g) {
   if (bytes <= 0) return P2pSplit{0, 0};

@@ -220,6 +220,52 @@ struct LLA2aPlanOut {
 ncclResult_t ll_a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const int64_t* recvBytes, bool uniform,
                          uint64_t llA2aMax, int64_t linesPerSlot, LLA2aPlanOut* out);
 
+// -------------------------------------------------------- direct all-to-all
+// A comm's VCCL_DIRECT_A2A_THRESHOLD (bytes per ordered pair) as it takes
+// effect: clamped to what one inbox region holds ((regionBytes - 16) rounded
+// down to 16 bytes, the slack launch.cc direct_work_of leaves); 0 without
+// mapped inboxes (regionBytes == 0), with Direct excluded by NCCL_ALGO, with a
+// peer behind the net proxy, with fewer than 2 or more than kDirectMaxRanks
+// ranks, or on a comm without point-to-point connections.
+uint64_t direct_a2a_max(int64_t threshold, int64_t regionBytes, bool directAllowed, bool anyNet, int nRanks,
+                        bool hasP2p);
+// Pair rule, three-way, from B and the two comm-wide limits alone (so both
+// ends agree): LL iff ll_a2a_pair; else direct iff directA2aMax > 0 && B <=
+// directA2aMax (B = 0 included); else the FIFOs.
+enum { kA2aFifo = 0, kA2aLL = 1, kA2aDirect = 2 };
+inline int a2a_pair_path(uint64_t llA2aMax, uint64_t directA2aMax, int64_t bytes) {
+  if (ll_a2a_pair(llA2aMax, bytes)) return kA2aLL;
+  return directA2aMax > 0 && (uint64_t)bytes <= directA2aMax ? kA2aDirect : kA2aFifo;
+}
+// One ncclAllToAll (uniform) / ncclAllToAllv call as `rank` runs it (device/
+// direct.hpp direct_alltoall).  Launch rule, identical on every rank: a uniform
+// call of B bytes per pair is one LL launch and nothing else when 0 < B <=
+// llA2aMax, else one direct launch and nothing else when 0 < B <= directA2aMax,
+// else the FIFO path whole; a v-call has an LL launch iff llA2aMax > 0, then
+// exactly one direct launch iff directA2aMax > 0 — even when this rank's row
+// and column hold no direct pair: peers wait for its flags — then the FIFO
+// launch for the residual pairs.  A path without its launch takes no pair.
+// The self block is LL as ll_a2a_plan has it; else a local copy in the direct
+// kernel when that launch happens, both lengths agree and fit directA2aMax
+// (the kernel skips it when the pointers coincide); else a FIFO-launch copy.
+// Geometry, from comm-wide values only (M = B for a uniform call, directA2aMax
+// for a v-call: a rank knows only its row and column): nb = ceil(M / 16 KiB)
+// clamped by maxCTAs / minCTAs, then by directMaxBlocks and kDirectMaxBlocks
+// last; blkBytes = alignUp(ceil(M / nb), 16); nBlocks = ceil(M / blkBytes).
+// Pair (r -> p) occupies bytes [0, B) of region (0, 0, r) at p; one chunk, one
+// epoch per launch.  With directA2aMax == 0 the LL bits, the LL launch flag and
+// the residuals are ll_a2a_plan's.  ncclInvalidArgument as ll_a2a_plan.
+struct DirectA2aPlanOut {
+  std::vector<char> sendPath, recvPath;  // per peer: kA2aFifo / kA2aLL / kA2aDirect
+  bool llLaunch = false, directLaunch = false;
+  int nBlocks = 0;         // 0 without a direct launch
+  int64_t blkBytes = 0;
+  std::vector<int> resSends, resRecvs;
+};
+ncclResult_t direct_a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const int64_t* recvBytes, bool uniform,
+                             uint64_t llA2aMax, uint64_t directA2aMax, int64_t linesPerSlot, int minCTAs, int maxCTAs,
+                             int directMaxBlocks, DirectA2aPlanOut* out);
+
 // ------------------------------------------------------------ point-to-point
 // The plan of a group's ncclSend / ncclRecv calls of one comm on its per-peer
 // connections (device/p2p_types.hpp), restating the reference's queueing

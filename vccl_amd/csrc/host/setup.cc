@@ -14,7 +14,7 @@
 #include "../device/coll_types.hpp"
 #include "../device/ring_launch.hpp"  // kRingMaxThreads
 #include "core.h"                     // VWARN / VINFO / param_int
-#include "plan.h"                     // ll_rooted_max, direct_rooted_max
+#include "plan.h"                     // ll_rooted_max, direct_rooted_max, ll_a2a_max, direct_a2a_max
 
 namespace vccl {
 
@@ -379,12 +379,21 @@ ncclResult_t setup_local(int n, int minCTAs, int maxCTAs, CommSetup* s, SetupSiz
   // LL all-to-all (the small pairs of ncclAllToAll(v) in one hop): opt-in the
   // same way, bytes per ordered pair; the pairs above it keep the p2p FIFOs
   s->llA2aMaxBytes = ll_a2a_max_of(*s, param_int("LL_A2A_THRESHOLD", 0), n, false, n > 1 && s->p2pOff == kP2pOn);
+  // Direct all-to-all (the mid-size pairs, 16-byte payload stores through the
+  // inbox): opt-in the same way, bytes per ordered pair, at most one region
+  s->directA2aMaxBytes =
+      direct_a2a_max_of(*s, param_int("DIRECT_A2A_THRESHOLD", 0), n, false, n > 1 && s->p2pOff == kP2pOn);
   return ncclSuccess;
 }
 
 size_t ll_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool hasP2p) {
   return (size_t)ll_a2a_max(threshold, (int64_t)s.llLines * 8, (s.algoAllowed & kAllowLLRsAg) != 0, anyNet, nRanks,
                             hasP2p);
+}
+
+size_t direct_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool hasP2p) {
+  return (size_t)direct_a2a_max(threshold, s.dRegionBytes, (s.algoAllowed & kAllowDirect) != 0, anyNet, nRanks,
+                                hasP2p);
 }
 
 static bool same_gpu(const PeerId& a, const PeerId& b) { return a.hostHash == b.hostHash && a.busId == b.busId; }
@@ -409,7 +418,7 @@ ncclResult_t setup_mesh(int rank, const std::vector<PeerId>& peers, CommSetup* s
     // (full xGMI mesh): all-reduce takes the ring.  Net channels move
     // through the proxy, a few are enough (NCCL's net defaults use 2-4).
     s->llMaxBytes = s->llRsAgMaxBytes = s->llRootedMaxBytes = s->llA2aMaxBytes = 0;
-    s->directMaxBytes = s->directRsAgMaxBytes = s->directRootedMaxBytes = 0;
+    s->directMaxBytes = s->directRsAgMaxBytes = s->directRootedMaxBytes = s->directA2aMaxBytes = 0;
     s->ll128MinBytes = s->ll128MaxBytes = 0;
     if (s->algoForce == 4) s->algoForce = 1;  // LL128 lines need the xGMI mesh: SIMPLE
     // ... so no LL128 FIFO is mapped: the local one is dropped too

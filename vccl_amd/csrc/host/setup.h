@@ -70,6 +70,10 @@ struct CommSetup {
   // (VCCL_DIRECT_ROOTED_THRESHOLD, plan.h direct_rooted_max; default 0 = off;
   // not part of what vcclCommSetup reports either)
   size_t directRootedMaxBytes = 0;
+  // Largest ordered pair of an ncclAllToAll(v) on the one-hop direct path
+  // (VCCL_DIRECT_A2A_THRESHOLD, plan.h direct_a2a_max; default 0 = off; not
+  // part of what vcclCommSetup reports either)
+  size_t directA2aMaxBytes = 0;
 };
 enum { kP2pOn = 0, kP2pOffEnv = 1, kP2pOffRanks = 2, kP2pOffNet = 3 };
 
@@ -90,6 +94,9 @@ ncclResult_t setup_local(int nRanks, int minCTAs, int maxCTAs, CommSetup* s, Set
 // CommSetup::llA2aMaxBytes for a VCCL_LL_A2A_THRESHOLD of `threshold` on a comm
 // whose other fields are decided (setup_local; vcclCommSetA2aThreshold).
 size_t ll_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool hasP2p);
+// CommSetup::directA2aMaxBytes for a VCCL_DIRECT_A2A_THRESHOLD of `threshold`,
+// likewise (setup_local; vcclCommSetDirectA2aThreshold).
+size_t direct_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool hasP2p);
 
 // What a rank publishes about where it runs (a PeerMap's identity fields).
 struct PeerId {

@@ -54,6 +54,8 @@ EXPORTED = [
     "vcclRootedAlgoEx", "vcclDirectRootedPlan",
     # one-hop LL all-to-all: the per-pair limit, one call's LL / FIFO split, the counters, the live knob
     "vcclLLA2aMax", "vcclLLA2aPlan", "vcclCommA2aStats", "vcclCommSetA2aThreshold",
+    # one-hop direct all-to-all: the per-pair limit, one call's LL / direct / FIFO split, the counters, the live knob
+    "vcclDirectA2aMax", "vcclDirectA2aPlan", "vcclCommA2aStatsEx", "vcclCommSetDirectA2aThreshold",
     # out of scope, exported so libnccl-linked binaries load: WARN + ncclInvalidUsage
     "ncclGroupSimulateEnd",
     # memory / registration / scalable init (what a libnccl caller such as
@@ -187,6 +189,15 @@ def lib() -> ctypes.CDLL:
         "vcclCommA2aStats": [vp, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong),
                              ctypes.POINTER(ctypes.c_ulonglong)],
         "vcclCommSetA2aThreshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
+        "vcclDirectA2aMax": [ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int, c_int,
+                             ctypes.POINTER(ctypes.c_int64)],
+        "vcclDirectA2aPlan": [c_int, c_int, ctypes.POINTER(c_size), ctypes.POINTER(c_size), c_int, ctypes.c_int64,
+                              ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int, ctypes.POINTER(c_int),
+                              ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                              ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int),
+                              ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
+        "vcclCommA2aStatsEx": [vp] + [ctypes.POINTER(ctypes.c_ulonglong)] * 5,
+        "vcclCommSetDirectA2aThreshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
         "vcclAlgoSelection": [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(c_int),
                               ctypes.POINTER(c_int)],
         "vcclCommSetup": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(u64),
@@ -438,6 +449,42 @@ def ll_a2a_plan(nranks: int, rank: int, send_bytes, recv_bytes, uniform: bool, l
             "res_sends": list(rs[:nrs.value]), "res_recvs": list(rr[:nrr.value])}
 
 
+A2A_FIFO, A2A_LL, A2A_DIRECT = 0, 1, 2
+
+
+def direct_a2a_max(threshold: int | None, region_bytes: int, direct_allowed: bool = True, any_net: bool = False,
+                   nranks: int = 8, has_p2p: bool = True) -> int:
+    """vcclDirectA2aMax: the per-pair limit of the one-hop direct all-to-all as
+    a comm takes it (None: VCCL_DIRECT_A2A_THRESHOLD from the environment; 0 = off)."""
+    eff = ctypes.c_int64()
+    check(lib().vcclDirectA2aMax(-1 if threshold is None else threshold, region_bytes, int(direct_allowed),
+                                 int(any_net), nranks, int(has_p2p), ctypes.byref(eff)), "vcclDirectA2aMax")
+    return eff.value
+
+
+def direct_a2a_plan(nranks: int, rank: int, send_bytes, recv_bytes, uniform: bool, ll_a2a_max: int,
+                    direct_a2a_max: int, lines_per_slot: int, min_ctas: int = 1, max_ctas: int = 64,
+                    direct_max_blocks: int = 64) -> dict:
+    """vcclDirectA2aPlan: one all-to-all(v) call's split between the LL launch,
+    the direct launch and the FIFO launch as `rank` runs it.  Returns
+    ll_launch / direct_launch, send_path / recv_path (per peer: A2A_FIFO,
+    A2A_LL, A2A_DIRECT), n_blocks / blk_bytes (the direct launch's geometry),
+    res_sends / res_recvs (peers left to the FIFOs)."""
+    n = nranks
+    arr = ctypes.c_size_t * n
+    ci = ctypes.c_int * n
+    sp, rp, rs, rr = ci(), ci(), ci(), ci()
+    ll, dl, nb, nrs, nrr = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    blk = ctypes.c_int64()
+    check(lib().vcclDirectA2aPlan(n, rank, arr(*send_bytes), arr(*recv_bytes), int(uniform), ll_a2a_max,
+                                  direct_a2a_max, lines_per_slot, min_ctas, max_ctas, direct_max_blocks, sp, rp,
+                                  ctypes.byref(ll), ctypes.byref(dl), ctypes.byref(nb), ctypes.byref(blk),
+                                  ctypes.byref(nrs), rs, ctypes.byref(nrr), rr), "vcclDirectA2aPlan")
+    return {"ll_launch": bool(ll.value), "direct_launch": bool(dl.value), "send_path": list(sp), "recv_path": list(rp),
+            "n_blocks": nb.value, "blk_bytes": blk.value,
+            "res_sends": list(rs[:nrs.value]), "res_recvs": list(rr[:nrr.value])}
+
+
 P2P_SEND, P2P_RECV, P2P_COPY = 0, 1, 2
 P2P_ITEM_FIELDS = ("launch", "wg", "kind", "sweep", "round", "part", "peer", "call", "call2", "offset", "bytes",
                    "steps")
@@ -627,6 +674,21 @@ class Comm:
         calls (every rank alike); returns the effective limit."""
         eff = ctypes.c_int64()
         check(lib().vcclCommSetA2aThreshold(self.handle, nbytes, ctypes.byref(eff)), "vcclCommSetA2aThreshold")
+        return eff.value
+
+    def a2a_stats_ex(self) -> tuple[int, int, int, int, int]:
+        """vcclCommA2aStatsEx: (LL launches, LL pairs, direct launches, direct
+        pairs, FIFO pairs) of this comm's all-to-alls; pairs = sends + recvs."""
+        v = [ctypes.c_ulonglong() for _ in range(5)]
+        check(lib().vcclCommA2aStatsEx(self.handle, *[ctypes.byref(x) for x in v]), "vcclCommA2aStatsEx")
+        return tuple(x.value for x in v)
+
+    def set_direct_a2a_threshold(self, nbytes: int) -> int:
+        """vcclCommSetDirectA2aThreshold: the per-pair direct all-to-all limit
+        for later calls (every rank alike); returns the effective limit."""
+        eff = ctypes.c_int64()
+        check(lib().vcclCommSetDirectA2aThreshold(self.handle, nbytes, ctypes.byref(eff)),
+              "vcclCommSetDirectA2aThreshold")
         return eff.value
 
     def coll_algo(self, coll: int, count: int, dtype: int) -> str:
