@@ -1,5 +1,5 @@
 """CPU checks of the one-hop direct all-to-all (host/plan.cc direct_a2a_max /
-direct_a2a_plan): the per-pair limit with its clamp and off switches, the
+a2a_plan through vcclDirectA2aPlan): the per-pair limit with its clamp and off switches, the
 parent's plan at limit 0, the three-way pair rule's symmetry between the two
 ends, the launch rule, the comm-wide geometry, the residual sends and recvs as
 a matched set for the p2p planner and its FIFO simulator, and the region-and-

@@ -1,5 +1,5 @@
 """CPU checks of the one-hop LL all-to-all (host/plan.cc ll_a2a_max /
-ll_a2a_plan): the per-pair limit with its off switches, the pair rule's
+a2a_plan through vcclLLA2aPlan): the per-pair limit with its off switches, the pair rule's
 symmetry between the two ends, the line-0 rule, the launch rule, the residual
 sends and recvs as a matched set for the p2p planner, and the slot simulator of
 tests/test_ll_rooted_plan.py run over sequences that mix all-to-all(v) plans

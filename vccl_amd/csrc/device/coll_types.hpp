@@ -55,21 +55,23 @@ __host__ __device__ __forceinline__ bool ll_rooted_line0_is_data(bool reduce, in
   return reduce ? reader == root0 : writer == root0;
 }
 
-// One-hop LL all-to-all (ll.hpp ll_alltoall; host/plan.cc ll_a2a_plan).  The
-// tables are ROTATED to the rank: entry k belongs to rank (rank + k) mod
-// nRanks, entry 0 to the rank itself.  An ordered pair whose "LL pair" bit is
-// set moves its bytes as lines [0, ceil(bytes / 8)) of slot (parity, writer) at
-// the reader; every other pair moves in the FIFO launch of the same call and
-// only exchanges the zero arrival token on line 0 here.  The LL pairs' lines
-// are flattened in entry order: entry k's send lines are the grid-stride
-// indices [sendLine0[k], sendLine0[k + 1]), likewise recvLine0.
-constexpr int kLLA2aMaxRanks = kOrderMaxRanks;
-struct LLA2aPeer {
+// One row of an all-to-all launch's per-peer table (LLA2aWork, DirectA2aWork;
+// host/plan.cc a2a_plan gives every ordered pair to one launch of its call).
+// The tables are ROTATED to the rank: entry k belongs to rank (rank + k) mod
+// nRanks, entry 0 to the rank itself.
+struct A2aPeer {
   const char* send;        // my block for this peer
   char* recv;              // where this peer's block lands
   int64_t sendBytes, recvBytes;
-  int32_t sendLL, recvLL;  // the "LL pair" bit of each direction
+  int32_t sendHere, recvHere;  // this direction travels in this launch
 };
+// One-hop LL all-to-all (ll.hpp ll_alltoall).  An ordered pair that travels
+// here moves its bytes as lines [0, ceil(bytes / 8)) of slot (parity, writer) at
+// the reader; every other pair moves in the direct or FIFO launch of the same
+// call and only exchanges the zero arrival token on line 0 here.  The LL pairs'
+// lines are flattened in entry order: entry k's send lines are the grid-stride
+// indices [sendLine0[k], sendLine0[k + 1]), likewise recvLine0.
+constexpr int kLLA2aMaxRanks = kOrderMaxRanks;
 struct LLA2aWork {
   DevComm* comm;
   int rank, nRanks;
@@ -77,7 +79,7 @@ struct LLA2aWork {
   int pad;
   char* localBuf;          // my LL buffer
   char* peerBuf[kLLA2aMaxRanks];  // rotated: peerBuf[k] = the LL buffer of rank (rank + k) mod nRanks
-  LLA2aPeer peer[kLLA2aMaxRanks];
+  A2aPeer peer[kLLA2aMaxRanks];
   int64_t sendLine0[kLLA2aMaxRanks + 1], recvLine0[kLLA2aMaxRanks + 1];  // [1 .. nRanks]; [nRanks] = the totals
 };
 static_assert(sizeof(LLA2aWork) <= 4096, "LLA2aWork must fit the kernel-argument budget");
@@ -184,19 +186,12 @@ struct DirectBatch {
 };
 // hipModuleLaunchKernel's by-value argument segment is 4 KiB
 static_assert(sizeof(DirectBatch) <= 4096, "DirectBatch must fit the kernel-argument budget");
-// One-hop direct all-to-all(v) (direct.hpp direct_alltoall; host/plan.cc
-// direct_a2a_plan).  The table is ROTATED to the rank like LLA2aWork's: entry k
-// belongs to rank (rank + k) mod nRanks, entry 0 to the rank itself.  An
-// ordered pair whose "direct pair" bit is set moves its bytes as [0, bytes) of
-// region (0, 0, writer) at the reader; workgroup b moves bytes [b * blkBytes,
-// (b + 1) * blkBytes) of every pair.  Every other pair moves in the LL or FIFO
-// launch of the same call and only exchanges flags here.
-struct DirectA2aPeer {
-  const char* send;        // my block for this peer
-  char* recv;              // where this peer's block lands
-  int64_t sendBytes, recvBytes;
-  int32_t sendDirect, recvDirect;  // the "direct pair" bit of each direction
-};
+// One-hop direct all-to-all(v) (direct.hpp direct_alltoall; the table is
+// A2aPeer's, rotated like LLA2aWork's).  An ordered pair that travels here
+// moves its bytes as [0, bytes) of region (0, 0, writer) at the reader;
+// workgroup b moves bytes [b * blkBytes, (b + 1) * blkBytes) of every pair.
+// Every other pair moves in the LL or FIFO launch of the same call and only
+// exchanges flags here.
 struct DirectA2aWork {
   DevComm* comm;
   const DirectPeers* peers;
@@ -205,7 +200,7 @@ struct DirectA2aWork {
   int pad;
   int64_t blkBytes;        // bytes per block, a multiple of 16
   int64_t regionBytes;     // bytes per (phase, rank) inbox region
-  DirectA2aPeer peer[kDirectMaxRanks];
+  A2aPeer peer[kDirectMaxRanks];
 };
 static_assert(sizeof(DirectA2aWork) <= 4096, "DirectA2aWork must fit the kernel-argument budget");
 

@@ -876,7 +876,7 @@ __device__ void direct_reduce_part(const DirectWork& w, uint32_t& e, int& shFail
 // One-hop all-to-all(v) (byte copies): the all-gather above with its own
 // source block and length per peer.  The ordered pair (me -> p) of B bytes
 // occupies bytes [0, B) of region (0, 0, me) at p — for the pairs the host
-// marked "direct pair" (host/plan.cc direct_a2a_plan; both ends decide on the
+// marked "direct pair" (host/plan.cc a2a_plan; both ends decide on the
 // same B and comm-wide limits).  The other pairs of a v-call travel in the LL
 // launch before or the FIFO launch behind this one, so a rank may have nothing
 // to say to a peer here: every workgroup of the grid still posts to and waits
@@ -896,7 +896,7 @@ __device__ void direct_reduce_part(const DirectWork& w, uint32_t& e, int& shFail
 __device__ __forceinline__ void direct_alltoall(const DirectA2aWork& w) {
   using Fn = FnCopy<uint8_t>;
   const Fn fn(0);
-  __shared__ DirectA2aPeer sh[kDirectMaxRanks];
+  __shared__ A2aPeer sh[kDirectMaxRanks];
   __shared__ int shFail;
 #pragma unroll
   for (int i = 0; i < kDirectMaxRanks; i++)
@@ -923,12 +923,12 @@ __device__ __forceinline__ void direct_alltoall(const DirectA2aWork& w) {
   for (int i = 0; i < n - 1; i++) {
     const int k = 1 + (b + i) % (n - 1);
     const int p = me + k < n ? me + k : me + k - n;
-    if (!sh[k].sendDirect) continue;
+    if (!sh[k].sendHere) continue;
     const char* s[kDirectMaxRanks] = {sh[k].send + lo};
     char* d[kDirectMaxRanks] = {P.buf[p] + direct_region_off(0, 0, me, n, w.regionBytes) + lo};
     direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len_of(sh[k].sendBytes), tid, nt);
   }
-  if (sh[0].sendDirect && sh[0].send != sh[0].recv) {  // the self block (nothing when already in place)
+  if (sh[0].sendHere && sh[0].send != sh[0].recv) {  // the self block (nothing when already in place)
     const char* s[kDirectMaxRanks] = {sh[0].send + lo};
     char* d[kDirectMaxRanks] = {sh[0].recv + lo};
     direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len_of(sh[0].sendBytes), tid, nt);
@@ -938,7 +938,7 @@ __device__ __forceinline__ void direct_alltoall(const DirectA2aWork& w) {
   if (direct_wait(dw, myFlags, 0, 0, b, e, &shFail)) {
     for (int k = 1; k < n; k++) {
       const int q = me + k < n ? me + k : me + k - n;
-      if (!sh[k].recvDirect) continue;
+      if (!sh[k].recvHere) continue;
       const char* s[kDirectMaxRanks] = {myBuf + direct_region_off(0, 0, q, n, w.regionBytes) + lo};
       char* d[kDirectMaxRanks] = {sh[k].recv + lo};
       direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len_of(sh[k].recvBytes), tid, nt);

@@ -368,7 +368,7 @@ __device__ inline void ll_allgather(const LLWork& w) {
 // One-hop LL all-to-all(v) (bytes): the reduce-scatter's write pattern without
 // the fold.  The block of ordered pair (me -> p) goes, as lines [0, ceil(B / 8)),
 // into slot (parity, me) at p, and p copies it out — for the pairs the host
-// marked "LL pair" (B <= the comm's per-pair limit, host/plan.cc ll_a2a_plan;
+// marked "LL pair" (B <= the comm's per-pair limit, host/plan.cc a2a_plan;
 // both ends decide on the same B).  A v-call's larger pairs travel in the FIFO
 // launch behind this one, so a rank may have nothing to say to a peer here:
 // line 0 of EVERY ordered pair is still stored once and seen once per launch —
@@ -378,7 +378,7 @@ __device__ inline void ll_allgather(const LLWork& w) {
 // The per-peer table (rotated to me: entry k = rank me + k) sits in LDS, filled
 // through constant indices like ll_load_parts.
 struct LLA2aTable {
-  LLA2aPeer p[kLLA2aMaxRanks];
+  A2aPeer p[kLLA2aMaxRanks];
   char* buf[kLLA2aMaxRanks];
   int64_t sendLine0[kLLA2aMaxRanks + 1], recvLine0[kLLA2aMaxRanks + 1];
 };
@@ -413,7 +413,7 @@ __device__ inline void ll_alltoall(const LLA2aWork& w) {
   int k = 1;
   for (int64_t l = gtid; l < sendLines; l += gthreads) {
     while (k + 1 < n && l >= sh.sendLine0[k + 1]) k++;
-    const LLA2aPeer& p = sh.p[k];
+    const A2aPeer& p = sh.p[k];
     const int64_t pl = l - sh.sendLine0[k];
     const uint64_t v = ll_load8(p.send, pl, p.sendBytes);
     u32x4 line;
@@ -436,13 +436,13 @@ __device__ inline void ll_alltoall(const LLA2aWork& w) {
     line.z = 0;
     line.w = e;
     for (int j = 1; j < n; j++) {
-      if (sh.p[j].sendLL && sh.p[j].sendBytes > 0) continue;
+      if (sh.p[j].sendHere && sh.p[j].sendBytes > 0) continue;
       const SysAddr d = sys_addr(sh.buf[j] + mySlot);
       __builtin_amdgcn_raw_buffer_store_b128(line, d.r, d.voff, 0, kSysAux);
     }
   }
   // The self block: a local copy (nothing when it is already in place).
-  if (sh.p[0].sendLL && sh.p[0].recv != sh.p[0].send) {
+  if (sh.p[0].sendHere && sh.p[0].recv != sh.p[0].send) {
     const int64_t nb = sh.p[0].sendBytes;
     for (int64_t l = gtid; l < (nb + 7) / 8; l += gthreads)
       ll_store8(sh.p[0].recv, l, nb, ll_load8(sh.p[0].send, l, nb));
@@ -453,7 +453,7 @@ __device__ inline void ll_alltoall(const LLA2aWork& w) {
   k = 1;
   for (int64_t l = gtid; l < recvLines && ok; l += gthreads) {
     while (k + 1 < n && l >= sh.recvLine0[k + 1]) k++;
-    const LLA2aPeer& p = sh.p[k];
+    const A2aPeer& p = sh.p[k];
     const int64_t pl = l - sh.recvLine0[k];
     const int q = me + k < n ? me + k : me + k - n;
     uint64_t x;
@@ -463,7 +463,7 @@ __device__ inline void ll_alltoall(const LLA2aWork& w) {
   }
   if (gtid == 0 && ok) {  // ... and every peer's line 0 that was not read as data
     for (int j = 1; j < n; j++) {
-      if (sh.p[j].recvLL && sh.p[j].recvBytes > 0) continue;
+      if (sh.p[j].recvHere && sh.p[j].recvBytes > 0) continue;
       const int q = me + j < n ? me + j : me + j - n;
       uint64_t x;
       if (!ll_read_line(w.localBuf + ll_slot_off(parity, q, n, w.linesPerSlot), e, w.comm, &x)) break;

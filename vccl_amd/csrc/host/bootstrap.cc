@@ -258,8 +258,8 @@ void bootstrap_close(Bootstrap* b) {
 
 }  // namespace vccl
 
-extern "C" __attribute__((visibility("default"))) ncclResult_t vcclBootstrapAllGather(
-    const ncclUniqueId* id, int rank, int nranks, void* buf, size_t bytesPerRank) {
+VCCL_EXPORT ncclResult_t vcclBootstrapAllGather(const ncclUniqueId* id, int rank, int nranks, void* buf,
+                                                size_t bytesPerRank) {
   if (!id || !buf || nranks < 1 || rank < 0 || rank >= nranks) return ncclInvalidArgument;
   vccl::Bootstrap* b = nullptr;
   ncclResult_t r = vccl::bootstrap_init(id, rank, nranks, &b);

@@ -53,6 +53,9 @@ void log_msg(int level, const char* file, int line, const char* fmt, ...)
     if (r_ != ncclSuccess) return r_;                                                \
   } while (0)
 
+// The C ABI (include/nccl.h, vccl_ext.h, vccl_bootstrap.h): everything else is hidden.
+#define VCCL_EXPORT extern "C" __attribute__((visibility("default")))
+
 // ----------------------------------------------------------------- params
 // NCCL_PARAM idiom (param.h:17-25): env NCCL_<name> (or VCCL_<name>), cached.
 int64_t param_int(const char* name, int64_t deflt);

@@ -572,7 +572,6 @@ ncclResult_t comm_destroy(ncclComm* c, bool abort) {
 
 using namespace vccl;
 
-#define VCCL_EXPORT extern "C" __attribute__((visibility("default")))
 #define VCCL_ALIAS(name) __attribute__((alias(#name), visibility("default")))
 
 VCCL_EXPORT ncclResult_t ncclGetVersion(int* version) {

@@ -392,7 +392,6 @@ static ncclResult_t direct_work_of(const Task& t, DirectWork* out, int* ktOut, i
   const bool rooted = t.coll == kBroadcast || t.coll == kReduce;
   const auto [count, esz] = call_size(t.coll, t.count, t.datatype);  // all-gather / broadcast: bytes
   const int64_t eltAlign = std::max<int64_t>(1, 16 / esz);
-  auto align_up = [](int64_t x, int64_t a) { return (x + a - 1) / a * a; };
   DirectWork w{};
   fill_op_fields(w, t);
   w.peers = comm->dPeers;
@@ -431,14 +430,8 @@ static ncclResult_t direct_work_of(const Task& t, DirectWork* out, int* ktOut, i
     if (t.coll == kReduceScatter) w.cbd = rs_cbd(t, kProtoSimple);
   }
   w.nChunks = (int)((count + w.chunkElts - 1) / w.chunkElts);
-  // Blocks of >= 16 KiB (one 512-thread x 2-pack hunk), at most the cap.
-  const int64_t minBlk = (16 << 10) / esz;
-  // CTA bounds first, then the co-residency caps (directMaxBlocks,
-  // kDirectMaxBlocks) last, so NCCL_MIN_CTAS cannot push past them.
-  int64_t nb = (shard0 + minBlk - 1) / minBlk;
-  nb = std::max<int64_t>(std::min<int64_t>(nb, comm->maxCTAs), comm->minCTAs);
-  nb = std::max<int64_t>(1, std::min<int64_t>({nb, (int64_t)comm->directMaxBlocks, (int64_t)kDirectMaxBlocks}));
-  w.blkElts = align_up((shard0 + nb - 1) / nb, eltAlign);
+  // Blocks of >= 16 KiB within the CTA bounds, then the co-residency caps (plan.h).
+  w.blkElts = direct_blk_elts(shard0, esz, comm->minCTAs, comm->maxCTAs, comm->directMaxBlocks);
   if (blkForce > 0) {
     if (blkForce < w.blkElts || blkForce % eltAlign) return ncclInternalError;
     w.blkElts = blkForce;
@@ -763,17 +756,34 @@ static ncclResult_t launch_p2p(const std::vector<Task>& ts) {
   return r;
 }
 
-// ------------------------------------------------------------ LL all-to-all
+// ---------------------------------------------------------------- all-to-all
+// The rotated per-peer table of one all-to-all launch (coll_types.hpp A2aPeer):
+// entry k is rank (me + k) mod n's, its direction bits set where `plan` gave
+// the pair to `path`.
+static void fill_a2a_peers(const Task& t, const A2aPlanOut& plan, int path, A2aPeer* table) {
+  const int n = t.comm->nRanks, me = t.comm->rank;
+  const A2aArgs& a = *t.a2a;
+  for (int k = 0; k < n; k++) {
+    const int p = (me + k) % n;
+    A2aPeer& e = table[k];
+    e.send = t.sendbuff ? (const char*)t.sendbuff + a.sendOff[p] : nullptr;
+    e.recv = t.recvbuff ? (char*)t.recvbuff + a.recvOff[p] : nullptr;
+    e.sendBytes = a.sendBytes[p];
+    e.recvBytes = a.recvBytes[p];
+    e.sendHere = plan.sendPath[p] == path;
+    e.recvHere = plan.recvPath[p] == path;
+  }
+}
+
 // The LL launch of one ncclAllToAll(v) (ll.hpp ll_alltoall) on the call's
 // stream, ordered against the comm's other launches like a call outside a
 // group (launch_task).  The tables go in rotated to this rank, the LL pairs'
 // lines flattened in that order.  Plain ncclSend / ncclRecv never come here:
 // they are not collective — a peer outside the exchange launches nothing, so
 // the arrival barrier the slot reuse rests on (ll.hpp header) would not hold.
-static ncclResult_t launch_ll_a2a(const Task& t, const LLA2aPlanOut& plan) {
+static ncclResult_t launch_ll_a2a(const Task& t, const A2aPlanOut& plan) {
   ncclComm* comm = t.comm;
   const int n = comm->nRanks, me = comm->rank;
-  const A2aArgs& a = *t.a2a;
   if (n > kLLA2aMaxRanks || !comm->llBuf || (int)comm->llPeer.size() < n) return ncclInternalError;
   LLA2aWork w{};
   w.comm = comm->devComm;
@@ -781,21 +791,15 @@ static ncclResult_t launch_ll_a2a(const Task& t, const LLA2aPlanOut& plan) {
   w.nRanks = n;
   w.linesPerSlot = comm->llLines;
   w.localBuf = comm->llBuf;
+  fill_a2a_peers(t, plan, kA2aLL, w.peer);
   int64_t sl = 0, rl = 0;
   for (int k = 0; k < n; k++) {
-    const int p = (me + k) % n;
-    w.peerBuf[k] = comm->llPeer[p];
-    LLA2aPeer& e = w.peer[k];
-    e.send = t.sendbuff ? (const char*)t.sendbuff + a.sendOff[p] : nullptr;
-    e.recv = t.recvbuff ? (char*)t.recvbuff + a.recvOff[p] : nullptr;
-    e.sendBytes = a.sendBytes[p];
-    e.recvBytes = a.recvBytes[p];
-    e.sendLL = plan.sendLL[p];
-    e.recvLL = plan.recvLL[p];
+    w.peerBuf[k] = comm->llPeer[(me + k) % n];
+    const A2aPeer& e = w.peer[k];
     w.sendLine0[k] = sl;
     w.recvLine0[k] = rl;
     if (k == 0) continue;  // the self block is not part of the flattening
-    const int64_t s = e.sendLL ? ll_lines_of(e.sendBytes) : 0, r = e.recvLL ? ll_lines_of(e.recvBytes) : 0;
+    const int64_t s = e.sendHere ? ll_lines_of(e.sendBytes) : 0, r = e.recvHere ? ll_lines_of(e.recvBytes) : 0;
     if (s > comm->llLines || r > comm->llLines) return ncclInternalError;
     sl += s;
     rl += r;
@@ -814,16 +818,14 @@ static ncclResult_t launch_ll_a2a(const Task& t, const LLA2aPlanOut& plan) {
   return stream_mark(comm, t.stream, cs);
 }
 
-// ------------------------------------------------------ direct all-to-all
 // The direct launch of one ncclAllToAll(v) (direct.hpp direct_alltoall) on the
 // call's stream, ordered against the comm's other launches exactly like
 // launch_ll_a2a.  The table goes in rotated to this rank; the grid is the
 // plan's nBlocks, already under the co-residency caps the other direct kernels
 // take (directMaxBlocks, which ranks sharing a GPU lower; kDirectMaxBlocks).
-static ncclResult_t launch_direct_a2a(const Task& t, const DirectA2aPlanOut& plan) {
+static ncclResult_t launch_direct_a2a(const Task& t, const A2aPlanOut& plan) {
   ncclComm* comm = t.comm;
   const int n = comm->nRanks, me = comm->rank;
-  const A2aArgs& a = *t.a2a;
   if (n > kDirectMaxRanks || !comm->dPeers || plan.nBlocks < 1 || plan.nBlocks > kDirectMaxBlocks ||
       plan.blkBytes < 16 || plan.blkBytes % 16)
     return ncclInternalError;
@@ -837,16 +839,10 @@ static ncclResult_t launch_direct_a2a(const Task& t, const DirectA2aPlanOut& pla
   w.nBlocks = plan.nBlocks;
   w.blkBytes = plan.blkBytes;
   w.regionBytes = comm->dRegionBytes;
+  fill_a2a_peers(t, plan, kA2aDirect, w.peer);
   for (int k = 0; k < n; k++) {
-    const int p = (me + k) % n;
-    DirectA2aPeer& e = w.peer[k];
-    e.send = t.sendbuff ? (const char*)t.sendbuff + a.sendOff[p] : nullptr;
-    e.recv = t.recvbuff ? (char*)t.recvbuff + a.recvOff[p] : nullptr;
-    e.sendBytes = a.sendBytes[p];
-    e.recvBytes = a.recvBytes[p];
-    e.sendDirect = plan.sendPath[p] == kA2aDirect;
-    e.recvDirect = plan.recvPath[p] == kA2aDirect;
-    if ((e.sendDirect && e.sendBytes > cover) || (e.recvDirect && e.recvBytes > cover)) return ncclInternalError;
+    const A2aPeer& e = w.peer[k];
+    if ((e.sendHere && e.sendBytes > cover) || (e.recvHere && e.recvBytes > cover)) return ncclInternalError;
   }
   DeviceGuard dev(comm->device);
   HIPCHECK(dev.status);
@@ -881,9 +877,9 @@ static ncclResult_t launch_comm_p2p(const std::vector<Task>& mine) {
       continue;
     }
     const A2aArgs& a = *t.a2a;
-    DirectA2aPlanOut plan;
-    if (direct_a2a_plan(n, me, a.sendBytes, a.recvBytes, a.uniform, comm->llA2aMaxBytes, comm->directA2aMaxBytes,
-                        comm->llLines, comm->minCTAs, comm->maxCTAs, comm->directMaxBlocks, &plan) != ncclSuccess)
+    A2aPlanOut plan;
+    if (a2a_plan(n, me, a.sendBytes, a.recvBytes, a.uniform, comm->llA2aMaxBytes, comm->directA2aMaxBytes,
+                 comm->llLines, comm->minCTAs, comm->maxCTAs, comm->directMaxBlocks, &plan) != ncclSuccess)
       return ncclInternalError;
     const size_t nFifo = plan.resSends.size() + plan.resRecvs.size();
     const size_t nDirect = (size_t)std::count(plan.sendPath.begin(), plan.sendPath.end(), (char)kA2aDirect) +
@@ -893,14 +889,8 @@ static ncclResult_t launch_comm_p2p(const std::vector<Task>& mine) {
     comm->a2aFifoPairs += nFifo;
     comm->opCount += 2 * (size_t)n - nFifo;  // as the FIFO path counts them; whatever the outcome
     if (plan.llLaunch) {
-      LLA2aPlanOut ll;
-      ll.launch = true;
-      for (int p = 0; p < n; p++) {
-        ll.sendLL.push_back(plan.sendPath[p] == kA2aLL);
-        ll.recvLL.push_back(plan.recvPath[p] == kA2aLL);
-      }
       comm->a2aLLLaunches++;
-      NCCLCHECK(launch_ll_a2a(t, ll));
+      NCCLCHECK(launch_ll_a2a(t, plan));
     }
     if (plan.directLaunch) {
       comm->a2aDirectLaunches++;

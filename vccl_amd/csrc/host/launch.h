@@ -1,5 +1,6 @@
-// What launch.cc offers the API file (enqueue.cc): a checked call as a Task,
-// its launch alone or as part of a group, and the path queries.
+// What launch.cc offers the API file (enqueue.cc) and the extension exports
+// (ext.cc): a checked call as a Task, its launch alone or as part of a group,
+// and the path queries.
 #pragma once
 #include <vector>
 
@@ -15,7 +16,7 @@ inline bool is_p2p(int coll) { return coll == kTaskSend || coll == kTaskRecv; }
 // ... and of an ncclAllToAll(v) on a comm whose one-hop LL or direct all-to-all
 // is on (llA2aMaxBytes > 0 || directA2aMaxBytes > 0): one task; launch_group
 // gives its pairs within the limits to one LL launch and one direct launch
-// (plan.h direct_a2a_plan) and turns the rest into sends and recvs of the
+// (plan.h a2a_plan) and turns the rest into sends and recvs of the
 // group's p2p launch.  With both paths off the API expands the call into sends
 // and recvs itself, as it always did.
 enum { kTaskA2a = 7 };

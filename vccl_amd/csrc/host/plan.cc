@@ -555,45 +555,12 @@ ncclResult_t direct_rooted_plan(int coll, int nRanks, int rank, int root, int64_
   return ncclSuccess;
 }
 
-// ------------------------------------------------------------ LL all-to-all
+// ---------------------------------------------------------------- all-to-all
 uint64_t ll_a2a_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks, bool hasP2p) {
   if (threshold <= 0 || llSlotBytes <= 0 || !llAllowed || anyNet || nRanks < 2 || nRanks > kOrderMaxRanks || !hasP2p)
     return 0;
   return (uint64_t)std::min(threshold, llSlotBytes);
 }
-
-ncclResult_t ll_a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const int64_t* recvBytes, bool uniform,
-                         uint64_t llA2aMax, int64_t linesPerSlot, LLA2aPlanOut* out) {
-  const int n = nRanks;
-  out->sendLL.assign(n, 0);
-  out->recvLL.assign(n, 0);
-  out->stores.clear();
-  out->polls.clear();
-  out->resSends.clear();
-  out->resRecvs.clear();
-  // uniform: every pair carries sendBytes[0]; all of them LL, or none
-  out->launch = llA2aMax > 0 && (!uniform || (sendBytes[0] > 0 && ll_a2a_pair(llA2aMax, sendBytes[0])));
-  for (int k = 0; k < n; k++) {
-    const int p = (rank + k) % n;
-    bool s = out->launch && ll_a2a_pair(llA2aMax, sendBytes[p]);
-    bool r = out->launch && ll_a2a_pair(llA2aMax, recvBytes[p]);
-    if (p == rank) s = r = s && r && sendBytes[p] == recvBytes[p];  // else the FIFO launch's copy (or its refusal)
-    out->sendLL[p] = s;
-    out->recvLL[p] = r;
-    if (p == rank || !out->launch) continue;
-    const int64_t sl = s ? (sendBytes[p] + 7) / 8 : 0, rl = r ? (recvBytes[p] + 7) / 8 : 0;
-    if (sl > linesPerSlot || rl > linesPerSlot) return ncclInvalidArgument;
-    out->stores.push_back(sl > 0 ? LLRange{p, 0, 0, sl} : LLRange{p, -1, 0, 1});
-    out->polls.push_back(rl > 0 ? LLRange{p, 0, 0, rl} : LLRange{p, -1, 0, 1});
-  }
-  for (int p = 0; p < n; p++) {
-    if (!out->sendLL[p]) out->resSends.push_back(p);
-    if (!out->recvLL[p]) out->resRecvs.push_back(p);
-  }
-  return ncclSuccess;
-}
-
-// -------------------------------------------------------- direct all-to-all
 uint64_t direct_a2a_max(int64_t threshold, int64_t regionBytes, bool directAllowed, bool anyNet, int nRanks,
                         bool hasP2p) {
   if (threshold <= 0 || regionBytes <= 16 || !directAllowed || anyNet || nRanks < 2 || nRanks > kDirectMaxRanks ||
@@ -602,41 +569,47 @@ uint64_t direct_a2a_max(int64_t threshold, int64_t regionBytes, bool directAllow
   return (uint64_t)std::min(threshold, (regionBytes - 16) / 16 * 16);
 }
 
-ncclResult_t direct_a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const int64_t* recvBytes, bool uniform,
-                             uint64_t llA2aMax, uint64_t directA2aMax, int64_t linesPerSlot, int minCTAs, int maxCTAs,
-                             int directMaxBlocks, DirectA2aPlanOut* out) {
+ncclResult_t a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const int64_t* recvBytes, bool uniform,
+                      uint64_t llA2aMax, uint64_t directA2aMax, int64_t linesPerSlot, int minCTAs, int maxCTAs,
+                      int directMaxBlocks, A2aPlanOut* out) {
   const int n = nRanks;
-  LLA2aPlanOut ll;
-  const ncclResult_t llRes = ll_a2a_plan(n, rank, sendBytes, recvBytes, uniform, llA2aMax, linesPerSlot, &ll);
-  if (llRes != ncclSuccess) return llRes;
-  out->llLaunch = ll.launch;
-  // uniform: every pair carries sendBytes[0]; all of them direct, or none
-  out->directLaunch = directA2aMax > 0 && (uniform ? !ll.launch && sendBytes[0] > 0 &&
-                                                         (uint64_t)sendBytes[0] <= directA2aMax
-                                                   : true);
+  // the launch rule: a v-call launches every path that is on; a uniform call,
+  // whose pairs all carry sendBytes[0], the one path they all take
+  const int uniformPath = a2a_pair_path(llA2aMax, directA2aMax, sendBytes[0]);
+  auto launches = [&](uint64_t limit, int path) {
+    return limit > 0 && (!uniform || (sendBytes[0] > 0 && uniformPath == path));
+  };
+  out->llLaunch = launches(llA2aMax, kA2aLL);
+  out->directLaunch = launches(directA2aMax, kA2aDirect);
+  // a path without its launch takes no pair
+  const uint64_t llMax = out->llLaunch ? llA2aMax : 0, directMax = out->directLaunch ? directA2aMax : 0;
   out->sendPath.assign(n, kA2aFifo);
   out->recvPath.assign(n, kA2aFifo);
+  out->stores.clear();
+  out->polls.clear();
   out->resSends.clear();
   out->resRecvs.clear();
+  for (int k = 0; k < n; k++) {  // the kernels' rotation
+    const int p = (rank + k) % n;
+    // the self block: its path when both lengths agree, else the FIFO launch's copy (or its refusal)
+    if (p == rank && sendBytes[p] != recvBytes[p]) continue;
+    const int s = out->sendPath[p] = (char)a2a_pair_path(llMax, directMax, sendBytes[p]);
+    const int r = out->recvPath[p] = (char)a2a_pair_path(llMax, directMax, recvBytes[p]);
+    if (p == rank || !out->llLaunch) continue;
+    const int64_t sl = s == kA2aLL ? (sendBytes[p] + 7) / 8 : 0, rl = r == kA2aLL ? (recvBytes[p] + 7) / 8 : 0;
+    if (sl > linesPerSlot || rl > linesPerSlot) return ncclInvalidArgument;
+    out->stores.push_back(sl > 0 ? LLRange{p, 0, 0, sl} : LLRange{p, -1, 0, 1});
+    out->polls.push_back(rl > 0 ? LLRange{p, 0, 0, rl} : LLRange{p, -1, 0, 1});
+  }
   for (int p = 0; p < n; p++) {
-    bool s = out->directLaunch && !ll.sendLL[p] && (uint64_t)sendBytes[p] <= directA2aMax;
-    bool r = out->directLaunch && !ll.recvLL[p] && (uint64_t)recvBytes[p] <= directA2aMax;
-    if (p == rank) s = r = s && r && sendBytes[p] == recvBytes[p];  // else the FIFO launch's copy (or its refusal)
-    out->sendPath[p] = ll.sendLL[p] ? kA2aLL : s ? kA2aDirect : kA2aFifo;
-    out->recvPath[p] = ll.recvLL[p] ? kA2aLL : r ? kA2aDirect : kA2aFifo;
     if (out->sendPath[p] == kA2aFifo) out->resSends.push_back(p);
     if (out->recvPath[p] == kA2aFifo) out->resRecvs.push_back(p);
   }
   out->nBlocks = 0;
   out->blkBytes = 0;
   if (out->directLaunch) {
-    // launch.cc direct_work_of's block formula on M bytes: CTA bounds first,
-    // then the co-residency caps last
     const int64_t M = uniform ? sendBytes[0] : (int64_t)directA2aMax;
-    int64_t nb = (M + (16 << 10) - 1) / (16 << 10);
-    nb = std::max<int64_t>(std::min<int64_t>(nb, maxCTAs), minCTAs);
-    nb = std::max<int64_t>(1, std::min<int64_t>({nb, (int64_t)directMaxBlocks, (int64_t)kDirectMaxBlocks}));
-    out->blkBytes = ((M + nb - 1) / nb + 15) / 16 * 16;
+    out->blkBytes = direct_blk_elts(M, 1, minCTAs, maxCTAs, directMaxBlocks);
     out->nBlocks = (int)((M + out->blkBytes - 1) / out->blkBytes);
   }
   return ncclSuccess;

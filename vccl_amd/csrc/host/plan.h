@@ -1,13 +1,15 @@
 // The restatement of VCCL's planner (plan.cc): pure integer arithmetic on
 // plain structs — no runtime call, no communicator, no stream.  launch.cc
-// reads a comm into these inputs; the plan exports (enqueue.cc) and through
+// reads a comm into these inputs; the plan exports (ext.cc) and through
 // them the CPU parity tests (oracle/vccl_sched.py) pass explicit ones.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
 
 #include "../../../include/nccl.h"
+#include "../device/coll_types.hpp"
 #include "../device/ring_types.hpp"
 
 #pragma GCC visibility push(hidden)  // internal: the library's exported symbols stay the C ABI's
@@ -185,42 +187,13 @@ struct DirectRootedPlanOut {
 ncclResult_t direct_rooted_plan(int coll, int nRanks, int rank, int root, int64_t count, int64_t eltSize,
                                 int64_t regionBytes, int chunk, DirectRootedPlanOut* out);
 
-// ------------------------------------------------------------ LL all-to-all
+// ---------------------------------------------------------------- all-to-all
 // A comm's VCCL_LL_A2A_THRESHOLD (bytes per ordered pair) as it takes effect:
 // clamped to what one LL slot holds; 0 without LL buffers, with LL excluded by
 // NCCL_PROTO, with a peer behind the net proxy, with fewer than 2 or more than
 // kOrderMaxRanks ranks, or on a comm without point-to-point connections (the
 // pairs above the limit need them).
 uint64_t ll_a2a_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks, bool hasP2p);
-// Pair rule: the ordered pair (writer -> reader) of B bytes travels by LL iff
-// llA2aMax > 0 && B <= llA2aMax (B = 0 counts as LL: its token is all it needs).
-// Both ends know B and the comm-wide constant, nothing else enters.
-inline bool ll_a2a_pair(uint64_t llA2aMax, int64_t bytes) { return llA2aMax > 0 && (uint64_t)bytes <= llA2aMax; }
-// One ncclAllToAll (uniform) / ncclAllToAllv call as `rank` runs it (device/
-// ll.hpp ll_alltoall).  Launch rule, identical on every rank: a uniform call
-// launches LL iff 0 < bytes per pair <= llA2aMax and then has no FIFO work at
-// all, else it takes the FIFO path whole; a v-call launches LL whenever
-// llA2aMax > 0 — peers may hold LL pairs among themselves and expect this
-// rank's arrival token — and its pairs above the limit follow in the FIFO
-// launch.  Without an LL launch no pair is LL.  Pair (r -> p)'s data occupies
-// lines [0, ceil(B / 8)) of slot (parity, r) at p; stores / polls list them as
-// LLRange{peer, 0, 0, lines} and the 1-line zero token of every other pair as
-// LLRange{peer, -1, 0, 1}, so line 0 of every ordered pair is written once and
-// read once per launch.  The self block is LL (a local copy in the LL kernel)
-// when the launch happens, both its lengths agree and fit the limit; otherwise
-// it stays a FIFO-launch copy.  resSends / resRecvs: the peers whose send /
-// recv stays on the FIFOs, in peer order.  ncclInvalidArgument when an LL pair
-// exceeds the slot.
-struct LLA2aPlanOut {
-  std::vector<char> sendLL, recvLL;  // per peer
-  bool launch = false;
-  std::vector<LLRange> stores, polls;
-  std::vector<int> resSends, resRecvs;
-};
-ncclResult_t ll_a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const int64_t* recvBytes, bool uniform,
-                         uint64_t llA2aMax, int64_t linesPerSlot, LLA2aPlanOut* out);
-
-// -------------------------------------------------------- direct all-to-all
 // A comm's VCCL_DIRECT_A2A_THRESHOLD (bytes per ordered pair) as it takes
 // effect: clamped to what one inbox region holds ((regionBytes - 16) rounded
 // down to 16 bytes, the slack launch.cc direct_work_of leaves); 0 without
@@ -230,41 +203,66 @@ ncclResult_t ll_a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const i
 uint64_t direct_a2a_max(int64_t threshold, int64_t regionBytes, bool directAllowed, bool anyNet, int nRanks,
                         bool hasP2p);
 // Pair rule, three-way, from B and the two comm-wide limits alone (so both
-// ends agree): LL iff ll_a2a_pair; else direct iff directA2aMax > 0 && B <=
+// ends agree, nothing else enters): the ordered pair (writer -> reader) of B
+// bytes travels by LL iff llA2aMax > 0 && B <= llA2aMax (B = 0 counts as LL:
+// its token is all it needs); else direct iff directA2aMax > 0 && B <=
 // directA2aMax (B = 0 included); else the FIFOs.
 enum { kA2aFifo = 0, kA2aLL = 1, kA2aDirect = 2 };
 inline int a2a_pair_path(uint64_t llA2aMax, uint64_t directA2aMax, int64_t bytes) {
-  if (ll_a2a_pair(llA2aMax, bytes)) return kA2aLL;
+  if (llA2aMax > 0 && (uint64_t)bytes <= llA2aMax) return kA2aLL;
   return directA2aMax > 0 && (uint64_t)bytes <= directA2aMax ? kA2aDirect : kA2aFifo;
 }
+// The direct kernels' block length for a shard of `len` elements of `esz`
+// bytes (launch.cc direct_work_of, a2a_plan): nb = ceil(len / 16 KiB) blocks
+// (one 512-thread x 2-pack hunk each) clamped by maxCTAs / minCTAs, then by the
+// co-residency caps directMaxBlocks and kDirectMaxBlocks LAST, so NCCL_MIN_CTAS
+// cannot push past them; the length is alignUp(ceil(len / nb), 16
+// bytes), in elements.  The caller's grid is ceil(len / that).
+inline int64_t direct_blk_elts(int64_t len, int64_t esz, int minCTAs, int maxCTAs, int directMaxBlocks) {
+  const int64_t minBlk = (16 << 10) / esz, eltAlign = std::max<int64_t>(1, 16 / esz);
+  int64_t nb = (len + minBlk - 1) / minBlk;
+  nb = std::max<int64_t>(std::min<int64_t>(nb, maxCTAs), minCTAs);
+  nb = std::max<int64_t>(1, std::min<int64_t>({nb, (int64_t)directMaxBlocks, (int64_t)kDirectMaxBlocks}));
+  return ((len + nb - 1) / nb + eltAlign - 1) / eltAlign * eltAlign;
+}
 // One ncclAllToAll (uniform) / ncclAllToAllv call as `rank` runs it (device/
-// direct.hpp direct_alltoall).  Launch rule, identical on every rank: a uniform
-// call of B bytes per pair is one LL launch and nothing else when 0 < B <=
-// llA2aMax, else one direct launch and nothing else when 0 < B <= directA2aMax,
-// else the FIFO path whole; a v-call has an LL launch iff llA2aMax > 0, then
-// exactly one direct launch iff directA2aMax > 0 — even when this rank's row
-// and column hold no direct pair: peers wait for its flags — then the FIFO
-// launch for the residual pairs.  A path without its launch takes no pair.
-// The self block is LL as ll_a2a_plan has it; else a local copy in the direct
-// kernel when that launch happens, both lengths agree and fit directA2aMax
-// (the kernel skips it when the pointers coincide); else a FIFO-launch copy.
-// Geometry, from comm-wide values only (M = B for a uniform call, directA2aMax
-// for a v-call: a rank knows only its row and column): nb = ceil(M / 16 KiB)
-// clamped by maxCTAs / minCTAs, then by directMaxBlocks and kDirectMaxBlocks
-// last; blkBytes = alignUp(ceil(M / nb), 16); nBlocks = ceil(M / blkBytes).
-// Pair (r -> p) occupies bytes [0, B) of region (0, 0, r) at p; one chunk, one
-// epoch per launch.  With directA2aMax == 0 the LL bits, the LL launch flag and
-// the residuals are ll_a2a_plan's.  ncclInvalidArgument as ll_a2a_plan.
-struct DirectA2aPlanOut {
+// ll.hpp ll_alltoall, device/direct.hpp direct_alltoall).  Launch rule,
+// identical on every rank: a uniform call of B bytes per pair is one LL launch
+// and nothing else when 0 < B <= llA2aMax, else one direct launch and nothing
+// else when 0 < B <= directA2aMax, else the FIFO path whole; a v-call has an LL
+// launch whenever llA2aMax > 0 — peers may hold LL pairs among themselves and
+// expect this rank's arrival token — then exactly one direct launch iff
+// directA2aMax > 0 — even when this rank's row and column hold no direct pair:
+// peers wait for its flags — then the FIFO launch for the residual pairs, those
+// above both limits.  A path without its launch takes no pair.  The self block
+// takes its path (a local copy in that path's kernel, which skips it when the
+// pointers coincide) when both its lengths agree; otherwise it stays a
+// FIFO-launch copy (or its refusal).
+// LL: pair (r -> p)'s data occupies lines [0, ceil(B / 8)) of slot (parity, r)
+// at p; stores / polls list them as LLRange{peer, 0, 0, lines} and the 1-line
+// zero token of every other pair as LLRange{peer, -1, 0, 1}, in the kernel's
+// rotation (rank + k) mod n, so line 0 of every ordered pair is written once
+// and read once per launch; both are empty without an LL launch.
+// ncclInvalidArgument when an LL pair exceeds the slot.
+// Direct geometry, from comm-wide values only (M = B for a uniform call,
+// directA2aMax for a v-call: a rank knows only its row and column): blkBytes =
+// direct_blk_elts(M, 1, ...), nBlocks = ceil(M / blkBytes); both 0 without a
+// direct launch.  Pair (r -> p) occupies bytes [0, B) of region (0, 0, r) at p;
+// one chunk, one epoch per launch.
+// resSends / resRecvs: the peers whose send / recv stays on the FIFOs, in peer
+// order.  With directA2aMax == 0 this is the two-way LL / FIFO plan
+// (vcclLLA2aPlan), and the CTA bounds and directMaxBlocks go unread.
+struct A2aPlanOut {
   std::vector<char> sendPath, recvPath;  // per peer: kA2aFifo / kA2aLL / kA2aDirect
   bool llLaunch = false, directLaunch = false;
-  int nBlocks = 0;         // 0 without a direct launch
+  int nBlocks = 0;
   int64_t blkBytes = 0;
+  std::vector<LLRange> stores, polls;
   std::vector<int> resSends, resRecvs;
 };
-ncclResult_t direct_a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const int64_t* recvBytes, bool uniform,
-                             uint64_t llA2aMax, uint64_t directA2aMax, int64_t linesPerSlot, int minCTAs, int maxCTAs,
-                             int directMaxBlocks, DirectA2aPlanOut* out);
+ncclResult_t a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const int64_t* recvBytes, bool uniform,
+                      uint64_t llA2aMax, uint64_t directA2aMax, int64_t linesPerSlot, int minCTAs, int maxCTAs,
+                      int directMaxBlocks, A2aPlanOut* out);
 
 // ------------------------------------------------------------ point-to-point
 // The plan of a group's ncclSend / ncclRecv calls of one comm on its per-peer

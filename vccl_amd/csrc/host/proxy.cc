@@ -408,8 +408,7 @@ void net_stop(ncclComm* c) {
 }  // namespace vccl
 
 // Bytes moved by this comm's net proxy so far (diagnostics / tests).
-extern "C" __attribute__((visibility("default"))) ncclResult_t vcclCommNetStats(
-    ncclComm_t comm, uint64_t* sent, uint64_t* received, int* connections) {
+VCCL_EXPORT ncclResult_t vcclCommNetStats(ncclComm_t comm, uint64_t* sent, uint64_t* received, int* connections) {
   if (vccl::comm_check(comm, "vcclCommNetStats") != ncclSuccess) return ncclInvalidArgument;
   const vccl::NetProxy* P = comm->net;
   if (sent) *sent = P ? P->bytesSent.load() : 0;

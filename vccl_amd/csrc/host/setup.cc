@@ -546,8 +546,6 @@ RingView ring_view(const std::vector<std::vector<int>>& rings, int ch, int rank,
 
 using namespace vccl;
 
-#define VCCL_EXPORT extern "C" __attribute__((visibility("default")))
-
 // vccl_ext.h: the ring set the library uses for nRanks ranks.
 VCCL_EXPORT ncclResult_t vcclRingOrders(int nRanks, int maxRings, int* orders, int* nRings) {
   if (nRanks < 1 || nRanks > kMaxRanks || maxRings < 1 || !orders || !nRings) return ncclInvalidArgument;
