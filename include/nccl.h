@@ -232,6 +232,26 @@ ncclResult_t  ncclCommInitRankScalable(ncclComm_t* newcomm, int nranks, int myra
     ncclUniqueId* commIds, ncclConfig_t* config);
 ncclResult_t pncclCommInitRankScalable(ncclComm_t* newcomm, int nranks, int myrank, int nId,
     ncclUniqueId* commIds, ncclConfig_t* config);
+/* nccl.h.in:208-217.  Every collective works on unregistered buffers.  On a
+ * communicator created with VCCL_REG_THRESHOLD=<bytes> set (default 0 = off),
+ * ncclCommRegister records [buff, buff + size) and makes it addressable by the
+ * communicator's other ranks; ncclCommDeregister withdraws it.  Both are local
+ * and non-collective: no rank waits for another, any number of ranks may
+ * register, in any order.  An ncclAllReduce, ncclReduceScatter or ncclAllGather
+ * of at least the threshold (all-reduce: count x size; the other two: the whole
+ * nranks-block buffer), alone or the communicator's only collective of its
+ * group, then takes the zero-copy direct path — ahead of the size-based choice
+ * of a path, at ANY size above the threshold — when its buffers lie inside live
+ * registrations on EVERY rank (all-reduce: sendbuff and recvbuff; the other
+ * two: sendbuff); otherwise the same launch runs the staged direct path (at any
+ * size, not the ring), decided on the device, identically on every rank.  The
+ * results of the two are bit-identical.  A full table (32 registrations), a
+ * host pointer or a failed export still returns ncclSuccess with a handle: the
+ * range then counts as unregistered.  A handle this communicator did not hand
+ * out is ncclInvalidArgument.  ncclCommDestroy / ncclCommAbort drop everything.
+ * Without the threshold registration does nothing and *handle = buff.  Inside a
+ * stream capture nothing new is imported: a graph uses what earlier eager calls
+ * imported (anything else falls back).  vccl_ext.h: vcclCommRegStats. */
 ncclResult_t  ncclCommRegister(const ncclComm_t comm, void* buff, size_t size, void** handle);
 ncclResult_t pncclCommRegister(const ncclComm_t comm, void* buff, size_t size, void** handle);
 ncclResult_t  ncclCommDeregister(const ncclComm_t comm, void* handle);

@@ -332,6 +332,58 @@ ncclResult_t vcclCommA2aStatsEx(ncclComm_t comm, unsigned long long* llLaunches,
                                 unsigned long long* directLaunches, unsigned long long* directPairs,
                                 unsigned long long* fifoPairs);
 ncclResult_t vcclCommSetDirectA2aThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
+/* Zero-copy direct all-reduce / reduce-scatter / all-gather over
+ * ncclCommRegister'ed buffers (opt-in: VCCL_REG_THRESHOLD=<bytes> at init,
+ * default 0 = off).
+ *   vcclRegMax       the threshold as a comm takes it (threshold < 0: from the
+ *                    environment): 0 without mapped inboxes (inbox), with
+ *                    Direct excluded by NCCL_ALGO, with a peer behind the net
+ *                    proxy, or with fewer than 2 / more than 8 ranks.
+ *   vcclRegEligible  whether a call launches the negotiating kernel: effective
+ *                    > 0, coll 0 / 1 / 2, groupCalls (the collectives of the
+ *                    call's comm in its group; 0 or 1 alone) <= 1, and at
+ *                    least `effective` bytes (all-reduce count * size, reduce-
+ *                    scatter / all-gather nRanks * count * size).
+ *   vcclRegPlan      the ordered steps of one zero-copy launch as `rank` runs
+ *                    it on nBlocks workgroups (the staged direct grid of the
+ *                    call): steps[8 k ..] = kind (0 post, 1 wait, 2 read-fold,
+ *                    3 read-copy), epoch (0 negotiate, 1 data), phase, peer,
+ *                    the peer's buffer read (0 sendbuff, 1 recvbuff), its byte
+ *                    offset, the byte offset in my recvbuff, bytes — in the
+ *                    kernel's order; every write is to the rank's own recvbuff.
+ *                    *blkElts: elements (an all-gather: bytes) of a shard one
+ *                    workgroup moves.  ncclInvalidArgument when cap < *nSteps.
+ *   vcclRegTable*    the registration table on its own (no comm, no GPU): 32
+ *                    entries; Insert hands out the lowest free entry (*entry =
+ *                    -1 when full: refused, not an error) and its generation
+ *                    (odd = live; +1 on insert, +1 on removal); Find gives the
+ *                    lowest live entry holding the whole of [addr, addr +
+ *                    bytes) and the offset in it (*entry = -1: none); Remove
+ *                    frees a live entry (ncclInvalidArgument otherwise).
+ *   vcclCommRegStats  synchronises the device, then: eligible launches, zero-
+ *                    copy outcomes, fallback outcomes (device-resident, so
+ *                    graph replays count), this rank's live registrations and
+ *                    the peers' ranges it has imported.  All 0 on a comm
+ *                    without a registry.
+ *   vcclCommSetRegThreshold  the threshold for later calls; every rank calls
+ *                    it alike, outside a group.  A comm initialised without
+ *                    VCCL_REG_THRESHOLD has no registry: *effective stays 0. */
+typedef struct vcclRegTable vcclRegTable_t;
+ncclResult_t vcclRegMax(int64_t threshold, int inbox, int directAllowed, int anyNet, int nRanks, int64_t* effective);
+ncclResult_t vcclRegEligible(int coll, size_t count, ncclDataType_t datatype, int nRanks, int64_t effective,
+                             int groupCalls, int* eligible);
+ncclResult_t vcclRegPlan(int coll, size_t count, ncclDataType_t datatype, int nRanks, int rank, int nBlocks,
+                         int64_t* blkElts, int cap, int* nSteps, int64_t* steps);
+ncclResult_t vcclRegTableNew(vcclRegTable_t** table);
+ncclResult_t vcclRegTableInsert(vcclRegTable_t* table, uint64_t addr, size_t bytes, int* entry,
+                                uint32_t* generation);
+ncclResult_t vcclRegTableFind(const vcclRegTable_t* table, uint64_t addr, size_t bytes, int* entry,
+                              uint64_t* offset, uint32_t* generation);
+ncclResult_t vcclRegTableRemove(vcclRegTable_t* table, int entry);
+ncclResult_t vcclRegTableFree(vcclRegTable_t* table);
+ncclResult_t vcclCommRegStats(ncclComm_t comm, unsigned long long* launches, unsigned long long* zeroCopy,
+                              unsigned long long* fallback, int* liveEntries, int* imported);
+ncclResult_t vcclCommSetRegThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
 /* What initialisation decides for rank `rank` of an nRanks communicator with
  * CTA bounds minCTAs / maxCTAs (a comm's defaults: 1 / 128), from the
  * environment as at init and each rank's identity pid[r], hostHash[r],

@@ -3,8 +3,10 @@
 // UBSAN=1 build knobs, makefiles/common.mk:98-109).  No GPU call is made:
 // the planner exports (vcclGroupPlanEx, vcclRingPartition, vcclRingChunkOf,
 // vcclAlgoSelection), the communicator setup (vcclCommSetup) under random
-// environments, the op encoding, error strings and the argument checks
-// that reject bad handles before any device work.  Random inputs from a fixed
+// environments, the registration table (vcclRegTable*) against a reference
+// model with the zero-copy threshold, eligibility and step lists, the op
+// encoding, error strings and the argument checks that reject bad handles
+// before any device work.  Random inputs from a fixed
 // seed; prints a summary and exits non-zero on an unexpected result (the
 // sanitizers abort on any memory or UB error).
 #include <algorithm>
@@ -490,6 +492,88 @@ int main() {
   unsetenv("VCCL_DIRECT_A2A_THRESHOLD");
   EXPECT(vcclCommA2aStatsEx(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == ncclInvalidArgument);
   EXPECT(vcclCommSetDirectA2aThreshold(nullptr, 4096, nullptr) == ncclInvalidArgument);
+  // the registration table (vcclRegTable*) against a reference model under
+  // random inserts, lookups and removals, with invalid entries and handles;
+  // the zero-copy threshold, eligibility and step lists on random arguments
+  long regOps = 0;
+  {
+    struct Model {
+      bool live;
+      uint64_t addr, bytes;
+      uint32_t gen;
+    };
+    Model m[32] = {};
+    vcclRegTable_t* t = nullptr;
+    EXPECT(vcclRegTableNew(&t) == ncclSuccess && t != nullptr);
+    EXPECT(vcclRegTableNew(nullptr) == ncclInvalidArgument);
+    for (int trial = 0; trial < 40000; trial++) {
+      const uint64_t addr = rng() % 64 == 0 ? ~(uint64_t)0 - rng() % 8 : 4096 + rng() % 8192;
+      const size_t bytes = (size_t)pick({0, 1, 2, 100, 4096});
+      const int op = (int)(rng() % 4);
+      if (op == 0) {
+        int e = -7;
+        uint32_t g = 77;
+        EXPECT(vcclRegTableInsert(t, addr, bytes, &e, rng() % 8 ? &g : nullptr) == ncclSuccess);
+        int want = -1;
+        if (bytes > 0 && addr + bytes >= addr)
+          for (int i = 0; i < 32 && want < 0; i++)
+            if (!m[i].live) want = i;
+        EXPECT(e == want);
+        if (e >= 0 && e < 32) m[e] = Model{true, addr, bytes, m[e].gen + 1};
+        if (e >= 0 && g != 77) EXPECT(g == m[e].gen && (g & 1u));
+      } else if (op == 1) {
+        const int e = (int)(rng() % 40) - 4;
+        const bool ok = e >= 0 && e < 32 && m[e].live;
+        EXPECT(vcclRegTableRemove(t, e) == (ok ? ncclSuccess : ncclInvalidArgument));
+        if (ok) m[e].live = false, m[e].gen++;
+      } else {
+        int e = -7;
+        uint64_t off = 99;
+        uint32_t g = 77;
+        EXPECT(vcclRegTableFind(t, addr, bytes, &e, &off, &g) == ncclSuccess);
+        int want = -1;
+        for (int i = 0; i < 32 && want < 0; i++)
+          if (m[i].live && addr + bytes >= addr && addr >= m[i].addr && addr < m[i].addr + m[i].bytes &&
+              addr + bytes <= m[i].addr + m[i].bytes)
+            want = i;
+        EXPECT(e == want);
+        if (e >= 0 && e < 32) EXPECT(off == addr - m[e].addr && g == m[e].gen);
+      }
+      regOps++;
+    }
+    EXPECT(vcclRegTableInsert(t, 1, 1, nullptr, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclRegTableFind(nullptr, 1, 1, nullptr, nullptr, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclRegTableRemove(nullptr, 0) == ncclInvalidArgument);
+    EXPECT(vcclRegTableFree(t) == ncclSuccess && vcclRegTableFree(nullptr) == ncclSuccess);
+    for (int trial = 0; trial < 20000; trial++) {
+      const int n = (int)pick({0, 1, 2, 3, 4, 8, 9}), rank = (int)(rng() % (n + 1)) - (rng() % 32 == 0);
+      const int coll = (int)(rng() % 6), dt = rng() % 16 ? dts[rng() % 10] : 12;
+      const size_t count = (size_t)pick({0, 1, 7, 4095, 4096, 4097, 1000003}) + rng() % 3;
+      int64_t eff = -7;
+      const ncclResult_t r0 = vcclRegMax(pick({-1, 0, 1, 32768, 1ll << 40}), (int)(rng() % 2), (int)(rng() % 2),
+                                         (int)(rng() % 2), n, rng() % 16 ? &eff : nullptr);
+      EXPECT(r0 == ncclSuccess || r0 == ncclInvalidArgument);
+      if (r0 == ncclSuccess) EXPECT(eff >= 0 && (eff == 0 || (n >= 2 && n <= 8)));
+      int el = -7;
+      const ncclResult_t r1 = vcclRegEligible(coll, count, (ncclDataType_t)dt, n, pick({-1, 0, 1, 32768}),
+                                              (int)pick({-1, 0, 1, 2, 40}), &el);
+      EXPECT(r1 == ncclSuccess || r1 == ncclInvalidArgument);
+      if (r1 == ncclSuccess) EXPECT((el == 0 || el == 1) && (coll <= 2 || el == 0));
+      const int nb = (int)pick({0, 1, 5, 16, 128, 129}), cap = (int)pick({0, 8, 80});
+      std::vector<int64_t> steps(8 * (size_t)cap + 8, -1);
+      int ns = -7;
+      int64_t blk = -7;
+      const ncclResult_t r2 = vcclRegPlan(coll, count, (ncclDataType_t)dt, n, rank, nb, rng() % 8 ? &blk : nullptr, cap,
+                                          &ns, steps.data());
+      EXPECT(r2 == ncclSuccess || r2 == ncclInvalidArgument);
+      if (r2 == ncclSuccess) EXPECT(ns > 0 && ns <= cap && (blk == -7 || blk > 0));
+      EXPECT(steps[8 * (size_t)cap] == -1);
+      regOps++;
+    }
+    EXPECT(vcclCommRegStats(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclCommSetRegThreshold(nullptr, 4096, nullptr) == ncclInvalidArgument);
+  }
+  printf("host_api_check: %ld registration table operations, thresholds and zero-copy plans\n", regOps);
   printf("host_api_check: %ld all-to-all limits and plans\n", a2a);
   printf("host_api_check: %ld direct all-to-all limits and plans\n", directA2a);
   printf("host_api_check: %ld rooted selections and layouts\n", rooted);

@@ -204,6 +204,51 @@ struct DirectA2aWork {
 };
 static_assert(sizeof(DirectA2aWork) <= 4096, "DirectA2aWork must fit the kernel-argument budget");
 
+// Zero-copy direct collectives over registered buffers (direct_reg.hpp,
+// DESIGN.md §4.14): the import table, the descriptor that travels in a flag
+// line, and the launch's work.
+constexpr int kRegTableEntries = 32;       // host/reg.h kRegMaxEntries
+constexpr uint32_t kRegNone = 0xffffffffu;
+
+// The import table: peer p's registered ranges as THIS process addresses them
+// (host/regcomm.cc).  It lives in host-pinned mapped memory: the host updates
+// it with plain stores while no launch of the comm is in flight, so an enqueue
+// never puts a copy on a stream (which could queue behind the spinning kernel
+// of another comm of the same process, ncclCommInitAll).  The three counters
+// (bumped by workgroup 0) are device-resident.
+struct RegPeerEntry {
+  char* base;            // nullptr: not imported
+  uint64_t size;
+  uint32_t generation;
+  uint32_t pad;
+};
+struct RegPeers {
+  RegPeerEntry e[kDirectMaxRanks][kRegTableEntries];
+};
+struct RegStats {
+  unsigned long long launches, zeroCopy, fallback;
+};
+
+// What travels in a phase-0 flag line behind the 4-byte epoch.
+struct RegDesc {
+  uint64_t sendOff, recvOff;
+  uint64_t sendBytes, recvBytes;
+  uint32_t sendEntry, sendGen;   // kRegNone: not registered
+  uint32_t recvEntry, recvGen;
+};
+static_assert(sizeof(RegDesc) + 8 <= kDirectFlagStride, "the descriptor rides in the flag's line");
+
+struct DirectRegWork {
+  DirectWork w;          // the staged geometry (the fallback runs it as it is)
+  const RegPeers* reg;   // host-pinned, mapped
+  RegStats* stats;       // device-resident
+  RegDesc mine;
+  int64_t zcBlkElts;     // host/plan.cc reg_plan on w.nBlocks
+  int needRecv;          // all-reduce: peers read my recvbuff too
+  int pad;
+};
+static_assert(sizeof(DirectRegWork) <= 4096, "DirectRegWork must fit the kernel-argument budget");
+
 __host__ __device__ inline DirectPart direct_part_of(const DirectWork& w) {
   return DirectPart{w.sendbuff, w.recvbuff, w.count, w.nChunks, w.root, w.chunkElts, w.blkElts, w.cbd,
                     w.arChunk};

@@ -96,6 +96,29 @@
 //                    non-roots included, although they wait for no data.
 // In the LL protocol the job of the closing round needed the arrival token of
 // the rooted LL kernels (ll.hpp); here the closing flag round does it.
+//    zero-copy      (direct_reg.hpp, a launch of its own over registered
+//    AR / RS / AG    buffers) spends one position on a negotiation — flags
+//                    only, a descriptor riding in the flag's own line: post (0),
+//                    wait (0) on every peer, post (1) (R1), wait (1) (R2) — and
+//                    then EITHER one position that touches no region at all
+//                    (it pulls from the peers' user buffers): post (0), wait
+//                    (0), post (1) after it (R1), wait (1) closing it (R2); OR,
+//                    when any rank said no, the staged part of the same
+//                    collective unchanged, which obeys R1 / R2 by the lines
+//                    above.  Both epochs raise every (phase, writer, block)
+//                    flag of parity 0 once, as any chunk does, so the chains
+//                    of the proof hold with "region" read as "nothing": a peer
+//                    one position ahead writes only (0, *) regions, after it
+//                    left the negotiation (R2), which it could only do after
+//                    this rank's phase-1 flag — raised after this rank's last
+//                    read of a (0, *) region of the previous call.  The
+//                    verdict is the AND of the same n bits in every workgroup
+//                    of every rank, so every rank consumes the same number of
+//                    positions per launch: 2 (zero-copy) or 1 + the staged
+//                    count (fallback), and the epoch sequence stays common.
+//                    A flag line's payload words are rewritten by their
+//                    writer's next negotiation only after the reader's
+//                    phase-1 flag of this one (R2), raised after it read them.
 #pragma once
 #include "coll_types.hpp"
 #include "ll.hpp"

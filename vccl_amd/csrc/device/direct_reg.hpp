@@ -1,0 +1,308 @@
+// Zero-copy direct all-reduce / reduce-scatter / all-gather over
+// ncclCommRegister'ed buffers (opt-in, VCCL_REG_THRESHOLD).
+//
+// Reference role: the reference's registered-buffer collectives
+// (src/register/coll_reg.cc: with every rank's user buffer registered a
+// kernel addresses the peers' buffers directly and the staging copies
+// disappear).  Here: the direct kernels of direct.hpp without their inbox.
+// A rank cannot know whether its peers passed registered buffers, so every
+// rank launches this kernel for every eligible call (host/plan.cc
+// reg_eligible) and the kernel settles the rest, on the direct grid, flags
+// and epochs (workgroup b talks only to its namesakes):
+//
+//   epoch k (negotiate)
+//     post (0, me, b) at every peer, my descriptor in the flag's 64-byte line
+//          (written by the lane that raises the flag, drained before the flag
+//          store: the inbox's payload-then-flag hand-off) — {entry,
+//          generation, offset, bytes} of sendbuff in my registration table,
+//          the all-reduce adds the same for recvbuff; an unregistered buffer
+//          sends entry kRegNone.  An ordinary phase-0 flag: "my input is ready";
+//     wait (0, *, b); ok_me = my own buffers are registered, and for every
+//          peer: its descriptor names an entry my import table (RegPeers)
+//          holds at the same generation, and offset + bytes lies inside it;
+//     post (1, me, b) carrying ok_me;  wait (1, *, b);
+//     D = AND of the n verdicts — the same in every workgroup of every rank.
+//   D = 0: the staged direct path exactly — direct_*_part (direct.hpp) on the
+//     geometry the DirectWork carries, from epoch k + 1 on.
+//   D = 1, epoch k + 1: no inbox, one "chunk"; every rank PULLS (sc0 sc1 loads
+//     from the peers' buffers) and stores into its own recvbuff only — nothing
+//     here writes a peer's memory but flags.  The step list is host/plan.cc
+//     reg_plan's, kept side by side with this order:
+//       reduce-scatter  fold block b of shard `me` from the n inputs in the
+//                       staged kernel's order (cbd_channel_of + rsOrder);
+//                       post (0) "I have finished reading you"; wait (0);
+//                       post (1); wait (1);
+//       all-gather      copy block b of every rank's input into recvbuff (my
+//                       own only when out of place); the same two rounds;
+//       all-reduce      fold block b of shard `me` (direct_shard_elts of the
+//                       whole count) from the n inputs, every element in the
+//                       ring order its ar_chunk_of lookup gives (as
+//                       direct_allreduce_part), write-through into my
+//                       recvbuff; post (0) "shard `me` of my recvbuff is
+//                       final, and I have finished reading your inputs";
+//                       wait (0); pull block b of every other shard o from
+//                       o's RECVBUFF; post (1) "finished reading your
+//                       recvbuff"; wait (1).
+//       In place is safe: shard o of any input is read only by o, and a rank
+//       overwrites foreign shards of its buffer only after every peer's (0).
+// Epoch positions per launch: 2 (zero-copy) or 1 + the staged count
+// (fallback), the same on every rank since D is; R1 / R2 of direct.hpp hold in
+// both epochs (the proof sits next to the rule in direct.hpp's header).
+#pragma once
+#include "direct.hpp"
+
+namespace vccl {
+
+// The pointers the negotiation resolved, rank-indexed (LDS).
+struct RegResolved {
+  const char* send[kDirectMaxRanks];
+  const char* recv[kDirectMaxRanks];
+  int ok[kDirectMaxRanks];
+};
+
+__device__ __forceinline__ void reg_st64(char* line, int off, uint64_t v) {
+  __hip_atomic_store((uint64_t*)(line + off), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__device__ __forceinline__ void reg_st32(char* line, int off, uint32_t v) {
+  __hip_atomic_store((uint32_t*)(line + off), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__device__ __forceinline__ uint64_t reg_ld64(const char* line, int off) {
+  return __hip_atomic_load((const uint64_t*)(line + off), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__device__ __forceinline__ uint32_t reg_ld32(const char* line, int off) {
+  return __hip_atomic_load((const uint32_t*)(line + off), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// direct_post with a payload in the line: lane k of wave 0 writes the words
+// into flag line (phase, 0, me, b) at peer (me + k) mod n, drains, then raises
+// the flag.  Layout: +0 epoch, +4 verdict (phase 1), +8 the RegDesc (phase 0).
+__device__ __forceinline__ void reg_post(const DirectWork& w, const DirectPeers& P, int phase, int b, uint32_t e,
+                                         const RegDesc* d, uint32_t verdict) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  const int k = threadIdx.x;
+  if (k >= 1 && k < w.nRanks) {
+    const int p = w.rank + k < w.nRanks ? w.rank + k : w.rank + k - w.nRanks;
+    char* line = P.flags[p] + direct_flag_off(phase, 0, w.rank, b);
+    if (d) {
+      reg_st64(line, 8, d->sendOff);
+      reg_st64(line, 16, d->recvOff);
+      reg_st64(line, 24, d->sendBytes);
+      reg_st64(line, 32, d->recvBytes);
+      reg_st32(line, 40, d->sendEntry);
+      reg_st32(line, 44, d->sendGen);
+      reg_st32(line, 48, d->recvEntry);
+      reg_st32(line, 52, d->recvGen);
+    } else {
+      reg_st32(line, 4, verdict);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // payload, then flag
+    if (w.comm->useFences) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    __hip_atomic_store((uint32_t*)line, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// One registered range of peer t as the descriptor names it, checked against
+// my import table: the pointer, or nullptr.  `need`: the bytes I will read.
+__device__ __forceinline__ const char* reg_resolve(const RegPeers* reg, int t, uint32_t entry, uint32_t gen,
+                                                   uint64_t off, uint64_t bytes, uint64_t need) {
+  if (entry >= (uint32_t)kRegTableEntries) return nullptr;
+  const RegPeerEntry& pe = reg->e[t][entry];
+  if (!pe.base || pe.generation != gen) return nullptr;
+  const uint64_t len = bytes > need ? bytes : need;
+  if (off > pe.size || len > pe.size - off) return nullptr;
+  return pe.base + off;
+}
+
+// Epoch k.  Returns D; fills `rs` with every peer's pointers when D = 1.
+__device__ __forceinline__ bool reg_negotiate(const DirectRegWork& rw, uint32_t e, RegResolved* rs, int* shFail) {
+  const DirectWork& w = rw.w;
+  const DirectPeers& P = *w.peers;
+  const int n = w.nRanks, me = w.rank, b = blockIdx.x, t = threadIdx.x;
+  const char* myFlags = P.flags[me];
+  reg_post(w, P, 0, b, e, &rw.mine, 0);
+  const bool live = direct_wait(w, myFlags, 0, 0, b, e, shFail);
+  if (t < n) {
+    int ok = 0;
+    const char* s = nullptr;
+    const char* r = nullptr;
+    if (t == me) {
+      ok = rw.mine.sendEntry != kRegNone && (!rw.needRecv || rw.mine.recvEntry != kRegNone);
+    } else if (live) {
+      const char* line = myFlags + direct_flag_off(0, 0, t, b);
+      s = reg_resolve(rw.reg, t, reg_ld32(line, 40), reg_ld32(line, 44), reg_ld64(line, 8), reg_ld64(line, 24),
+                      rw.mine.sendBytes);
+      ok = s != nullptr;
+      if (rw.needRecv) {
+        r = reg_resolve(rw.reg, t, reg_ld32(line, 48), reg_ld32(line, 52), reg_ld64(line, 16), reg_ld64(line, 32),
+                        rw.mine.recvBytes);
+        ok = ok && r != nullptr;
+      }
+    }
+    rs->send[t] = s;
+    rs->recv[t] = r;
+    rs->ok[t] = ok;
+  }
+  __syncthreads();
+  uint32_t okMe = 1;
+  for (int q = 0; q < n; q++) okMe &= (uint32_t)rs->ok[q];
+  reg_post(w, P, 1, b, e, nullptr, okMe);
+  bool D = direct_wait(w, myFlags, 1, 0, b, e, shFail) && okMe;
+  if (D)
+    for (int q = 0; q < n; q++)
+      if (q != me) D = D && reg_ld32(myFlags + direct_flag_off(1, 0, q, b), 4) != 0;
+  __syncthreads();  // the verdict reads precede any later post
+  return D;
+}
+
+// The two closing rounds of the one-hop zero-copy kernels.
+__device__ __forceinline__ void reg_close(const DirectWork& w, const DirectPeers& P, int b, uint32_t e, int* shFail) {
+  direct_post(w, P, 0, 0, b, e);
+  (void)direct_wait(w, P.flags[w.rank], 0, 0, b, e, shFail);
+  direct_post(w, P, 1, 0, b, e);
+  (void)direct_wait(w, P.flags[w.rank], 1, 0, b, e, shFail);
+}
+
+template <class Fn>
+__device__ __forceinline__ void reg_reducescatter_zc(const DirectRegWork& rw, const RegResolved& rs, uint32_t e,
+                                                     int* shFail) {
+  using T = typename Fn::EltType;
+  constexpr int64_t esz = (int64_t)sizeof(T);
+  const DirectWork& w = rw.w;
+  const Fn fn(load_op_arg(w.redArgPtr, w.redArgBytes, w.redArg));
+  const int n = w.nRanks, me = w.rank, b = blockIdx.x;
+  const int64_t count = (int64_t)w.count;
+  const int64_t lo = (int64_t)b * rw.zcBlkElts < count ? (int64_t)b * rw.zcBlkElts : count;
+  const int64_t hi = lo + rw.zcBlkElts < count ? lo + rw.zcBlkElts : count;
+  char* out = (char*)w.recvbuff;
+  for (int64_t cur = lo; cur < hi;) {
+    int64_t end;
+    const int ch = cbd_channel_of(w.cbd, cur, &end);
+    end = end < hi ? end : hi;
+    const int8_t* order = w.comm->rsOrder[ch % w.comm->nRings];
+    const char* s[kDirectMaxRanks];
+    char* d[kDirectMaxRanks] = {out + cur * esz};
+#pragma unroll
+    for (int j = 0; j < kDirectMaxRanks; j++) {
+      const int q = j < n ? order[j] : me;
+      s[j] = (q == me ? (const char*)w.sendbuff : rs.send[q]) + ((int64_t)me * count + cur) * esz;
+    }
+    direct_rc<Fn, kDirectUnroll, kSys, kSys, kSys>(fn, s, n, w.preOp ? n : 0, true, d, 1, end - cur, threadIdx.x,
+                                                   blockDim.x);
+    cur = end;
+  }
+  reg_close(w, *w.peers, b, e, shFail);
+}
+
+__device__ __forceinline__ void reg_allgather_zc(const DirectRegWork& rw, const RegResolved& rs, uint32_t e,
+                                                 int* shFail) {
+  using Fn = FnCopy<uint8_t>;
+  const Fn fn(0);
+  const DirectWork& w = rw.w;
+  const int n = w.nRanks, me = w.rank, b = blockIdx.x;
+  const int64_t count = (int64_t)w.count;
+  const int64_t lo = (int64_t)b * rw.zcBlkElts < count ? (int64_t)b * rw.zcBlkElts : count;
+  const int64_t hi = lo + rw.zcBlkElts < count ? lo + rw.zcBlkElts : count;
+  char* out = (char*)w.recvbuff;
+  for (int k = 0; k < n; k++) {
+    const int o = me + k < n ? me + k : me + k - n;
+    const char* s[kDirectMaxRanks] = {(o == me ? (const char*)w.sendbuff : rs.send[o]) + lo};
+    char* d[kDirectMaxRanks] = {out + (int64_t)o * count + lo};
+    if (o == me && s[0] == d[0]) continue;  // in place: my block is already there
+    direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, hi - lo, threadIdx.x, blockDim.x);
+  }
+  reg_close(w, *w.peers, b, e, shFail);
+}
+
+template <class Fn>
+__device__ __forceinline__ void reg_allreduce_zc(const DirectRegWork& rw, const RegResolved& rs, uint32_t e,
+                                                 int* shFail) {
+  using T = typename Fn::EltType;
+  constexpr int64_t esz = (int64_t)sizeof(T);
+  const DirectWork& w = rw.w;
+  const DirectPeers& P = *w.peers;
+  const Fn fn(load_op_arg(w.redArgPtr, w.redArgBytes, w.redArg));
+  const int n = w.nRanks, me = w.rank, b = blockIdx.x;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int64_t eltAlign = 16 / sizeof(T) ? 16 / sizeof(T) : 1;
+  const int64_t count = (int64_t)w.count;
+  const int64_t shardElts = direct_shard_elts(count, n, eltAlign);
+  auto block_of = [&](int o, int64_t* off, int64_t* len) {  // block b of shard o
+    int64_t shardEnd = (int64_t)(o + 1) * shardElts;
+    shardEnd = shardEnd < count ? shardEnd : count;
+    const int64_t lo = (int64_t)o * shardElts + (int64_t)b * rw.zcBlkElts;
+    const int64_t hi = lo + rw.zcBlkElts < shardEnd ? lo + rw.zcBlkElts : shardEnd;
+    *off = lo;
+    *len = hi > lo ? hi - lo : 0;
+  };
+  char* out = (char*)w.recvbuff;
+  {
+    // The fold of my block: direct_allreduce_part's walk — each wave a span of
+    // whole 16-byte packs, ring chunk by ring chunk — on the peers' inputs.
+    int64_t off, len;
+    block_of(me, &off, &len);
+    const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), nw = nt >> 6;
+    const int64_t span = ((len + eltAlign - 1) / eltAlign + nw - 1) / nw * eltAlign;
+    int64_t cur = (int64_t)wv * span < len ? (int64_t)wv * span : len;
+    const int64_t wend = cur + span < len ? cur + span : len;
+    while (cur < wend) {
+      int k;
+      int64_t segEnd;
+      const int ch = ar_chunk_of(w.cbd, w.arChunk, n, eltAlign, off + cur, &k, &segEnd);
+      segEnd -= off;
+      const int64_t end = segEnd < wend ? segEnd : wend;
+      const int8_t* R = w.comm->ringAt[ch % w.comm->nRings];
+      const char* s[kDirectMaxRanks];
+      char* d[kDirectMaxRanks] = {out + (off + cur) * esz};
+#pragma unroll
+      for (int j = 0; j < kDirectMaxRanks; j++) {
+        int pos = k + 1 + j;
+        pos = pos >= n ? pos - n : pos;
+        pos = pos >= n ? pos - n : pos;
+        const int q = j < n ? __builtin_amdgcn_readfirstlane(R[pos]) : me;
+        s[j] = (q == me ? (const char*)w.sendbuff : rs.send[q]) + (off + cur) * esz;
+      }
+      direct_rc<Fn, kDirectUnroll, kSys, kSys, kSys>(fn, s, n, w.preOp ? n : 0, true, d, 1, end - cur, lane, 64);
+      cur = end;
+    }
+  }
+  direct_post(w, P, 0, 0, b, e);
+  if (direct_wait(w, P.flags[me], 0, 0, b, e, shFail)) {
+    for (int k = 1; k < n; k++) {
+      const int o = me + k < n ? me + k : me + k - n;
+      int64_t off, len;
+      block_of(o, &off, &len);
+      const char* s[kDirectMaxRanks] = {rs.recv[o] + off * esz};
+      char* d[kDirectMaxRanks] = {out + off * esz};
+      direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+    }
+  }
+  direct_post(w, P, 1, 0, b, e);
+  (void)direct_wait(w, P.flags[me], 1, 0, b, e, shFail);
+}
+
+// One launch: negotiate, then `zc` (zero-copy, one epoch) or `staged` (the
+// direct_*_part of the collective).  The counters are workgroup 0's.
+template <class ZC, class Staged>
+__device__ __forceinline__ void direct_reg_run(const DirectRegWork& rw, ZC zc, Staged staged) {
+  __shared__ int shFail;
+  __shared__ RegResolved rs;
+  const DirectWork& w = rw.w;
+  uint32_t e = epoch_after(__hip_atomic_load(&w.comm->dEpoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  if (threadIdx.x == 0) shFail = 0;
+  __syncthreads();
+  const bool D = reg_negotiate(rw, e, &rs, &shFail);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    atomicAdd(&rw.stats->launches, 1ull);
+    atomicAdd(D ? &rw.stats->zeroCopy : &rw.stats->fallback, 1ull);
+  }
+  if (D) {
+    e = epoch_after(e);
+    zc(rw, rs, e, &shFail);
+  } else {
+    staged(w, e, shFail);
+  }
+  epoch_retire(&w.comm->dEpoch, &w.comm->dDone, e);
+}
+
+}  // namespace vccl

@@ -1,0 +1,76 @@
+// Zero-copy direct kernels over registered buffers (direct_reg.hpp) for ONE
+// kernel element type (VCCL_KT) and ONE half (VCCL_REG_PART: 0 the all-reduce,
+// 1 the reduce-scatter and, in the K_U8 unit, the byte-copy all-gather) —
+// separate objects, built in parallel with the collective kernels of
+// ring_kernels.hip.  One call per launch; the staged part of the same
+// collective is the fallback the negotiation may pick.
+#include <hip/hip_runtime.h>
+
+#include "direct_reg.hpp"
+#include "dispatch.hpp"
+#include "ring_launch.hpp"
+
+#ifndef VCCL_KT
+#error "compile with -DVCCL_KT=<kernel element type>"
+#endif
+#ifndef VCCL_REG_PART
+#error "compile with -DVCCL_REG_PART=<0 all-reduce | 1 reduce-scatter / all-gather>"
+#endif
+
+namespace vccl {
+
+#if VCCL_REG_PART == 0
+template <class Fn>
+__global__ __launch_bounds__(kDirectThreads) void k_direct_reg_allreduce(DirectRegWork rw) {
+  direct_reg_run(
+      rw, [](const DirectRegWork& r, const RegResolved& rs, uint32_t e, int* f) { reg_allreduce_zc<Fn>(r, rs, e, f); },
+      [](const DirectWork& w, uint32_t& e, int& f) { direct_allreduce_part<Fn>(w, e, f); });
+}
+
+template <>
+hipError_t direct_reg_launch_ar<VCCL_KT>(int devOp, const DirectRegWork& rw, hipStream_t stream, hipEvent_t stop) {
+  using T = typename KTypeOf<VCCL_KT>::T;
+  const dim3 grid(rw.w.nBlocks), block(kDirectThreads);
+  hipError_t err = hipErrorInvalidValue;
+  dispatch_op<T>(devOp, [&]<class Fn>() {
+    if constexpr (!std::is_same<Fn, FnCopy<T>>::value)
+      err = launch_k(k_direct_reg_allreduce<Fn>, grid, block, stream, stop, rw);
+  });
+  return err;
+}
+
+#else
+template <class Fn>
+__global__ __launch_bounds__(kDirectThreads) void k_direct_reg_reducescatter(DirectRegWork rw) {
+  direct_reg_run(
+      rw,
+      [](const DirectRegWork& r, const RegResolved& rs, uint32_t e, int* f) { reg_reducescatter_zc<Fn>(r, rs, e, f); },
+      [](const DirectWork& w, uint32_t& e, int& f) { direct_reducescatter_part<Fn>(w, e, f); });
+}
+template <int K>  // the K_U8 unit only
+__global__ __launch_bounds__(kDirectThreads) void k_direct_reg_allgather(DirectRegWork rw) {
+  direct_reg_run(
+      rw, [](const DirectRegWork& r, const RegResolved& rs, uint32_t e, int* f) { reg_allgather_zc(r, rs, e, f); },
+      [](const DirectWork& w, uint32_t& e, int& f) { direct_allgather_part(w, e, f); });
+}
+
+template <>
+hipError_t direct_reg_launch_rsag<VCCL_KT>(int coll, int devOp, const DirectRegWork& rw, hipStream_t stream,
+                                           hipEvent_t stop) {
+  using T = typename KTypeOf<VCCL_KT>::T;
+  const dim3 grid(rw.w.nBlocks), block(kDirectThreads);
+  if (coll == kCollAllGather) {
+    if constexpr (VCCL_KT == K_U8) return launch_k(k_direct_reg_allgather<K_U8>, grid, block, stream, stop, rw);
+    return hipErrorInvalidValue;
+  }
+  hipError_t err = hipErrorInvalidValue;
+  if (coll != kCollReduceScatter) return err;
+  dispatch_op<T>(devOp, [&]<class Fn>() {
+    if constexpr (!std::is_same<Fn, FnCopy<T>>::value)
+      err = launch_k(k_direct_reg_reducescatter<Fn>, grid, block, stream, stop, rw);
+  });
+  return err;
+}
+#endif
+
+}  // namespace vccl

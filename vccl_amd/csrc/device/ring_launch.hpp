@@ -67,6 +67,23 @@ hipError_t ll_a2a_launch(const LLA2aWork& w, int grid, hipStream_t stream, hipEv
 template <int K>
 hipError_t direct_launch(int coll, int devOp, const DirectBatch& b, hipStream_t stream, hipEvent_t stop);
 
+// Zero-copy direct all-reduce / reduce-scatter / all-gather over registered
+// buffers, with the staged kernel of the same collective as its in-kernel
+// fallback (direct_reg.hpp): one call per launch, rw.w.nBlocks workgroups.
+// Built apart from the direct kernels, the all-reduce in an object of its own
+// (direct_reg_kernels.hip, VCCL_REG_PART 0 / 1): each kernel carries its
+// staged fallback, and the fp8 units are the build's longest compiles.
+template <int K>
+hipError_t direct_reg_launch_ar(int devOp, const DirectRegWork& rw, hipStream_t stream, hipEvent_t stop);
+template <int K>
+hipError_t direct_reg_launch_rsag(int coll, int devOp, const DirectRegWork& rw, hipStream_t stream, hipEvent_t stop);
+template <int K>
+inline hipError_t direct_reg_launch(int coll, int devOp, const DirectRegWork& rw, hipStream_t stream,
+                                    hipEvent_t stop) {
+  return coll == kCollAllReduce ? direct_reg_launch_ar<K>(devOp, rw, stream, stop)
+                                : direct_reg_launch_rsag<K>(coll, devOp, rw, stream, stop);
+}
+
 // One-hop direct all-to-all(v) (direct.hpp direct_alltoall): a byte copy,
 // built once in the K_U8 unit; w.nBlocks workgroups of kDirectThreads threads.
 hipError_t direct_a2a_launch(const DirectA2aWork& w, hipStream_t stream, hipEvent_t stop);

@@ -19,6 +19,7 @@
 
 namespace vccl {
 struct DirectPeers;  // direct.hpp
+struct RegComm;      // regcomm.h
 }
 
 namespace vccl {
@@ -95,6 +96,10 @@ struct PeerMap {               // what one rank published about itself
     hipIpcMemHandle_t handle;  // for peers in other processes
     char* ptr;                 // raw pointer (valid only in the owner process)
   } buf[kMapCount];
+  // VCCL_REG_THRESHOLD: the name of this rank's buffer registry in shared
+  // memory and whether it exists (regcomm.h); ANDed over the ranks at init
+  char regShm[48];
+  int regOk;
 };
 
 struct UserRedOp {             // ncclRedOpCreatePreMulSum state (enqueue.cc:2528-2567)
@@ -135,6 +140,9 @@ struct ncclComm : vccl::CommSetup {
   char* p2pBuf = nullptr;
   char* p2pFlags = nullptr;
   vccl::P2pConn* p2pConns = nullptr;
+  // ncclCommRegister'ed buffers and the peers' imported ones (regcomm.h);
+  // null unless VCCL_REG_THRESHOLD took effect at init
+  vccl::RegComm* reg = nullptr;
   vccl::NetProxy* net = nullptr;  // inter-node ring connections (proxy.cc)
   int netListenFd = -1;        // proxy listener, open from init until connections are made
   vccl::DevComm* devComm = nullptr;

@@ -10,6 +10,7 @@
 #include "../device/coll_types.hpp"
 #include "../device/dispatch.hpp"
 #include "launch.h"
+#include "regcomm.h"
 
 namespace vccl {
 
@@ -420,6 +421,113 @@ VCCL_EXPORT ncclResult_t vcclCommSetDirectA2aThreshold(ncclComm_t comm, int64_t 
   comm->directA2aMaxBytes = direct_a2a_max_of(*comm, bytes, comm->nRanks, comm->p2pOff == kP2pOffNet,
                                               comm->p2pConns != nullptr && comm->dPeers != nullptr);
   if (effective) *effective = (int64_t)comm->directA2aMaxBytes;
+  return ncclSuccess;
+}
+
+// -------------------------------------------------------- registered buffers
+// A comm's VCCL_REG_THRESHOLD as it takes effect (the registry bit of the init
+// all-gather aside: this is the arithmetic).
+VCCL_EXPORT ncclResult_t vcclRegMax(int64_t threshold, int inbox, int directAllowed, int anyNet, int nRanks,
+                                    int64_t* effective) {
+  if (!effective || nRanks < 1) return ncclInvalidArgument;
+  if (threshold < 0) threshold = param_int("REG_THRESHOLD", 0);
+  *effective = (int64_t)reg_max(threshold, inbox != 0, directAllowed != 0, anyNet != 0, nRanks);
+  return ncclSuccess;
+}
+
+VCCL_EXPORT ncclResult_t vcclRegEligible(int coll, size_t count, ncclDataType_t datatype, int nRanks,
+                                         int64_t effective, int groupCalls, int* eligible) {
+  if (!eligible || coll < kAllReduce || coll > kReduce || type_size(datatype) < 1 || nRanks < 1 || effective < 0 ||
+      groupCalls < 0 || count > (size_t)1 << 56)
+    return ncclInvalidArgument;
+  *eligible = reg_eligible(coll, (int64_t)count, type_size(datatype), nRanks, (uint64_t)effective, groupCalls);
+  return ncclSuccess;
+}
+
+// The ordered steps of one zero-copy launch as `rank` runs it on nBlocks workgroups.
+VCCL_EXPORT ncclResult_t vcclRegPlan(int coll, size_t count, ncclDataType_t datatype, int nRanks, int rank,
+                                     int nBlocks, int64_t* blkElts, int cap, int* nSteps, int64_t* steps) {
+  if ((coll != kAllReduce && coll != kReduceScatter && coll != kAllGather) || nRanks < 2 ||
+      nRanks > kDirectMaxRanks || rank < 0 || rank >= nRanks || type_size(datatype) < 1 || count == 0 ||
+      count > (size_t)1 << 56 || nBlocks < 1 || nBlocks > kDirectMaxBlocks || !nSteps || cap < 0 || (cap && !steps))
+    return ncclInvalidArgument;
+  const CallSize sz = call_size(coll, count, datatype);
+  RegPlanOut out;
+  NCCLCHECK(reg_plan(coll, nRanks, rank, sz.count, sz.eltSize, nBlocks, &out));
+  if (blkElts) *blkElts = out.blkElts;
+  *nSteps = (int)out.steps.size();
+  if (*nSteps > cap) return ncclInvalidArgument;
+  for (size_t k = 0; k < out.steps.size(); k++) {
+    const RegStep& d = out.steps[k];
+    const int64_t v[8] = {d.kind, d.epoch, d.phase, d.peer, d.buf, d.peerOff, d.ownOff, d.bytes};
+    for (int j = 0; j < 8; j++) steps[8 * k + j] = v[j];
+  }
+  return ncclSuccess;
+}
+
+// The pure registration table on its own: no comm, no GPU.
+struct vcclRegTable {
+  RegTable t;
+};
+VCCL_EXPORT ncclResult_t vcclRegTableNew(vcclRegTable_t** table) {
+  if (!table) return ncclInvalidArgument;
+  *table = new vcclRegTable();
+  reg_table_clear(&(*table)->t);
+  return ncclSuccess;
+}
+VCCL_EXPORT ncclResult_t vcclRegTableInsert(vcclRegTable_t* table, uint64_t addr, size_t bytes, int* entry,
+                                            uint32_t* generation) {
+  if (!table || !entry) return ncclInvalidArgument;
+  *entry = reg_insert(&table->t, addr, bytes);  // -1: full (or an empty range) — refused, not an error
+  if (generation) *generation = *entry < 0 ? 0 : table->t.e[*entry].generation;
+  return ncclSuccess;
+}
+VCCL_EXPORT ncclResult_t vcclRegTableFind(const vcclRegTable_t* table, uint64_t addr, size_t bytes, int* entry,
+                                          uint64_t* offset, uint32_t* generation) {
+  if (!table || !entry) return ncclInvalidArgument;
+  uint64_t off = 0;
+  *entry = reg_find(&table->t, addr, bytes, &off);
+  if (offset) *offset = *entry < 0 ? 0 : off;
+  if (generation) *generation = *entry < 0 ? 0 : table->t.e[*entry].generation;
+  return ncclSuccess;
+}
+VCCL_EXPORT ncclResult_t vcclRegTableRemove(vcclRegTable_t* table, int entry) {
+  if (!table || !reg_remove(&table->t, entry)) return ncclInvalidArgument;
+  return ncclSuccess;
+}
+VCCL_EXPORT ncclResult_t vcclRegTableFree(vcclRegTable_t* table) {
+  delete table;
+  return ncclSuccess;
+}
+
+// Synchronises the device, then reads the three device-resident counters.
+VCCL_EXPORT ncclResult_t vcclCommRegStats(ncclComm_t comm, unsigned long long* launches,
+                                          unsigned long long* zeroCopy, unsigned long long* fallback,
+                                          int* liveEntries, int* imported) {
+  NCCLCHECK(comm_check(comm, "vcclCommRegStats"));
+  unsigned long long w[3] = {0, 0, 0};
+  if (comm->reg) {
+    DeviceGuard dev(comm->device);
+    HIPCHECK(dev.status);
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpy(w, comm->reg->stats, sizeof(w), hipMemcpyDeviceToHost));
+  }
+  if (launches) *launches = w[0];
+  if (zeroCopy) *zeroCopy = w[1];
+  if (fallback) *fallback = w[2];
+  if (liveEntries) *liveEntries = comm->reg ? reg_live_count(&comm->reg->table) : 0;
+  if (imported) *imported = comm->reg ? reg_imported_count(comm) : 0;
+  return ncclSuccess;
+}
+
+// A tuning / measurement knob: every rank must call it alike, outside a group.
+// A comm initialised without a registry has none to switch on: 0 stays 0.
+VCCL_EXPORT ncclResult_t vcclCommSetRegThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective) {
+  NCCLCHECK(comm_check(comm, "vcclCommSetRegThreshold"));
+  if (bytes < 0) return ncclInvalidArgument;
+  if (comm->reg)  // a registry exists only where no peer is behind the net proxy
+    comm->reg->threshold = reg_max_of(*comm, bytes, comm->nRanks, false, comm->dPeers != nullptr);
+  if (effective) *effective = comm->reg ? (int64_t)comm->reg->threshold : 0;
   return ncclSuccess;
 }
 

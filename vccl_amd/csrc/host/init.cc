@@ -26,6 +26,7 @@
 #include "../device/coll_types.hpp"
 #include "../device/ring_launch.hpp"
 #include "core.h"
+#include "regcomm.h"
 #include "setup.h"
 
 namespace vccl {
@@ -107,6 +108,7 @@ static void destroy_null(hipEvent_t& e) {
 
 static void free_resources(ncclComm* c) {
   net_stop(c);  // first: its threads read the host staging memory and flags
+  reg_destroy(c);  // the buffer registry, its imports and every handle still out
   for (void* p : c->ipcOpened) (void)hipIpcCloseMemHandle(p);
   c->ipcOpened.clear();
   free_null(c->fifoBuf);
@@ -398,6 +400,7 @@ static ncclResult_t init_rank(ncclComm* c, const ncclUniqueId* id) {
   NCCLCHECK(create_flags_and_events(c));
   PeerMap me{};
   NCCLCHECK(alloc_buffers(c, sizes, &me));
+  reg_create(c, &me);  // VCCL_REG_THRESHOLD: this rank's buffer registry, named in `me`
   NCCLCHECK(exchange_peers(c, &me));
   MeshSetup mesh;
   NCCLCHECK(apply_mesh(c, &mesh));
@@ -406,8 +409,10 @@ static ncclResult_t init_rank(ncclComm* c, const ncclUniqueId* id) {
   VINFO("rank %d: map peers", c->rank);
   if (c->nRanks > 1) NCCLCHECK(connect_channels(c, rings, mesh));
   if (c->nRanks > 1) NCCLCHECK(connect_p2p(c, mesh));
+  NCCLCHECK(reg_connect(c, mesh.anyNet));  // every peer's registry mapped before the barrier ...
   VINFO("rank %d: final barrier", c->rank);
   NCCLCHECK(bootstrap_barrier(c->bootstrap));
+  reg_unlink(c);  // ... so its name can go after it
   VINFO("comm %p rank %d/%d dev %d: %d channels x %d threads, step %d B, FIFO slot %d B", (void*)c, c->rank,
         c->nRanks, c->device, c->nChannels, c->nThreads, c->stepBytes, c->slotBytes);
   VINFO("rank %d: thresholds LL %zu, LL RS/AG %zu, direct %zu, direct RS/AG %zu, LL128 [%zu, %zu]%s, "
@@ -626,17 +631,23 @@ VCCL_EXPORT ncclResult_t ncclMemFree(void* ptr) {
   return ncclSuccess;
 }
 
-// nccl.h.in:208-217: buffer registration enables zero-copy in the reference;
-// that is out of scope here and every collective works on
-// unregistered buffers, so registration is accepted and does nothing.
-VCCL_EXPORT ncclResult_t ncclCommRegister(const ncclComm_t comm, void* buff, size_t, void** handle) {
+// nccl.h.in:208-217: buffer registration enables zero-copy in the reference
+// (src/register/register.cc).  Every collective works on unregistered buffers;
+// on a comm created with VCCL_REG_THRESHOLD the range is recorded and made
+// addressable by the comm's other ranks (regcomm.h) — local, non-collective —
+// and the direct all-reduce / reduce-scatter / all-gather of at least the
+// threshold run zero-copy when every rank's buffers are registered (DESIGN.md
+// §4.14).  Without it registration is accepted and does nothing, as before.
+VCCL_EXPORT ncclResult_t ncclCommRegister(const ncclComm_t comm, void* buff, size_t size, void** handle) {
   NCCLCHECK(comm_check(comm, "ncclCommRegister"));
   if (!handle) return ncclInvalidArgument;
+  if (comm->reg) return reg_register(comm, buff, size, handle);
   *handle = buff;
   return ncclSuccess;
 }
-VCCL_EXPORT ncclResult_t ncclCommDeregister(const ncclComm_t comm, void*) {
+VCCL_EXPORT ncclResult_t ncclCommDeregister(const ncclComm_t comm, void* handle) {
   NCCLCHECK(comm_check(comm, "ncclCommDeregister"));
+  if (comm->reg) return reg_deregister(comm, handle);
   return ncclSuccess;
 }
 

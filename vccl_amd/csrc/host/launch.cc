@@ -17,6 +17,7 @@
 #include "../device/launch.hpp"
 #include "../device/p2p_launch.hpp"
 #include "../device/ring_launch.hpp"
+#include "regcomm.h"
 
 namespace vccl {
 
@@ -488,13 +489,60 @@ static ncclResult_t launch_direct(const Task* ts, int nTasks, hipEvent_t stop) {
   return ncclSuccess;
 }
 
+// Zero-copy over registered buffers (device/direct_reg.hpp).  Eligibility is
+// plan.cc reg_eligible's: from the call's arguments and comm-wide values alone,
+// so every rank launches the negotiating kernel for the same calls, ahead of
+// select_algo's choice and at any size above the threshold; its fallback is
+// the staged direct path at any size, decided on the device.
+static bool reg_task_eligible(const Task& t) {
+  const ncclComm* c = t.comm;
+  return c->reg && c->dPeers &&
+         reg_eligible(t.coll, (int64_t)t.count, type_size(t.datatype), c->nRanks, c->reg->threshold, t.groupColls);
+}
+// The staged geometry is direct_work_of's (the fallback runs it as it is), the
+// zero-copy block length plan.cc reg_plan's on the same grid; the descriptors
+// are this rank's registrations of the call's buffers as of now, and the
+// import table is brought up to date first (nothing in the steady state).
+static ncclResult_t launch_direct_reg(const Task& t, hipEvent_t stop) {
+  ncclComm* comm = t.comm;
+  CaptureState cs{false, 0};
+  NCCLCHECK(capture_state(t.stream, &cs));
+  NCCLCHECK(reg_refresh(comm, cs.active));
+  DirectRegWork rw{};
+  int kt = -1, devOp = -1;
+  NCCLCHECK(direct_work_of(t, &rw.w, &kt, &devOp));
+  const auto [count, esz] = call_size(t.coll, t.count, t.datatype);
+  RegPlanOut rp;
+  NCCLCHECK(reg_plan(t.coll, comm->nRanks, comm->rank, count, esz, rw.w.nBlocks, &rp));
+  rw.reg = comm->reg->tabDev;
+  rw.stats = comm->reg->stats;
+  rw.zcBlkElts = rp.blkElts;
+  rw.needRecv = t.coll == kAllReduce;
+  // what the peers read of mine: the whole input; the all-reduce's output too
+  rw.mine.sendBytes = (uint64_t)(t.coll == kReduceScatter ? count * comm->nRanks : count) * (uint64_t)esz;
+  rw.mine.recvBytes = rw.needRecv ? (uint64_t)count * (uint64_t)esz : 0;
+  reg_describe(comm, t.sendbuff, rw.mine.sendBytes, &rw.mine.sendEntry, &rw.mine.sendGen, &rw.mine.sendOff);
+  rw.mine.recvEntry = kRegNone;
+  if (rw.needRecv)
+    reg_describe(comm, t.recvbuff, rw.mine.recvBytes, &rw.mine.recvEntry, &rw.mine.recvGen, &rw.mine.recvOff);
+  const hipError_t e =
+      by_kernel_type(kt, [&]<int K>() { return direct_reg_launch<K>(t.coll, devOp, rw, t.stream, stop); });
+  if (e != hipSuccess) {
+    VWARN("zero-copy direct kernel launch failed: %s", hipGetErrorString(e));
+    return ncclUnhandledCudaError;
+  }
+  return ncclSuccess;
+}
+
 // A call's path: select_algo on the comm's thresholds.
 static int choose_algo(const Task& t) {
   return select_algo(policy_of(t.comm), t.coll, type_size(t.datatype), (int64_t)t.count);
 }
 
 // 1 .. max_parts(algo) fusable calls as one launch of path `algo`.
+constexpr int kAlgoDirectReg = 100;  // launch.cc only: one eligible call, the zero-copy kernel
 static ncclResult_t launch_path(int algo, const Task* ts, int n, hipEvent_t stop) {
+  if (algo == kAlgoDirectReg) return n == 1 ? launch_direct_reg(ts[0], stop) : ncclInternalError;
   return algo == kAlgoLL ? launch_ll(ts, n, stop)
          : algo == kAlgoDirect ? launch_direct(ts, n, stop) : launch_ring(ts, n, algo == kAlgoRingLL128, stop);
 }
@@ -513,7 +561,8 @@ ncclResult_t launch_task(const Task& t) {
   } else {
     CaptureState cs{false, 0};
     r = stream_order(comm, t.stream, &cs);
-    if (r == ncclSuccess) r = launch_path(choose_algo(t), &t, 1, stop_event(comm, cs));
+    if (r == ncclSuccess)
+      r = launch_path(reg_task_eligible(t) ? kAlgoDirectReg : choose_algo(t), &t, 1, stop_event(comm, cs));
     if (r == ncclSuccess) r = stream_mark(comm, t.stream, cs);
   }
   comm->opCount++;  // whatever the outcome
@@ -625,8 +674,12 @@ static ncclResult_t launch_planned(std::vector<Task>& tasks, const std::vector<i
   std::vector<int64_t> runLines;
   static const bool fusePlanned = param_int("GROUP_PLAN_FUSE", 1) != 0;
   for (int k : plan.order) {
-    const Task& t = tasks[idx[k]];
-    const int a = plan.algo[k];
+    Task t = tasks[idx[k]];
+    // the comm's only collective of the group, eligible for the zero-copy
+    // kernel: its partition is the call's alone, as outside a group
+    const bool zeroCopy = reg_task_eligible(t);
+    if (zeroCopy) t.planned = false;
+    const int a = zeroCopy ? kAlgoDirectReg : plan.algo[k];
     const int64_t lines = a == kAlgoLL ? ll_lines_of(t) : 0;
     if (fusePlanned && !runs.empty() && runPlan.back() == plan.planOf[k] && runAlgo.back() == a &&
         runs.back().size() < (size_t)max_parts(a) && fusable(runs.back()[0], t) &&
@@ -913,6 +966,8 @@ static ncclResult_t launch_comm_p2p(const std::vector<Task>& mine) {
 static ncclResult_t launch_group_colls(std::vector<Task>& tasks) {
   ncclResult_t ret = ncclSuccess;
   const size_t n = tasks.size();
+  for (Task& t : tasks)
+    t.groupColls = (int)std::count_if(tasks.begin(), tasks.end(), [&](const Task& o) { return o.comm == t.comm; });
   std::vector<char> done(n, 0);
   const bool fuse = param_int("GROUP_FUSE", 1) != 0;
   // VCCL_GROUP_PLAN=0: every call keeps its own path and the partition of a

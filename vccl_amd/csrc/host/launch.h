@@ -45,6 +45,9 @@ struct Task {
   CbdPlan plan;
   // kTaskA2a: the call's rows, owned by the API layer until launch_group returns
   const A2aArgs* a2a;
+  // The collectives of this call's comm in its group (launch_group_colls); 0
+  // outside a group.  More than one: not eligible for the zero-copy path.
+  int groupColls;
 };
 
 // The one place that reads a comm into the planner's thresholds.

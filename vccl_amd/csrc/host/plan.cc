@@ -555,6 +555,70 @@ ncclResult_t direct_rooted_plan(int coll, int nRanks, int rank, int root, int64_
   return ncclSuccess;
 }
 
+// -------------------------------------------------------- registered buffers
+uint64_t reg_max(int64_t threshold, bool inbox, bool directAllowed, bool anyNet, int nRanks) {
+  if (threshold <= 0 || !inbox || !directAllowed || anyNet || nRanks < 2 || nRanks > kDirectMaxRanks) return 0;
+  return (uint64_t)threshold;
+}
+int64_t reg_call_bytes(int coll, int64_t count, int64_t typeSize, int nRanks) {
+  return coll == kAllReduce ? count * typeSize : (int64_t)nRanks * count * typeSize;
+}
+bool reg_eligible(int coll, int64_t count, int64_t typeSize, int nRanks, uint64_t effective, int groupCalls) {
+  if (effective == 0 || groupCalls > 1) return false;
+  if (coll != kAllReduce && coll != kReduceScatter && coll != kAllGather) return false;
+  return (uint64_t)reg_call_bytes(coll, count, typeSize, nRanks) >= effective;
+}
+
+// The steps below are the zero-copy kernels' order, rank by
+// rank; the peer loops run in the direct kernels' rotation, (rank + k) mod n.
+ncclResult_t reg_plan(int coll, int nRanks, int rank, int64_t count, int64_t eltSize, int nBlocks, RegPlanOut* out) {
+  if (coll != kAllReduce && coll != kReduceScatter && coll != kAllGather) return ncclInvalidArgument;
+  const int n = nRanks;
+  const int64_t esz = eltSize, eltAlign = std::max<int64_t>(1, 16 / esz);
+  const int64_t shard = coll == kAllReduce ? direct_shard_elts(count, n, eltAlign) : count;
+  out->shardElts = shard;
+  out->blkElts = ((shard + nBlocks - 1) / nBlocks + eltAlign - 1) / eltAlign * eltAlign;
+  auto& st = out->steps;
+  st.clear();
+  auto post = [&](int epoch, int phase) { st.push_back(RegStep{kRStepPost, epoch, phase, 0, 0, 0, 0, 0}); };
+  auto wait = [&](int epoch, int phase) {
+    for (int k = 1; k < n; k++) st.push_back(RegStep{kRStepWait, epoch, phase, (rank + k) % n, 0, 0, 0, 0});
+  };
+  // epoch 0: descriptors out ("my input is ready"), descriptors in, verdicts out, verdicts in
+  post(0, 0);
+  wait(0, 0);
+  post(0, 1);
+  wait(0, 1);
+  if (coll == kAllReduce) {
+    // shard o = elements [o * shard, min((o + 1) * shard, count)), owned by rank o
+    auto lo_of = [&](int o) { return std::min((int64_t)o * shard, count) * esz; };
+    auto len_of = [&](int o) { return std::min((int64_t)(o + 1) * shard, count) * esz - lo_of(o); };
+    for (int k = 0; k < n; k++)  // fold my shard from the n inputs
+      st.push_back(RegStep{kRStepFold, 1, 0, (rank + k) % n, kRBufSend, lo_of(rank), lo_of(rank), len_of(rank)});
+    post(1, 0);  // "shard `rank` of my recvbuff is final, and I have finished reading your inputs"
+    wait(1, 0);
+    for (int k = 1; k < n; k++) {  // pull the other owners' shards from THEIR recvbuff
+      const int o = (rank + k) % n;
+      st.push_back(RegStep{kRStepCopy, 1, 0, o, kRBufRecv, lo_of(o), lo_of(o), len_of(o)});
+    }
+    post(1, 1);  // "finished reading your recvbuff"
+    wait(1, 1);
+    return ncclSuccess;
+  }
+  for (int k = 0; k < n; k++) {
+    const int p = (rank + k) % n;
+    if (coll == kReduceScatter)  // block `rank` of every input -> my recvbuff
+      st.push_back(RegStep{kRStepFold, 1, 0, p, kRBufSend, (int64_t)rank * count * esz, 0, count * esz});
+    else  // every rank's input -> block p of my recvbuff
+      st.push_back(RegStep{kRStepCopy, 1, 0, p, kRBufSend, 0, (int64_t)p * count * esz, count * esz});
+  }
+  post(1, 0);  // "I have finished reading you"
+  wait(1, 0);
+  post(1, 1);  // the closing round (reuse rule R2, direct.hpp)
+  wait(1, 1);
+  return ncclSuccess;
+}
+
 // ---------------------------------------------------------------- all-to-all
 uint64_t ll_a2a_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks, bool hasP2p) {
   if (threshold <= 0 || llSlotBytes <= 0 || !llAllowed || anyNet || nRanks < 2 || nRanks > kOrderMaxRanks || !hasP2p)

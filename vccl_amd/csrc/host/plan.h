@@ -187,6 +187,59 @@ struct DirectRootedPlanOut {
 ncclResult_t direct_rooted_plan(int coll, int nRanks, int rank, int root, int64_t count, int64_t eltSize,
                                 int64_t regionBytes, int chunk, DirectRootedPlanOut* out);
 
+// -------------------------------------------------------- registered buffers
+// The zero-copy direct all-reduce / reduce-scatter / all-gather over
+// ncclCommRegister'ed buffers (reg.h holds the table): the
+// host's half — the threshold, the eligibility rule and the step list of one
+// zero-copy launch.
+// A comm's VCCL_REG_THRESHOLD (bytes) as it takes effect: 0 without mapped
+// inboxes and direct flags, with Direct excluded by NCCL_ALGO, with a peer
+// behind the net proxy, or with fewer than 2 or more than kDirectMaxRanks ranks.
+uint64_t reg_max(int64_t threshold, bool inbox, bool directAllowed, bool anyNet, int nRanks);
+// A call's size as the threshold measures it: the all-reduce's count * esz,
+// the whole nRanks-block buffer of a reduce-scatter (recvcount) / all-gather
+// (sendcount).
+int64_t reg_call_bytes(int coll, int64_t count, int64_t typeSize, int nRanks);
+// From the call's own arguments and comm-wide values alone (a rank cannot
+// know what its peers registered): effective > 0, an all-reduce, reduce-
+// scatter or all-gather, not a member of a group that holds more than one
+// collective (groupCalls = the collectives of the call's group, 0 or 1 for a
+// call alone), and at least `effective` bytes.
+bool reg_eligible(int coll, int64_t count, int64_t typeSize, int nRanks, uint64_t effective, int groupCalls);
+// One zero-copy launch as `rank` runs it on a grid of nBlocks workgroups: two
+// positions of the comm's direct epoch sequence.  Epoch 0 negotiates (the
+// descriptors travel with the phase-0 flags, the verdicts with the phase-1
+// flags); epoch 1 moves the data with no inbox: one "chunk", every rank PULLS
+// from its peers' registered buffers and stores into its own recvbuff only.
+//   kRStepPost  {epoch, phase}: my flag at every peer
+//   kRStepWait  {epoch, phase, peer}: that peer's flag at me
+//   kRStepFold  {epoch, peer, buf, peerOff, ownOff, bytes}: `peer`'s buffer
+//               `buf` at peerOff is one source of the n-source fold stored at
+//               recvbuff[ownOff ..] (peer == rank: my own input); the n fold
+//               steps of a launch are ONE reduce-copy, listed in rank rotation
+//               (the fold order itself is the ring's, from the comm's tables)
+//   kRStepCopy  {epoch, peer, buf, peerOff, ownOff, bytes}: a plain copy of
+//               peer's buffer into recvbuff[ownOff ..] (peer == rank, buf
+//               send: the all-gather's own block, skipped by the kernel when
+//               the call is in place)
+// Offsets and lengths in bytes; a step covers a whole shard, of which
+// workgroup b moves elements [b * blkElts, (b + 1) * blkElts).  shardElts: the
+// all-reduce's direct_shard_elts of the whole count, a reduce-scatter's
+// recvcount, an all-gather's bytes per rank; blkElts = alignUp(ceil(shardElts
+// / nBlocks), 16 bytes).  count in elements of eltSize (an all-gather: bytes,
+// eltSize 1).  ncclInvalidArgument for any other collective.
+enum { kRStepPost = 0, kRStepWait = 1, kRStepFold = 2, kRStepCopy = 3 };
+enum { kRBufSend = 0, kRBufRecv = 1 };
+struct RegStep {
+  int kind, epoch, phase, peer, buf;
+  int64_t peerOff, ownOff, bytes;
+};
+struct RegPlanOut {
+  int64_t shardElts = 0, blkElts = 0;
+  std::vector<RegStep> steps;
+};
+ncclResult_t reg_plan(int coll, int nRanks, int rank, int64_t count, int64_t eltSize, int nBlocks, RegPlanOut* out);
+
 // ---------------------------------------------------------------- all-to-all
 // A comm's VCCL_LL_A2A_THRESHOLD (bytes per ordered pair) as it takes effect:
 // clamped to what one LL slot holds; 0 without LL buffers, with LL excluded by

@@ -396,6 +396,10 @@ size_t direct_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool
                                 hasP2p);
 }
 
+size_t reg_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool inbox) {
+  return (size_t)reg_max(threshold, inbox, (s.algoAllowed & kAllowDirect) != 0, anyNet, nRanks);
+}
+
 static bool same_gpu(const PeerId& a, const PeerId& b) { return a.hostHash == b.hostHash && a.busId == b.busId; }
 
 ncclResult_t setup_mesh(int rank, const std::vector<PeerId>& peers, CommSetup* s, MeshSetup* m) {

@@ -98,6 +98,10 @@ size_t ll_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool any
 // likewise (setup_local; vcclCommSetDirectA2aThreshold).
 size_t direct_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool hasP2p);
 
+// A comm's VCCL_REG_THRESHOLD of `threshold` as it takes effect (plan.h
+// reg_max; inbox: every peer's inbox and direct flags are mapped).
+size_t reg_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool inbox);
+
 // What a rank publishes about where it runs (a PeerMap's identity fields).
 struct PeerId {
   int pid;

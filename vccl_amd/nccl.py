@@ -56,6 +56,10 @@ EXPORTED = [
     "vcclLLA2aMax", "vcclLLA2aPlan", "vcclCommA2aStats", "vcclCommSetA2aThreshold",
     # one-hop direct all-to-all: the per-pair limit, one call's LL / direct / FIFO split, the counters, the live knob
     "vcclDirectA2aMax", "vcclDirectA2aPlan", "vcclCommA2aStatsEx", "vcclCommSetDirectA2aThreshold",
+    # zero-copy direct AR / RS / AG over registered buffers: the threshold, the eligibility rule, one launch's
+    # steps, the registration table on its own, the counters, the live knob
+    "vcclRegMax", "vcclRegEligible", "vcclRegPlan", "vcclRegTableNew", "vcclRegTableInsert", "vcclRegTableFind",
+    "vcclRegTableRemove", "vcclRegTableFree", "vcclCommRegStats", "vcclCommSetRegThreshold",
     # out of scope, exported so libnccl-linked binaries load: WARN + ncclInvalidUsage
     "ncclGroupSimulateEnd",
     # memory / registration / scalable init (what a libnccl caller such as
@@ -198,6 +202,20 @@ def lib() -> ctypes.CDLL:
                               ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
         "vcclCommA2aStatsEx": [vp] + [ctypes.POINTER(ctypes.c_ulonglong)] * 5,
         "vcclCommSetDirectA2aThreshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
+        "ncclCommRegister": [vp, vp, c_size, ctypes.POINTER(vp)],
+        "ncclCommDeregister": [vp, vp],
+        "vcclRegMax": [ctypes.c_int64, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int64)],
+        "vcclRegEligible": [c_int, c_size, c_int, c_int, ctypes.c_int64, c_int, ctypes.POINTER(c_int)],
+        "vcclRegPlan": [c_int, c_size, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int64), c_int,
+                        ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_int64)],
+        "vcclRegTableNew": [ctypes.POINTER(vp)],
+        "vcclRegTableInsert": [vp, u64, c_size, ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_uint32)],
+        "vcclRegTableFind": [vp, u64, c_size, ctypes.POINTER(c_int), ctypes.POINTER(u64),
+                             ctypes.POINTER(ctypes.c_uint32)],
+        "vcclRegTableRemove": [vp, c_int],
+        "vcclRegTableFree": [vp],
+        "vcclCommRegStats": [vp] + [ctypes.POINTER(ctypes.c_ulonglong)] * 3 + [ctypes.POINTER(c_int)] * 2,
+        "vcclCommSetRegThreshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
         "vcclAlgoSelection": [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(c_int),
                               ctypes.POINTER(c_int)],
         "vcclCommSetup": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(u64),
@@ -449,6 +467,76 @@ def ll_a2a_plan(nranks: int, rank: int, send_bytes, recv_bytes, uniform: bool, l
             "res_sends": list(rs[:nrs.value]), "res_recvs": list(rr[:nrr.value])}
 
 
+REG_STEP_KINDS = ("post", "wait", "fold", "copy")
+REG_BUFS = ("send", "recv")
+REG_MAX_ENTRIES = 32
+
+
+def reg_max(threshold: int | None, inbox: bool = True, direct_allowed: bool = True, any_net: bool = False,
+            nranks: int = 8) -> int:
+    """vcclRegMax: VCCL_REG_THRESHOLD as a comm takes it (None: from the
+    environment; 0 = off)."""
+    eff = ctypes.c_int64()
+    check(lib().vcclRegMax(-1 if threshold is None else threshold, int(inbox), int(direct_allowed), int(any_net),
+                           nranks, ctypes.byref(eff)), "vcclRegMax")
+    return eff.value
+
+
+def reg_eligible(coll: int, count: int, dtype: int, nranks: int, effective: int, group_calls: int = 0) -> bool:
+    """vcclRegEligible: whether a call launches the negotiating zero-copy kernel."""
+    out = ctypes.c_int()
+    check(lib().vcclRegEligible(coll, count, dtype, nranks, effective, group_calls, ctypes.byref(out)),
+          "vcclRegEligible")
+    return bool(out.value)
+
+
+def reg_plan(coll: int, count: int, dtype: int, nranks: int, rank: int, nblocks: int) -> dict:
+    """vcclRegPlan: one zero-copy launch as `rank` runs it on nblocks workgroups.
+    Returns blk_elts and steps = [(kind, epoch, phase, peer, buf, peer offset,
+    own offset, bytes)] with kind from REG_STEP_KINDS and buf from REG_BUFS."""
+    cap = 8 * nranks + 16
+    steps = (ctypes.c_int64 * (8 * cap))()
+    ns, blk = ctypes.c_int(), ctypes.c_int64()
+    check(lib().vcclRegPlan(coll, count, dtype, nranks, rank, nblocks, ctypes.byref(blk), cap, ctypes.byref(ns),
+                            steps), "vcclRegPlan")
+    out = []
+    for i in range(ns.value):
+        k, ep, ph, peer, buf, poff, ooff, nb = steps[8 * i:8 * i + 8]
+        out.append((REG_STEP_KINDS[k], ep, ph, peer, REG_BUFS[buf], poff, ooff, nb))
+    return {"blk_elts": blk.value, "steps": out}
+
+
+class RegTable:
+    """vcclRegTable*: the registration table on its own (no comm, no GPU)."""
+
+    def __init__(self):
+        self.handle = ctypes.c_void_p()
+        check(lib().vcclRegTableNew(ctypes.byref(self.handle)), "vcclRegTableNew")
+
+    def insert(self, addr: int, nbytes: int) -> tuple[int, int]:
+        """(entry, generation); entry -1: refused (the table is full)."""
+        e, g = ctypes.c_int(), ctypes.c_uint32()
+        check(lib().vcclRegTableInsert(self.handle, addr, nbytes, ctypes.byref(e), ctypes.byref(g)),
+              "vcclRegTableInsert")
+        return e.value, g.value
+
+    def find(self, addr: int, nbytes: int) -> tuple[int, int, int]:
+        """(entry, offset in it, generation); entry -1: not registered."""
+        e, o, g = ctypes.c_int(), ctypes.c_uint64(), ctypes.c_uint32()
+        check(lib().vcclRegTableFind(self.handle, addr, nbytes, ctypes.byref(e), ctypes.byref(o), ctypes.byref(g)),
+              "vcclRegTableFind")
+        return e.value, o.value, g.value
+
+    def remove(self, entry: int) -> int:
+        """The result code (ncclInvalidArgument for an entry that is not live)."""
+        return lib().vcclRegTableRemove(self.handle, entry)
+
+    def free(self):
+        if self.handle:
+            lib().vcclRegTableFree(self.handle)
+            self.handle = ctypes.c_void_p()
+
+
 A2A_FIFO, A2A_LL, A2A_DIRECT = 0, 1, 2
 
 
@@ -689,6 +777,30 @@ class Comm:
         eff = ctypes.c_int64()
         check(lib().vcclCommSetDirectA2aThreshold(self.handle, nbytes, ctypes.byref(eff)),
               "vcclCommSetDirectA2aThreshold")
+        return eff.value
+
+    def register(self, buf: int, nbytes: int) -> int:
+        """ncclCommRegister: the handle (an integer)."""
+        h = ctypes.c_void_p()
+        check(lib().ncclCommRegister(self.handle, buf, nbytes, ctypes.byref(h)), "ncclCommRegister")
+        return h.value or 0
+
+    def deregister(self, handle: int):
+        check(lib().ncclCommDeregister(self.handle, handle), "ncclCommDeregister")
+
+    def reg_stats(self) -> tuple[int, int, int, int, int]:
+        """vcclCommRegStats (synchronises the device): eligible launches,
+        zero-copy outcomes, fallback outcomes, live registrations, imported ranges."""
+        a, b, c = ctypes.c_ulonglong(), ctypes.c_ulonglong(), ctypes.c_ulonglong()
+        d, e = ctypes.c_int(), ctypes.c_int()
+        check(lib().vcclCommRegStats(self.handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d),
+                                     ctypes.byref(e)), "vcclCommRegStats")
+        return a.value, b.value, c.value, d.value, e.value
+
+    def set_reg_threshold(self, nbytes: int) -> int:
+        """vcclCommSetRegThreshold: every rank alike, outside a group; the effective value."""
+        eff = ctypes.c_int64()
+        check(lib().vcclCommSetRegThreshold(self.handle, nbytes, ctypes.byref(eff)), "vcclCommSetRegThreshold")
         return eff.value
 
     def coll_algo(self, coll: int, count: int, dtype: int) -> str:
