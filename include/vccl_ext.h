@@ -366,8 +366,9 @@ ncclResult_t vcclCommSetDirectA2aThreshold(ncclComm_t comm, int64_t bytes, int64
  *                    the peers' ranges it has imported.  All 0 on a comm
  *                    without a registry.
  *   vcclCommSetRegThreshold  the threshold for later calls; every rank calls
- *                    it alike, outside a group.  A comm initialised without
- *                    VCCL_REG_THRESHOLD has no registry: *effective stays 0. */
+ *                    it alike, outside a group.  A comm initialised with neither
+ *                    VCCL_REG_THRESHOLD nor VCCL_REG_A2A_THRESHOLD has no
+ *                    registry: *effective stays 0. */
 typedef struct vcclRegTable vcclRegTable_t;
 ncclResult_t vcclRegMax(int64_t threshold, int inbox, int directAllowed, int anyNet, int nRanks, int64_t* effective);
 ncclResult_t vcclRegEligible(int coll, size_t count, ncclDataType_t datatype, int nRanks, int64_t effective,
@@ -384,6 +385,45 @@ ncclResult_t vcclRegTableFree(vcclRegTable_t* table);
 ncclResult_t vcclCommRegStats(ncclComm_t comm, unsigned long long* launches, unsigned long long* zeroCopy,
                               unsigned long long* fallback, int* liveEntries, int* imported);
 ncclResult_t vcclCommSetRegThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
+/* Zero-copy ncclAllToAll / ncclAllToAllv over ncclCommRegister'ed send buffers
+ * (opt-in: VCCL_REG_A2A_THRESHOLD, bytes per ordered pair, default 0 = off;
+ * DESIGN.md 4.15).  Only sendbuff needs registering.
+ *   vcclRegA2aMax    the threshold as a comm takes it (threshold < 0: from the
+ *                    environment): 0 wherever vcclRegMax gives 0, without
+ *                    point-to-point connections (hasP2p = 0: the fallback needs
+ *                    the FIFOs), or when a rank failed to create its registry
+ *                    (allRegistries = 0).
+ *   vcclRegA2aEligible  whether the all-to-all that has `index` eligible ones
+ *                    of its comm before it in its group launches the
+ *                    negotiating kernel: effective > 0, index < 8, and a
+ *                    uniform call of pairBytes >= effective or any v-call.
+ *   vcclRegA2aPlan   one launch as `rank` runs it.  sendBytes / sendOff: the
+ *                    nRanks x nRanks matrices, row r rank r's bytes and byte
+ *                    offsets in its sendbuff per peer; recvOff: this rank's
+ *                    nRanks receive offsets.  *nBlocks: the grid.  steps[8 *
+ *                    cap]: kind (0 post, 1 wait, 2 vote, 3 pull, 4 self copy),
+ *                    epoch, phase, peer, the byte offset in the peer's
+ *                    sendbuff, the byte offset in my recvbuff, bytes, and the
+ *                    slice length (workgroup b moves bytes [b * slice, (b + 1)
+ *                    * slice) of the block) — in the kernel's order; with the
+ *                    verdict 0 the launch ends after epoch 0.
+ *                    ncclInvalidArgument when cap < *nSteps.
+ *   vcclCommRegA2aStats  synchronises the device, then: eligible launches,
+ *                    zero-copy outcomes, fallback outcomes (device-resident,
+ *                    so graph replays count).  All 0 without a registry.
+ *   vcclCommSetRegA2aThreshold  the threshold for later calls; every rank
+ *                    calls it alike, outside a group.  A comm initialised with
+ *                    neither VCCL_REG_THRESHOLD nor VCCL_REG_A2A_THRESHOLD has
+ *                    no registry: *effective stays 0. */
+ncclResult_t vcclRegA2aMax(int64_t threshold, int inbox, int directAllowed, int anyNet, int nRanks, int hasP2p,
+                           int allRegistries, int64_t* effective);
+ncclResult_t vcclRegA2aEligible(int uniform, size_t pairBytes, int64_t effective, int index, int* eligible);
+ncclResult_t vcclRegA2aPlan(int nRanks, int rank, const size_t* sendBytes, const size_t* sendOff,
+                            const size_t* recvOff, int uniform, int minCTAs, int maxCTAs, int directMaxBlocks,
+                            int* nBlocks, int cap, int* nSteps, int64_t* steps);
+ncclResult_t vcclCommRegA2aStats(ncclComm_t comm, unsigned long long* launches, unsigned long long* zeroCopy,
+                                 unsigned long long* fallback);
+ncclResult_t vcclCommSetRegA2aThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
 /* What initialisation decides for rank `rank` of an nRanks communicator with
  * CTA bounds minCTAs / maxCTAs (a comm's defaults: 1 / 128), from the
  * environment as at init and each rank's identity pid[r], hostHash[r],

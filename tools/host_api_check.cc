@@ -572,6 +572,53 @@ int main() {
     }
     EXPECT(vcclCommRegStats(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == ncclInvalidArgument);
     EXPECT(vcclCommSetRegThreshold(nullptr, 4096, nullptr) == ncclInvalidArgument);
+    // the zero-copy all-to-all's threshold, eligibility and step lists on
+    // random byte matrices, offsets, bounds and invalid arguments
+    for (int trial = 0; trial < 20000; trial++) {
+      if (rng() % 2) setenv("VCCL_REG_A2A_THRESHOLD", rng() % 4 ? "32768" : junk[rng() % 11], 1);
+      else unsetenv("VCCL_REG_A2A_THRESHOLD");
+      const int n = (int)pick({0, 1, 2, 3, 4, 8, 9}), rank = (int)(rng() % (n + 1)) - (rng() % 32 == 0);
+      int64_t eff = -7;
+      const ncclResult_t r0 = vcclRegA2aMax(pick({-1, 0, 1, 32768, 1ll << 40}), (int)(rng() % 2), (int)(rng() % 2),
+                                            (int)(rng() % 2), n, (int)(rng() % 2), (int)(rng() % 2),
+                                            rng() % 16 ? &eff : nullptr);
+      EXPECT(r0 == ncclSuccess || r0 == ncclInvalidArgument);
+      if (r0 == ncclSuccess) EXPECT(eff >= 0 && (eff == 0 || (n >= 2 && n <= 8)));
+      int el = -7;
+      const int index = (int)pick({-1, 0, 1, 7, 8, 9});
+      const ncclResult_t r1 = vcclRegA2aEligible((int)(rng() % 2), (size_t)pick({0, 1, 32767, 32768, 1 << 20}),
+                                                 pick({-1, 0, 1, 32768}), index, rng() % 16 ? &el : nullptr);
+      EXPECT(r1 == ncclSuccess || r1 == ncclInvalidArgument);
+      if (r1 == ncclSuccess) EXPECT((el == 0 || el == 1) && (index < 8 || el == 0));
+      const int uniform = (int)(rng() % 2), cap = (int)pick({0, 8, 64});
+      const size_t m = (size_t)(n > 0 ? n : 1);
+      std::vector<size_t> sb(m * m), so(m * m), ro(m);
+      const size_t ub = (size_t)pick({0, 1, 40, 32768, (1 << 20) + 3});
+      for (size_t i = 0; i < m * m; i++) {
+        sb[i] = uniform && rng() % 64 ? ub : (size_t)pick({0, 1, 17, 4096, 100003, 1ll << 57});
+        so[i] = (size_t)pick({0, 1, 4, 4096, 1 << 22}) + rng() % 3;
+      }
+      for (size_t i = 0; i < m; i++) ro[i] = (size_t)pick({0, 3, 4096, 1 << 22});
+      std::vector<int64_t> steps(8 * (size_t)cap + 8, -1);
+      int ns = -7, nb = -7;
+      const ncclResult_t r2 = vcclRegA2aPlan(n, rank, rng() % 32 ? sb.data() : nullptr, so.data(), ro.data(), uniform,
+                                             (int)pick({-1, 0, 1, 4, 200}), (int)pick({0, 1, 32, 64, 500}),
+                                             (int)pick({0, 1, 14, 64, 128, 300}), rng() % 32 ? &nb : nullptr, cap, &ns,
+                                             steps.data());
+      EXPECT(r2 == ncclSuccess || r2 == ncclInvalidArgument);
+      if (r2 == ncclSuccess) {
+        EXPECT(ns == 5 * n + 1 && ns <= cap && nb >= 1 && nb <= 128);
+        for (int k = 0; k < ns; k++) {  // every pull's slices fit the grid
+          const int64_t bytes = steps[8 * k + 6], blk = steps[8 * k + 7];
+          if (steps[8 * k] >= 3) EXPECT(blk >= 16 && blk % 16 == 0 && (bytes + blk - 1) / blk <= nb);
+        }
+      }
+      EXPECT(steps[8 * (size_t)cap] == -1);
+      regOps++;
+    }
+    unsetenv("VCCL_REG_A2A_THRESHOLD");
+    EXPECT(vcclCommRegA2aStats(nullptr, nullptr, nullptr, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclCommSetRegA2aThreshold(nullptr, 4096, nullptr) == ncclInvalidArgument);
   }
   printf("host_api_check: %ld registration table operations, thresholds and zero-copy plans\n", regOps);
   printf("host_api_check: %ld all-to-all limits and plans\n", a2a);

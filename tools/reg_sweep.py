@@ -17,6 +17,13 @@ pair, the max over ranks.
 
     python tools/reg_sweep.py [--min-bytes N] [--max-bytes N] [--steps K] [--ranks 4,8]
 
+With --a2a the sweep is ncclAllToAll (u8) instead, on a communicator created
+with VCCL_REG_A2A_THRESHOLD set: 64 KiB - 64 MiB per pair (x4 steps), 10 timed
+calls after 2 warm-ups, the same three modes (fallback: the per-peer FIFOs
+behind one negotiation launch; off: vcclCommSetRegA2aThreshold 0), every row
+checked and its path confirmed by vcclCommRegA2aStats
+(profiles/reg_sweep/reg_a2a_sweep.jsonl).
+
 The parent spawns the rank processes (bench.py's launcher; ranks share a GPU
 when the box has fewer than ranks — then the rows are rehearsal rows: they show
 HBM traffic and phase count, and nothing about xGMI) and prints one JSON line
@@ -36,11 +43,12 @@ def arg(name, default):
     return default
 
 
+A2A = "--a2a" in sys.argv
 MIN_BYTES = int(arg("--min-bytes", 64 << 10))
-MAX_BYTES = int(arg("--max-bytes", 1 << 30))
-STEPS = max(5, int(arg("--steps", 20)))
+MAX_BYTES = int(arg("--max-bytes", 64 << 20 if A2A else 1 << 30))
+STEPS = max(5, int(arg("--steps", 10 if A2A else 20)))
 RANKS = [int(x) for x in arg("--ranks", "4,8").split(",")]
-WARMUP = 3
+WARMUP = 2 if A2A else 3
 THRESH = 32 << 10
 
 
@@ -59,7 +67,7 @@ def parent():
         env = dict(os.environ)
         env.pop("WORLD_SIZE", None)
         env["REG_SWEEP_CHILD"] = "1"
-        env["VCCL_REG_THRESHOLD"] = str(THRESH)
+        env["VCCL_REG_A2A_THRESHOLD" if A2A else "VCCL_REG_THRESHOLD"] = str(THRESH)
         env.setdefault("VCCL_SPIN_TIMEOUT_S", "30")
         plan = bench.rank_launch_plan(["--gpus", str(n)] + sys.argv[1:], env, script=os.path.abspath(__file__))
         rc = rc or bench._spawn_ranks(plan)
@@ -97,8 +105,8 @@ def child():
     comm = nccl.Comm.init_rank(n, nccl.unique_id_from_bytes(obj[0]), rank)
     sp = torch.cuda.current_stream().cuda_stream
     F32, U8 = nccl.ncclFloat32, nccl.ncclUint8
-    if comm.set_reg_threshold(THRESH) != THRESH:
-        raise SystemExit("this communicator has no buffer registry (VCCL_REG_THRESHOLD did not take effect)")
+    if (comm.set_reg_a2a_threshold(THRESH) if A2A else comm.set_reg_threshold(THRESH)) != THRESH:
+        raise SystemExit("this communicator has no buffer registry (the threshold did not take effect)")
 
     def row(**kw):
         t = torch.tensor([kw["min_us"], kw["median_us"]], dtype=torch.float64)
@@ -135,8 +143,39 @@ def child():
         want = torch.cat([((i + p) % 251).to(torch.uint8) for p in range(n)])
         return x, y, lambda: comm.all_gather(x.data_ptr(), y.data_ptr(), per, U8, sp), lambda: torch.equal(y, want)
 
+    def a2a_rows():
+        """--a2a: ncclAllToAll (u8) at MIN_BYTES .. MAX_BYTES per pair, the three
+        modes per row; only sendbuff is registered (nobody reads a peer's recvbuff)."""
+        good = True
+        for pair in sizes(MIN_BYTES, MAX_BYTES):
+            for mode in ("zero_copy", "fallback", "off"):
+                i = torch.arange(pair * n, device="cuda", dtype=torch.int32)
+                x = ((i + 7 * rank) % 251).to(torch.uint8)
+                y = torch.empty(pair * n, device="cuda", dtype=torch.uint8)
+                j = i % pair + rank * pair  # block p of my output is block `rank` of rank p's input
+                want = ((j + 7 * (i // pair)) % 251).to(torch.uint8)
+                del i, j
+                handle = comm.register(x.data_ptr(), x.numel()) if mode == "zero_copy" else None
+                comm.set_reg_a2a_threshold(0 if mode == "off" else THRESH)
+                torch.cuda.synchronize()
+                dist.barrier()  # every rank's registrations precede every import
+                base = comm.reg_a2a_stats()
+                y.zero_()
+                us = timed(lambda: comm.all_to_all(x.data_ptr(), y.data_ptr(), pair, U8, sp), torch.cuda.synchronize)
+                d = [a - b for a, b in zip(comm.reg_a2a_stats(), base)]
+                calls = WARMUP + STEPS
+                path_ok = d == {"zero_copy": [calls, calls, 0], "fallback": [calls, 0, calls], "off": [0, 0, 0]}[mode]
+                good &= row(coll="alltoall", ranks=n, pair_bytes=pair, mode=mode, min_us=us[0],
+                            median_us=us[len(us) // 2], steps=STEPS, shared_gpu=shared,
+                            ok=bool(torch.equal(y, want)) and path_ok and comm.async_error() == 0)
+                if handle is not None:
+                    comm.deregister(handle)
+                del x, y, want
+        comm.set_reg_a2a_threshold(THRESH)
+        return good
+
     good = True
-    for coll in ("allreduce", "reducescatter", "allgather"):
+    for coll in () if A2A else ("allreduce", "reducescatter", "allgather"):
         for nbytes in sizes(MIN_BYTES, MAX_BYTES):
             for mode in ("zero_copy", "fallback", "off"):
                 x, y, call, check = buffers(coll, nbytes)
@@ -157,7 +196,10 @@ def child():
                 for h in handles:
                     comm.deregister(h)
                 del x, y
-    comm.set_reg_threshold(THRESH)
+    if A2A:
+        good = a2a_rows()
+    else:
+        comm.set_reg_threshold(THRESH)
     torch.cuda.synchronize()
     dist.barrier()
     comm.destroy()

@@ -249,6 +249,45 @@ struct DirectRegWork {
 };
 static_assert(sizeof(DirectRegWork) <= 4096, "DirectRegWork must fit the kernel-argument budget");
 
+// Zero-copy all-to-all(v) over registered send buffers (direct_reg.hpp
+// direct_reg_alltoall).  The table is rotated to the rank like
+// A2aPeer's: entry k belongs to rank (rank + k) mod nRanks.  {entry, gen,
+// regOff} name my block for that peer inside my registrations (kRegNone: not
+// registered, or nothing to send) — the descriptor that travels to it; blkBytes
+// is the slice length of ITS block for me (plan.h direct_blk_elts of recvBytes
+// at element size 1): only the reader slices, so nothing but the grid has to
+// agree between ranks.
+constexpr int kRegA2aMaxCalls = 8;  // eligible all-to-alls per comm and group (one skip word each)
+struct RegA2aPeer {
+  const char* send;        // my block for this peer (the self copy reads entry 0's)
+  char* recv;              // where this peer's block lands
+  int64_t sendBytes, recvBytes;
+  int64_t blkBytes;        // slice b = bytes [b * blkBytes, (b + 1) * blkBytes) of the peer's block
+  uint64_t regOff;
+  uint32_t entry, gen;
+};
+// Device-resident per comm: the three counters (bumped by workgroup 0, so graph
+// replays count) and the verdict D of each eligible call of the current group,
+// which the FIFO launch behind it reads (p2p_types.hpp P2pBatch::skip).
+struct RegA2aDev {
+  RegStats stats;
+  uint32_t skip[kRegA2aMaxCalls];
+};
+struct DirectRegA2aWork {
+  DevComm* comm;
+  const DirectPeers* peers;
+  const RegPeers* reg;     // host-pinned, mapped
+  RegA2aDev* dev;
+  int rank, nRanks;
+  int nBlocks;             // workgroups, the same on every rank of the call
+  int skipIdx;             // this call's skip word, 0 .. kRegA2aMaxCalls - 1
+  int selfOk;              // my part of the vote: every block I send is registered, and (v-call) my largest pair
+                           // reaches the threshold
+  int pad;
+  RegA2aPeer peer[kDirectMaxRanks];
+};
+static_assert(sizeof(DirectRegA2aWork) <= 4096, "DirectRegA2aWork must fit the kernel-argument budget");
+
 __host__ __device__ inline DirectPart direct_part_of(const DirectWork& w) {
   return DirectPart{w.sendbuff, w.recvbuff, w.count, w.nChunks, w.root, w.chunkElts, w.blkElts, w.cbd,
                     w.arChunk};

@@ -119,6 +119,17 @@
 //                    A flag line's payload words are rewritten by their
 //                    writer's next negotiation only after the reader's
 //                    phase-1 flag of this one (R2), raised after it read them.
+//    zero-copy      (direct_reg.hpp direct_reg_alltoall, a launch of its own
+//    all-to-all      over registered send buffers) the same two shapes: one
+//                    position of negotiation — post (0) with a per-peer
+//                    descriptor, wait (0) on every peer, post (1) after it
+//                    (R1), wait (1) (R2) — and then EITHER one position that
+//                    touches no region (it pulls from the peers' send
+//                    buffers): post (0) after the last pull, wait (0), post (1)
+//                    after it (R1), wait (1) closing it (R2); OR nothing at all
+//                    (the call's bytes move in the FIFO launch behind it, which
+//                    uses no inbox and no direct flag).  Positions per launch:
+//                    2 or 1, the same on every rank since the verdict is.
 #pragma once
 #include "coll_types.hpp"
 #include "ll.hpp"

@@ -305,4 +305,130 @@ __device__ __forceinline__ void direct_reg_run(const DirectRegWork& rw, ZC zc, S
   epoch_retire(&w.comm->dEpoch, &w.comm->dDone, e);
 }
 
+// ---------------------------------------------------------------- all-to-all
+// Zero-copy all-to-all(v) (opt-in, VCCL_REG_A2A_THRESHOLD): a
+// launch of its own on the direct grid, ahead of the call's FIFO items in the
+// comm's p2p launch.  Only sendbuff has to be registered — nobody touches a
+// peer's recvbuff.  The step list is host/plan.cc reg_a2a_plan's, kept side by
+// side with this order:
+//   epoch k (negotiate)
+//     post (0, me, b) at every peer p with the descriptor of MY BLOCK FOR p in
+//          the flag's line (reg_post's layout, the send words only): {entry,
+//          generation, offset of the block inside my registration, its bytes};
+//          kRegNone when the block is empty or not registered;
+//     wait (0, *, b); ok_me = the host's part (every block I send is
+//          registered; a v-call: my largest pair reaches the threshold), and
+//          for every peer I receive from: its descriptor names an entry my
+//          import table holds at that generation, offset + bytes lies inside
+//          it, and bytes equals what I expect;
+//     post (1, me, b) carrying ok_me;  wait (1, *, b);  D = AND of the n votes.
+//   D = 1, epoch k + 1: for k = 1 .. n - 1 pull slice b of the block rank
+//     (me + k) mod n holds for me (sc0 sc1 loads) into my recvbuff, any
+//     alignment on either side (direct_rc's shifted path); the self block is a
+//     local copy; reg_close.  Nothing writes a peer's memory but flags.
+//   D = 0: nothing more — the FIFO items behind this launch move the call.
+// Workgroup 0 stores D into the call's skip word (p2p.hpp drops the call's FIFO
+// items on D = 1) and bumps the counters.  Epoch positions per launch: 2 or 1,
+// the same on every rank since D is; R1 / R2 of direct.hpp hold in both epochs
+// exactly as for the zero-copy AR / RS / AG (the header's list).
+__device__ __forceinline__ void reg_a2a_post(const DirectWork& w, const DirectPeers& P, int b, uint32_t e,
+                                             const RegA2aPeer* sh) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  const int k = threadIdx.x;
+  if (k >= 1 && k < w.nRanks) {
+    const int p = w.rank + k < w.nRanks ? w.rank + k : w.rank + k - w.nRanks;
+    char* line = P.flags[p] + direct_flag_off(0, 0, w.rank, b);
+    reg_st64(line, 8, sh[k].regOff);
+    reg_st64(line, 24, (uint64_t)sh[k].sendBytes);
+    reg_st32(line, 40, sh[k].entry);
+    reg_st32(line, 44, sh[k].gen);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // payload, then flag
+    if (w.comm->useFences) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    __hip_atomic_store((uint32_t*)line, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+__device__ __forceinline__ void direct_reg_alltoall(const DirectRegA2aWork& w) {
+  using Fn = FnCopy<uint8_t>;
+  const Fn fn(0);
+  __shared__ RegA2aPeer sh[kDirectMaxRanks];   // rotated: entry k = rank (me + k) mod n
+  __shared__ const char* shSrc[kDirectMaxRanks];
+  __shared__ int shOk[kDirectMaxRanks];
+  __shared__ int shFail;
+#pragma unroll
+  for (int i = 0; i < kDirectMaxRanks; i++)
+    if ((int)threadIdx.x == i) sh[i] = w.peer[i];
+  if (threadIdx.x == 0) shFail = 0;
+  __syncthreads();
+  // what direct_wait / direct_post / reg_post read of a DirectWork
+  DirectWork dw{};
+  dw.comm = w.comm;
+  dw.nRanks = w.nRanks;
+  dw.rank = w.rank;
+  const DirectPeers& P = *w.peers;
+  const int n = w.nRanks, me = w.rank, b = blockIdx.x;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const char* myFlags = P.flags[me];
+  uint32_t e = epoch_after(__hip_atomic_load(&w.comm->dEpoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  reg_a2a_post(dw, P, b, e, sh);
+  const bool live = direct_wait(dw, myFlags, 0, 0, b, e, &shFail);
+  if (tid < n) {  // thread k: rank (me + k) mod n
+    const int k = tid, q = me + k < n ? me + k : me + k - n;
+    int ok = 0;
+    const char* s = nullptr;
+    if (k == 0) {
+      ok = w.selfOk;
+    } else if (live) {
+      const uint64_t need = (uint64_t)sh[k].recvBytes;
+      if (need == 0) {
+        ok = 1;
+      } else {
+        const char* line = myFlags + direct_flag_off(0, 0, q, b);
+        const uint64_t bytes = reg_ld64(line, 24);
+        s = reg_resolve(w.reg, q, reg_ld32(line, 40), reg_ld32(line, 44), reg_ld64(line, 8), bytes, need);
+        ok = s != nullptr && bytes == need;
+      }
+    }
+    shSrc[k] = s;
+    shOk[k] = ok;
+  }
+  __syncthreads();
+  uint32_t okMe = 1;
+  for (int k = 0; k < n; k++) okMe &= (uint32_t)shOk[k];
+  reg_post(dw, P, 1, b, e, nullptr, okMe);
+  bool D = direct_wait(dw, myFlags, 1, 0, b, e, &shFail) && okMe;
+  if (D)
+    for (int q = 0; q < n; q++)
+      if (q != me) D = D && reg_ld32(myFlags + direct_flag_off(1, 0, q, b), 4) != 0;
+  __syncthreads();  // the verdict reads precede any later post
+  if (b == 0 && tid == 0) {
+    w.dev->skip[w.skipIdx] = D ? 1u : 0u;
+    atomicAdd(&w.dev->stats.launches, 1ull);
+    atomicAdd(D ? &w.dev->stats.zeroCopy : &w.dev->stats.fallback, 1ull);
+  }
+  if (D) {
+    e = epoch_after(e);
+    for (int k = 1; k < n; k++) {  // rotated: every rank starts at its own successor
+      const int64_t lo = (int64_t)b * sh[k].blkBytes;
+      const int64_t hi = lo + sh[k].blkBytes < sh[k].recvBytes ? lo + sh[k].blkBytes : sh[k].recvBytes;
+      if (hi <= lo) continue;
+      const char* s[kDirectMaxRanks] = {shSrc[k] + lo};
+      char* d[kDirectMaxRanks] = {sh[k].recv + lo};
+      direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, hi - lo, tid, nt);
+    }
+    if (sh[0].send != sh[0].recv) {  // the self block (nothing when already in place)
+      const int64_t lo = (int64_t)b * sh[0].blkBytes;
+      const int64_t hi = lo + sh[0].blkBytes < sh[0].recvBytes ? lo + sh[0].blkBytes : sh[0].recvBytes;
+      if (hi > lo) {
+        const char* s[kDirectMaxRanks] = {sh[0].send + lo};
+        char* d[kDirectMaxRanks] = {sh[0].recv + lo};
+        direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, hi - lo, tid, nt);
+      }
+    }
+    reg_close(dw, P, b, e, &shFail);
+  }
+  epoch_retire(&w.comm->dEpoch, &w.comm->dDone, e);
+}
+
 }  // namespace vccl

@@ -1,6 +1,7 @@
 // Zero-copy direct kernels over registered buffers (direct_reg.hpp) for ONE
 // kernel element type (VCCL_KT) and ONE half (VCCL_REG_PART: 0 the all-reduce,
-// 1 the reduce-scatter and, in the K_U8 unit, the byte-copy all-gather) —
+// 1 the reduce-scatter and, in the K_U8 unit, the byte-copy all-gather and the
+// zero-copy all-to-all(v), which has no staged part: its fallback is the FIFOs) —
 // separate objects, built in parallel with the collective kernels of
 // ring_kernels.hip.  One call per launch; the staged part of the same
 // collective is the fallback the negotiation may pick.
@@ -71,6 +72,13 @@ hipError_t direct_reg_launch_rsag<VCCL_KT>(int coll, int devOp, const DirectRegW
   });
   return err;
 }
+
+#if VCCL_KT == 0  // K_U8: the byte-copy object also holds the zero-copy all-to-all(v)
+__global__ __launch_bounds__(kDirectThreads) void k_direct_reg_alltoall(DirectRegA2aWork w) { direct_reg_alltoall(w); }
+hipError_t direct_reg_a2a_launch(const DirectRegA2aWork& w, hipStream_t stream, hipEvent_t stop) {
+  return launch_k(k_direct_reg_alltoall, dim3(w.nBlocks), dim3(kDirectThreads), stream, stop, w);
+}
+#endif
 #endif
 
 }  // namespace vccl

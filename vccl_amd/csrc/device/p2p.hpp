@@ -79,6 +79,12 @@ __device__ __forceinline__ void p2p_run(const P2pBatch& b) {
   for (int i = 0; i < b.nWorks; i++) {
     const P2pWork& w = b.works[i];
     if (w.wg != wg) continue;
+    // An item of a zero-copy all-to-all that settled on D = 1 (P2pBatch::skip):
+    // dropped before its connection's counter is touched.  The word was
+    // written by an earlier launch and is the same on both ends of the message;
+    // the branch is uniform, and never taken with a null pointer or index 0.
+    if (w.skip > 0 && b.skip && __hip_atomic_load(b.skip + (w.skip - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+      continue;
     if (w.kind == kP2pCopy) {
       // self traffic: a plain copy, no connection
       RCArgs a;

@@ -54,7 +54,8 @@ struct P2pWork {
   int16_t conn;  // peer * parts + part (unused by a copy)
   int16_t wg;    // the workgroup that runs it
   int8_t kind;   // kP2pSend / kP2pRecv / kP2pCopy
-  int8_t pad[3];
+  int8_t skip;   // 1 .. 8: dropped when P2pBatch::skip[skip - 1] == 1; 0: never
+  int8_t pad[2];
 };
 static_assert(sizeof(P2pWork) == 32, "work item layout");
 
@@ -66,6 +67,12 @@ constexpr int kP2pMaxWorks = 120;
 struct P2pBatch {
   DevComm* comm;     // device-resident
   P2pConn* conns;    // device-resident, nRanks * parts entries (null at one rank)
+  // The verdicts of the group's zero-copy all-to-alls (device-resident, written
+  // by the launches ahead of this one on the stream; direct_reg.hpp
+  // direct_reg_alltoall): word i == 1 means call i + 1 moved its bytes itself
+  // and its items here are dropped — on every rank alike, so both ends drop the
+  // same matched messages.  Null: nothing is ever dropped.
+  const uint32_t* skip;
   int nWorks;
   int nConns;
   int stepBytes;

@@ -84,6 +84,11 @@ inline hipError_t direct_reg_launch(int coll, int devOp, const DirectRegWork& rw
                                 : direct_reg_launch_rsag<K>(coll, devOp, rw, stream, stop);
 }
 
+// Zero-copy all-to-all(v) over registered send buffers (direct_reg.hpp
+// direct_reg_alltoall): a byte copy, built once in the K_U8 unit of
+// direct_reg_kernels.hip (part 1); w.nBlocks workgroups of kDirectThreads threads.
+hipError_t direct_reg_a2a_launch(const DirectRegA2aWork& w, hipStream_t stream, hipEvent_t stop);
+
 // One-hop direct all-to-all(v) (direct.hpp direct_alltoall): a byte copy,
 // built once in the K_U8 unit; w.nBlocks workgroups of kDirectThreads threads.
 hipError_t direct_a2a_launch(const DirectA2aWork& w, hipStream_t stream, hipEvent_t stop);

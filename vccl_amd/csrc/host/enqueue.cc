@@ -199,9 +199,10 @@ static A2aRow a2a_row(const size_t* counts, const size_t* displs, size_t count, 
 }
 
 // The all-to-all of a comm whose one-hop LL or direct all-to-all is on
-// (llA2aMaxBytes > 0 || directA2aMaxBytes > 0): ONE queued task (kTaskA2a) —
-// launch_group splits its pairs between the LL launch, the direct launch and
-// the p2p launch.  The per-pair checks of the expansion below, in
+// (llA2aMaxBytes > 0 || directA2aMaxBytes > 0) or whose zero-copy all-to-all is
+// (regA2aMaxBytes > 0): ONE queued task (kTaskA2a) — launch_group splits its
+// pairs between the LL launch, the direct launch and the p2p launch, or gives
+// an eligible call to the zero-copy launch with the p2p launch as its fallback.  The per-pair checks of the expansion below, in
 // its order; the rows live in tl_a2a until the group has launched.
 static thread_local std::deque<A2aArgs> tl_a2a;
 static ncclResult_t all_to_all_task(const char* name, const void* sendbuff, const size_t* sendcounts,
@@ -252,7 +253,8 @@ static ncclResult_t all_to_all(const char* name, const void* sendbuff, const siz
   const size_t esz = (size_t)type_size(dt);
   const int n = comm->nRanks;
   static_assert(kDirectMaxRanks <= kOrderMaxRanks, "A2aArgs holds kOrderMaxRanks rows");
-  if ((comm->llA2aMaxBytes > 0 || comm->directA2aMaxBytes > 0) && n <= kOrderMaxRanks)
+  // ... or whose zero-copy all-to-all is (regA2aMaxBytes > 0, at most kDirectMaxRanks ranks)
+  if ((comm->llA2aMaxBytes > 0 || comm->directA2aMaxBytes > 0 || comm->regA2aMaxBytes > 0) && n <= kOrderMaxRanks)
     return all_to_all_task(name, sendbuff, sendcounts, sdispls, recvbuff, recvcounts, rdispls, count, dt, comm, stream);
   ncclGroupStart();
   for (int p = 0; p < n && r == ncclSuccess; p++) {

@@ -531,6 +531,89 @@ VCCL_EXPORT ncclResult_t vcclCommSetRegThreshold(ncclComm_t comm, int64_t bytes,
   return ncclSuccess;
 }
 
+// ------------------------------------------- all-to-all over registered buffers
+// A comm's VCCL_REG_A2A_THRESHOLD as it takes effect (the arithmetic).
+VCCL_EXPORT ncclResult_t vcclRegA2aMax(int64_t threshold, int inbox, int directAllowed, int anyNet, int nRanks,
+                                       int hasP2p, int allRegistries, int64_t* effective) {
+  if (!effective || nRanks < 1) return ncclInvalidArgument;
+  if (threshold < 0) threshold = param_int("REG_A2A_THRESHOLD", 0);
+  *effective = (int64_t)reg_a2a_max(threshold, inbox != 0, directAllowed != 0, anyNet != 0, nRanks, hasP2p != 0,
+                                    allRegistries != 0);
+  return ncclSuccess;
+}
+
+VCCL_EXPORT ncclResult_t vcclRegA2aEligible(int uniform, size_t pairBytes, int64_t effective, int index,
+                                            int* eligible) {
+  if (!eligible || effective < 0 || index < 0 || pairBytes > (size_t)1 << 60) return ncclInvalidArgument;
+  *eligible = reg_a2a_eligible(uniform != 0, (int64_t)pairBytes, (uint64_t)effective, index);
+  return ncclSuccess;
+}
+
+// The ordered steps of one zero-copy all-to-all launch as `rank` runs it.
+VCCL_EXPORT ncclResult_t vcclRegA2aPlan(int nRanks, int rank, const size_t* sendBytes, const size_t* sendOff,
+                                        const size_t* recvOff, int uniform, int minCTAs, int maxCTAs,
+                                        int directMaxBlocks, int* nBlocks, int cap, int* nSteps, int64_t* steps) {
+  if (nRanks < 2 || nRanks > kDirectMaxRanks || rank < 0 || rank >= nRanks || !sendBytes || !sendOff || !recvOff ||
+      minCTAs < 0 || maxCTAs < 1 || directMaxBlocks < 1 || !nBlocks || !nSteps || cap < 0 || (cap && !steps))
+    return ncclInvalidArgument;
+  const int n = nRanks;
+  std::vector<int64_t> sb((size_t)n * n), so((size_t)n * n), ro(n);
+  for (int i = 0; i < n * n; i++) {
+    if (sendBytes[i] > (size_t)1 << 56 || sendOff[i] > (size_t)1 << 56) return ncclInvalidArgument;
+    if (uniform && sendBytes[i] != sendBytes[0]) return ncclInvalidArgument;
+    sb[i] = (int64_t)sendBytes[i];
+    so[i] = (int64_t)sendOff[i];
+  }
+  for (int p = 0; p < n; p++) {
+    if (recvOff[p] > (size_t)1 << 56) return ncclInvalidArgument;
+    ro[p] = (int64_t)recvOff[p];
+  }
+  RegA2aPlanOut out;
+  NCCLCHECK(reg_a2a_plan(n, rank, sb.data(), so.data(), ro.data(), uniform != 0, minCTAs, maxCTAs, directMaxBlocks,
+                         &out));
+  *nBlocks = out.nBlocks;
+  *nSteps = (int)out.steps.size();
+  if (*nSteps > cap) return ncclInvalidArgument;
+  for (size_t k = 0; k < out.steps.size(); k++) {
+    const RegA2aStep& d = out.steps[k];
+    const int64_t v[8] = {d.kind, d.epoch, d.phase, d.peer, d.peerOff, d.ownOff, d.bytes, d.blkBytes};
+    for (int j = 0; j < 8; j++) steps[8 * k + j] = v[j];
+  }
+  return ncclSuccess;
+}
+
+// Synchronises the device, then reads the three device-resident counters.
+VCCL_EXPORT ncclResult_t vcclCommRegA2aStats(ncclComm_t comm, unsigned long long* launches,
+                                             unsigned long long* zeroCopy, unsigned long long* fallback) {
+  NCCLCHECK(comm_check(comm, "vcclCommRegA2aStats"));
+  unsigned long long w[3] = {0, 0, 0};
+  if (comm->reg && comm->reg->a2aDev) {
+    DeviceGuard dev(comm->device);
+    HIPCHECK(dev.status);
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpy(w, &comm->reg->a2aDev->stats, sizeof(w), hipMemcpyDeviceToHost));
+  }
+  if (launches) *launches = w[0];
+  if (zeroCopy) *zeroCopy = w[1];
+  if (fallback) *fallback = w[2];
+  return ncclSuccess;
+}
+
+// A tuning / measurement knob: every rank must call it alike, outside a group.
+// A comm initialised without a registry has none to switch on: 0 stays 0.
+VCCL_EXPORT ncclResult_t vcclCommSetRegA2aThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective) {
+  NCCLCHECK(comm_check(comm, "vcclCommSetRegA2aThreshold"));
+  if (bytes < 0) return ncclInvalidArgument;
+  if (comm->reg) {  // a registry exists only where every rank has one and no peer is behind the net proxy
+    const size_t eff = reg_a2a_max_of(*comm, bytes, comm->nRanks, false, comm->dPeers != nullptr,
+                                      comm->p2pConns != nullptr, true);
+    if (eff > 0) NCCLCHECK(reg_a2a_alloc(comm));
+    comm->regA2aMaxBytes = eff;
+  }
+  if (effective) *effective = (int64_t)comm->regA2aMaxBytes;
+  return ncclSuccess;
+}
+
 VCCL_EXPORT ncclResult_t vcclCommSetAlgo(ncclComm_t comm, int algo) {
   NCCLCHECK(comm_check(comm, "vcclCommSetAlgo"));
   const int a = internal_algo(algo);

@@ -767,11 +767,15 @@ static ncclResult_t launch_p2p(const std::vector<Task>& ts) {
     if (hipEventRecord(comm->joinEvent, s) != hipSuccess || hipStreamWaitEvent(s0, comm->joinEvent, 0) != hipSuccess)
       r = ncclUnhandledCudaError;
   }
+  // the verdicts of the zero-copy all-to-alls launched ahead of this (launch_comm_p2p)
+  const bool anySkip = std::any_of(ts.begin(), ts.end(), [](const Task& t) { return t.skip > 0; });
+  if (anySkip && (!comm->reg || !comm->reg->a2aDev)) return ncclInternalError;
   bool bound = false;
   for (size_t k = 0; k < plan.items.size() && r == ncclSuccess;) {
     P2pBatch b{};
     b.comm = comm->devComm;
     b.conns = comm->p2pConns;
+    b.skip = anySkip ? comm->reg->a2aDev->skip : nullptr;
     b.nConns = conns ? n * geo.parts : 0;
     b.stepBytes = (int)geo.stepBytes;
     b.nSendWgs = plan.nWgs;
@@ -785,6 +789,7 @@ static ncclResult_t launch_p2p(const std::vector<Task>& ts) {
       w.wg = (int16_t)it.wg;
       w.conn = (int16_t)(it.peer * geo.parts + it.part);
       w.bytes = it.bytes;
+      w.skip = (int8_t)ts[it.call].skip;  // a copy: its send's, which is its recv's
       if (it.kind != kP2pRecv) w.a = (const char*)ts[it.call].sendbuff + it.offset;
       if (it.kind != kP2pSend) w.b = (char*)ts[it.kind == kP2pCopy ? it.call2 : it.call].recvbuff + it.offset;
     }
@@ -909,10 +914,69 @@ static ncclResult_t launch_direct_a2a(const Task& t, const A2aPlanOut& plan) {
   return stream_mark(comm, t.stream, cs);
 }
 
+// The zero-copy launch of one eligible ncclAllToAll(v) (direct_reg.hpp
+// direct_reg_alltoall; plan.cc reg_a2a_plan is its step list) on the call's
+// stream, ordered like launch_direct_a2a, the import table brought up to date
+// first as launch_direct_reg does.  The grid is comm-wide (reg_a2a_blocks); the
+// slices are the reader's own (reg_a2a_blk per receive block).  The descriptors
+// are this rank's registrations of each block it sends, as of now.  selfPaired:
+// the call's self send and self recv are each other's match in the group's
+// sweep order — rank-local, so it enters the vote, not the eligibility.
+static ncclResult_t launch_reg_a2a(const Task& t, int skipIdx, bool selfPaired) {
+  ncclComm* comm = t.comm;
+  const int n = comm->nRanks, me = comm->rank;
+  const A2aArgs& a = *t.a2a;
+  if (n > kDirectMaxRanks || !comm->dPeers || !comm->reg || !comm->reg->a2aDev || skipIdx < 0 ||
+      skipIdx >= kRegA2aMaxCalls)
+    return ncclInternalError;
+  DeviceGuard dev(comm->device);
+  HIPCHECK(dev.status);
+  CaptureState cs{false, 0};
+  NCCLCHECK(stream_order(comm, t.stream, &cs));
+  NCCLCHECK(reg_refresh(comm, cs.active));
+  DirectRegA2aWork w{};
+  w.comm = comm->devComm;
+  w.peers = comm->dPeers;
+  w.reg = comm->reg->tabDev;
+  w.dev = comm->reg->a2aDev;
+  w.rank = me;
+  w.nRanks = n;
+  w.skipIdx = skipIdx;
+  w.nBlocks = reg_a2a_blocks(a.uniform, a.sendBytes[0], comm->minCTAs, comm->maxCTAs, comm->directMaxBlocks);
+  if (w.nBlocks < 1 || w.nBlocks > kDirectMaxBlocks) return ncclInternalError;
+  bool ok = selfPaired && a.sendBytes[me] == a.recvBytes[me];
+  for (int k = 0; k < n; k++) {
+    const int p = (me + k) % n;
+    RegA2aPeer& e = w.peer[k];
+    e.send = t.sendbuff ? (const char*)t.sendbuff + a.sendOff[p] : nullptr;
+    e.recv = t.recvbuff ? (char*)t.recvbuff + a.recvOff[p] : nullptr;
+    e.sendBytes = a.sendBytes[p];
+    e.recvBytes = a.recvBytes[p];
+    e.blkBytes = reg_a2a_blk(e.recvBytes, comm->minCTAs, comm->maxCTAs, comm->directMaxBlocks);
+    if ((e.recvBytes + e.blkBytes - 1) / e.blkBytes > w.nBlocks) return ncclInternalError;
+    e.entry = kRegNone;
+    if (k > 0 && e.sendBytes > 0) {  // my block for p as p will address it
+      reg_describe(comm, e.send, (uint64_t)e.sendBytes, &e.entry, &e.gen, &e.regOff);
+      ok = ok && e.entry != kRegNone;
+    }
+  }
+  w.selfOk = ok && reg_a2a_size_vote(n, me, a.sendBytes, a.recvBytes, a.uniform, comm->regA2aMaxBytes);
+  const hipError_t e = direct_reg_a2a_launch(w, t.stream, stop_event(comm, cs));
+  if (e != hipSuccess) {
+    VWARN("zero-copy all-to-all kernel launch failed: %s", hipGetErrorString(e));
+    return ncclUnhandledCudaError;
+  }
+  return stream_mark(comm, t.stream, cs);
+}
+
 // One comm's sends, recvs and all-to-all tasks of a group (call order): each
 // all-to-all's LL launch, then its direct launch, in call order, then the one
 // p2p launch with the plain sends and recvs and the all-to-alls' residual
-// pairs, in call order per peer — so matching by sweep is what it was.
+// pairs, in call order per peer — so matching by sweep is what it was.  An
+// all-to-all eligible for the zero-copy path (reg_a2a_eligible) launches that
+// kernel instead of the LL and direct ones, and ALL its pairs, the self copy
+// included, join the p2p launch predicated on its verdict: the host cannot
+// know whether the kernel moved them.
 static ncclResult_t launch_comm_p2p(const std::vector<Task>& mine) {
   if (std::none_of(mine.begin(), mine.end(), [](const Task& t) { return t.coll == kTaskA2a; }))
     return launch_p2p(mine);
@@ -924,12 +988,35 @@ static ncclResult_t launch_comm_p2p(const std::vector<Task>& mine) {
     return ncclInvalidUsage;
   }
   std::vector<Task> fifo;
+  int nReg = 0;                        // eligible all-to-alls so far: collective, so the same on every rank
+  size_t selfSends = 0, selfRecvs = 0;  // to self, so far (the sweep a self pair is matched in)
   for (const Task& t : mine) {
     if (t.coll != kTaskA2a) {
+      if (t.root == me) (t.coll == kTaskSend ? selfSends : selfRecvs)++;
       fifo.push_back(t);
       continue;
     }
     const A2aArgs& a = *t.a2a;
+    const bool selfPaired = selfSends++ == selfRecvs++;
+    auto expand = [&](int p, bool send, int skip) {  // the API's own expansion of pair p
+      return send ? Task{.coll = kTaskSend, .sendbuff = t.sendbuff ? (const char*)t.sendbuff + a.sendOff[p] : nullptr,
+                         .recvbuff = nullptr, .count = (size_t)a.sendBytes[p], .datatype = ncclUint8,
+                         .devOp = t.devOp, .root = p, .comm = comm, .stream = t.stream, .skip = skip}
+                  : Task{.coll = kTaskRecv, .sendbuff = nullptr,
+                         .recvbuff = t.recvbuff ? (char*)t.recvbuff + a.recvOff[p] : nullptr,
+                         .count = (size_t)a.recvBytes[p], .datatype = ncclUint8, .devOp = t.devOp, .root = p,
+                         .comm = comm, .stream = t.stream, .skip = skip};
+    };
+    if (comm->reg && reg_a2a_eligible(a.uniform, a.sendBytes[0], comm->regA2aMaxBytes, nReg)) {
+      // opCount: launch_p2p counts the 2 n expanded calls, as the FIFO expansion does
+      NCCLCHECK(launch_reg_a2a(t, nReg, selfPaired));
+      nReg++;
+      for (int p = 0; p < n; p++) {
+        fifo.push_back(expand(p, true, nReg));
+        fifo.push_back(expand(p, false, nReg));
+      }
+      continue;
+    }
     A2aPlanOut plan;
     if (a2a_plan(n, me, a.sendBytes, a.recvBytes, a.uniform, comm->llA2aMaxBytes, comm->directA2aMaxBytes,
                  comm->llLines, comm->minCTAs, comm->maxCTAs, comm->directMaxBlocks, &plan) != ncclSuccess)
@@ -950,14 +1037,8 @@ static ncclResult_t launch_comm_p2p(const std::vector<Task>& mine) {
       NCCLCHECK(launch_direct_a2a(t, plan));
     }
     for (int p = 0; p < n; p++) {  // the API's own expansion order: send p, recv p
-      Task s{.coll = kTaskSend, .sendbuff = t.sendbuff ? (const char*)t.sendbuff + a.sendOff[p] : nullptr,
-             .recvbuff = nullptr, .count = (size_t)a.sendBytes[p], .datatype = ncclUint8, .devOp = t.devOp,
-             .root = p, .comm = comm, .stream = t.stream};
-      Task r{.coll = kTaskRecv, .sendbuff = nullptr,
-             .recvbuff = t.recvbuff ? (char*)t.recvbuff + a.recvOff[p] : nullptr, .count = (size_t)a.recvBytes[p],
-             .datatype = ncclUint8, .devOp = t.devOp, .root = p, .comm = comm, .stream = t.stream};
-      if (plan.sendPath[p] == kA2aFifo) fifo.push_back(s);
-      if (plan.recvPath[p] == kA2aFifo) fifo.push_back(r);
+      if (plan.sendPath[p] == kA2aFifo) fifo.push_back(expand(p, true, 0));
+      if (plan.recvPath[p] == kA2aFifo) fifo.push_back(expand(p, false, 0));
     }
   }
   return fifo.empty() ? ncclSuccess : launch_p2p(fifo);

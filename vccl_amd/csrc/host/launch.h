@@ -14,7 +14,9 @@ namespace vccl {
 enum { kTaskSend = 5, kTaskRecv = 6 };
 inline bool is_p2p(int coll) { return coll == kTaskSend || coll == kTaskRecv; }
 // ... and of an ncclAllToAll(v) on a comm whose one-hop LL or direct all-to-all
-// is on (llA2aMaxBytes > 0 || directA2aMaxBytes > 0): one task; launch_group
+// is on (llA2aMaxBytes > 0 || directA2aMaxBytes > 0) or whose zero-copy
+// all-to-all is (regA2aMaxBytes > 0, which pre-empts the other two for the
+// calls plan.h reg_a2a_eligible names): one task; launch_group
 // gives its pairs within the limits to one LL launch and one direct launch
 // (plan.h a2a_plan) and turns the rest into sends and recvs of the
 // group's p2p launch.  With both paths off the API expands the call into sends
@@ -48,6 +50,10 @@ struct Task {
   // The collectives of this call's comm in its group (launch_group_colls); 0
   // outside a group.  More than one: not eligible for the zero-copy path.
   int groupColls;
+  // A send / recv expanded from an all-to-all that launched the zero-copy
+  // kernel (launch_comm_p2p): 1 .. kRegA2aMaxCalls, the skip word its FIFO items
+  // are predicated on (device/p2p_types.hpp P2pWork::skip); 0: never dropped.
+  int skip;
 };
 
 // The one place that reads a comm into the planner's thresholds.

@@ -619,6 +619,71 @@ ncclResult_t reg_plan(int coll, int nRanks, int rank, int64_t count, int64_t elt
   return ncclSuccess;
 }
 
+// ------------------------------------------- all-to-all over registered buffers
+uint64_t reg_a2a_max(int64_t threshold, bool inbox, bool directAllowed, bool anyNet, int nRanks, bool hasP2p,
+                     bool allRegistries) {
+  if (!hasP2p || !allRegistries) return 0;
+  return reg_max(threshold, inbox, directAllowed, anyNet, nRanks);
+}
+bool reg_a2a_eligible(bool uniform, int64_t pairBytes, uint64_t effective, int index) {
+  if (effective == 0 || index < 0 || index >= kRegA2aMaxCalls) return false;
+  return !uniform || (uint64_t)pairBytes >= effective;
+}
+bool reg_a2a_size_vote(int nRanks, int rank, const int64_t* sendBytes, const int64_t* recvBytes, bool uniform,
+                       uint64_t effective) {
+  if (uniform) return true;
+  int64_t largest = 0;
+  for (int p = 0; p < nRanks; p++)
+    if (p != rank) largest = std::max({largest, sendBytes[p], recvBytes[p]});
+  return (uint64_t)largest >= effective;
+}
+int reg_a2a_blocks(bool uniform, int64_t pairBytes, int minCTAs, int maxCTAs, int directMaxBlocks) {
+  if (uniform) {
+    const int64_t blk = reg_a2a_blk(pairBytes, minCTAs, maxCTAs, directMaxBlocks);
+    return (int)std::max<int64_t>(1, (pairBytes + blk - 1) / blk);
+  }
+  // direct_blk_elts' block count for a block of any length
+  const int64_t nb = std::max<int64_t>(std::min<int64_t>(kDirectMaxBlocks, maxCTAs), minCTAs);
+  return (int)std::max<int64_t>(1, std::min<int64_t>({nb, (int64_t)directMaxBlocks, (int64_t)kDirectMaxBlocks}));
+}
+int64_t reg_a2a_blk(int64_t bytes, int minCTAs, int maxCTAs, int directMaxBlocks) {
+  return std::max<int64_t>(16, direct_blk_elts(bytes, 1, minCTAs, maxCTAs, directMaxBlocks));
+}
+
+// The steps below are direct_reg_alltoall's order (device/direct_reg.hpp), rank
+// by rank; the peer loops run in the direct kernels' rotation, (rank + k) mod n.
+ncclResult_t reg_a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const int64_t* sendOff,
+                          const int64_t* recvOff, bool uniform, int minCTAs, int maxCTAs, int directMaxBlocks,
+                          RegA2aPlanOut* out) {
+  const int n = nRanks;
+  if (n < 2 || n > kDirectMaxRanks || rank < 0 || rank >= n) return ncclInvalidArgument;
+  out->nBlocks = reg_a2a_blocks(uniform, sendBytes[0], minCTAs, maxCTAs, directMaxBlocks);
+  auto& st = out->steps;
+  st.clear();
+  auto post = [&](int epoch, int phase) { st.push_back(RegA2aStep{kAStepPost, epoch, phase, 0, 0, 0, 0, 0}); };
+  auto wait = [&](int epoch, int phase) {
+    for (int k = 1; k < n; k++) st.push_back(RegA2aStep{kAStepWait, epoch, phase, (rank + k) % n, 0, 0, 0, 0});
+  };
+  post(0, 0);  // the descriptor of my block for each peer, "my input is ready"
+  wait(0, 0);
+  st.push_back(RegA2aStep{kAStepVote, 0, 0, 0, 0, 0, 0, 0});
+  post(0, 1);
+  wait(0, 1);
+  for (int k = 1; k <= n; k++) {  // the peers in rotation, then the self block
+    const int p = (rank + k) % n;
+    const int64_t bytes = sendBytes[(size_t)p * n + rank];
+    const int64_t blk = reg_a2a_blk(bytes, minCTAs, maxCTAs, directMaxBlocks);
+    if ((bytes + blk - 1) / blk > out->nBlocks) return ncclInternalError;
+    st.push_back(RegA2aStep{p == rank ? kAStepSelf : kAStepPull, 1, 0, p, sendOff[(size_t)p * n + rank], recvOff[p],
+                            bytes, blk});
+  }
+  post(1, 0);  // "I have finished reading you"
+  wait(1, 0);
+  post(1, 1);  // the closing round (reuse rule R2, direct.hpp)
+  wait(1, 1);
+  return ncclSuccess;
+}
+
 // ---------------------------------------------------------------- all-to-all
 uint64_t ll_a2a_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks, bool hasP2p) {
   if (threshold <= 0 || llSlotBytes <= 0 || !llAllowed || anyNet || nRanks < 2 || nRanks > kOrderMaxRanks || !hasP2p)

@@ -240,6 +240,58 @@ struct RegPlanOut {
 };
 ncclResult_t reg_plan(int coll, int nRanks, int rank, int64_t count, int64_t eltSize, int nBlocks, RegPlanOut* out);
 
+// ------------------------------------------- all-to-all over registered buffers
+// The zero-copy ncclAllToAll(v) (device/direct_reg.hpp direct_reg_alltoall,
+// DESIGN.md §4.15): the host's half.
+// A comm's VCCL_REG_A2A_THRESHOLD (bytes per ordered pair) as it takes effect:
+// 0 wherever reg_max gives 0, on a comm without point-to-point connections (the
+// fallback needs the FIFOs), or when any rank failed to create its registry.
+uint64_t reg_a2a_max(int64_t threshold, bool inbox, bool directAllowed, bool anyNet, int nRanks, bool hasP2p,
+                     bool allRegistries);
+// From comm-wide values only, so every rank launches the negotiating kernel for
+// the same calls: the index-th (from 0) all-to-all of its comm in its group,
+// fewer than kRegA2aMaxCalls before it; a uniform call of pairBytes >=
+// effective; EVERY v-call (a rank knows only its row and column: size enters as
+// part of the rank's vote).  An eligible call pre-empts a2a_plan: none of its
+// pairs go to the LL or direct all-to-all launch.
+bool reg_a2a_eligible(bool uniform, int64_t pairBytes, uint64_t effective, int index);
+// A v-call rank's part of the vote: its largest pair with another rank, send or
+// receive, reaches the threshold (a uniform call passed it to be eligible).
+bool reg_a2a_size_vote(int nRanks, int rank, const int64_t* sendBytes, const int64_t* recvBytes, bool uniform,
+                       uint64_t effective);
+// The grid, the same on every rank: a uniform call's ceil(B / direct_blk_elts(B,
+// 1, ...)); a v-call's largest grid under the CTA bounds and co-residency caps.
+int reg_a2a_blocks(bool uniform, int64_t pairBytes, int minCTAs, int maxCTAs, int directMaxBlocks);
+// The slice length of one block of `bytes` bytes: direct_blk_elts at element
+// size 1 (at least 16), whose ceil(bytes / that) slices never exceed the grid.
+// Chosen by the reader alone: the sender takes no part in a pull.
+int64_t reg_a2a_blk(int64_t bytes, int minCTAs, int maxCTAs, int directMaxBlocks);
+// One launch as `rank` runs it.  sendBytes / sendOff: the whole n x n matrices,
+// row r rank r's (bytes and byte offsets in r's sendbuff, column p = for peer
+// p); recvOff: this rank's n receive offsets.  Steps, in the kernel's order:
+//   kAStepPost  {epoch, phase}: my flag at every peer (epoch 0 phase 0 carries
+//               the per-peer descriptor, phase 1 the vote)
+//   kAStepWait  {epoch, phase, peer}
+//   kAStepVote  {epoch 0}: ok_me from the descriptors just read
+//   kAStepPull  {epoch 1, peer, peerOff = the sender's displacement for me,
+//               ownOff, bytes, blkBytes}: workgroup b moves bytes [b * blkBytes,
+//               (b + 1) * blkBytes) of it; peers in rotation (rank + k) mod n
+//   kAStepSelf  {epoch 1, peerOff (in my sendbuff), ownOff, bytes, blkBytes}
+// then the closing rounds (post / wait (1, 0), post / wait (1, 1)).  With D = 0
+// the launch ends after epoch 0: the list's prefix.
+enum { kAStepPost = 0, kAStepWait = 1, kAStepVote = 2, kAStepPull = 3, kAStepSelf = 4 };
+struct RegA2aStep {
+  int kind, epoch, phase, peer;
+  int64_t peerOff, ownOff, bytes, blkBytes;
+};
+struct RegA2aPlanOut {
+  int nBlocks = 0;
+  std::vector<RegA2aStep> steps;
+};
+ncclResult_t reg_a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const int64_t* sendOff,
+                          const int64_t* recvOff, bool uniform, int minCTAs, int maxCTAs, int directMaxBlocks,
+                          RegA2aPlanOut* out);
+
 // ---------------------------------------------------------------- all-to-all
 // A comm's VCCL_LL_A2A_THRESHOLD (bytes per ordered pair) as it takes effect:
 // clamped to what one LL slot holds; 0 without LL buffers, with LL excluded by

@@ -20,7 +20,7 @@ static bool same_process(const ncclComm* c, int p) {
 void reg_create(ncclComm* c, PeerMap* me) {
   me->regOk = 0;
   me->regShm[0] = 0;
-  if (c->nRanks < 2 || param_int("REG_THRESHOLD", 0) <= 0) return;
+  if (c->nRanks < 2 || (param_int("REG_THRESHOLD", 0) <= 0 && param_int("REG_A2A_THRESHOLD", 0) <= 0)) return;
   static std::atomic<unsigned> serial{0};
   char name[sizeof(me->regShm)];
   snprintf(name, sizeof(name), "/vccl-reg-%d-%u-%d", (int)getpid(), serial.fetch_add(1), c->rank);
@@ -56,7 +56,9 @@ ncclResult_t reg_connect(ncclComm* c, bool anyNet) {
   bool all = c->reg != nullptr;
   for (const PeerMap& p : c->peers) all = all && p.regOk != 0;
   const uint64_t eff = all ? reg_max_of(*c, param_int("REG_THRESHOLD", 0), n, anyNet, c->dPeers != nullptr) : 0;
-  if (eff == 0) {
+  const uint64_t effA2a = reg_a2a_max_of(*c, param_int("REG_A2A_THRESHOLD", 0), n, anyNet, c->dPeers != nullptr,
+                                         c->p2pConns != nullptr, all);
+  if (eff == 0 && effA2a == 0) {
     reg_destroy(c);
     return ncclSuccess;
   }
@@ -83,9 +85,23 @@ ncclResult_t reg_connect(ncclComm* c, bool anyNet) {
   HIPCHECK(hipHostGetDevicePointer((void**)&r->tabDev, r->tab, 0));
   HIPCHECK(hipMalloc((void**)&r->stats, sizeof(RegStats)));
   HIPCHECK(hipMemset(r->stats, 0, sizeof(RegStats)));
+  if (effA2a > 0) NCCLCHECK(reg_a2a_alloc(c));
   r->threshold = eff;
-  VINFO("rank %d: buffer registry %s, zero-copy threshold %llu B", c->rank, r->shmName.c_str(),
-        (unsigned long long)eff);
+  c->regA2aMaxBytes = (size_t)effA2a;
+  VINFO("rank %d: buffer registry %s, zero-copy threshold %llu B, all-to-all %llu B per pair", c->rank,
+        r->shmName.c_str(), (unsigned long long)eff, (unsigned long long)effA2a);
+  return ncclSuccess;
+}
+
+// The all-to-all path's counters and skip words: only on a comm that switches
+// the path on (at init or through vcclCommSetRegA2aThreshold).
+ncclResult_t reg_a2a_alloc(ncclComm* c) {
+  RegComm* r = c->reg;
+  if (!r || r->a2aDev) return ncclSuccess;
+  DeviceGuard dev(c->device);
+  HIPCHECK(dev.status);
+  HIPCHECK(hipMalloc((void**)&r->a2aDev, sizeof(RegA2aDev)));
+  HIPCHECK(hipMemset(r->a2aDev, 0, sizeof(RegA2aDev)));
   return ncclSuccess;
 }
 
@@ -105,6 +121,8 @@ void reg_destroy(ncclComm* c) {
   if (r->mine) munmap(r->mine, sizeof(RegShm));
   if (r->tab) (void)hipHostFree(r->tab);
   if (r->stats) (void)hipFree(r->stats);
+  if (r->a2aDev) (void)hipFree(r->a2aDev);
+  c->regA2aMaxBytes = 0;
   for (RegHandle* h : r->handles) delete h;
   delete r;
   c->reg = nullptr;

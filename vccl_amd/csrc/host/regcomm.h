@@ -1,6 +1,8 @@
 // A communicator's buffer registry and import cache: what
 // ncclCommRegister / ncclCommDeregister do on a comm created with
-// VCCL_REG_THRESHOLD set, and what an eligible call reads at its enqueue.
+// VCCL_REG_THRESHOLD or VCCL_REG_A2A_THRESHOLD set (either builds the
+// registry; each switches on its own path only), and what an eligible call
+// reads at its enqueue.
 //
 // Registry: one per rank and comm, in POSIX shared memory created at init (its
 // name travels in PeerMap; every rank maps every peer's read-only before the
@@ -73,12 +75,17 @@ struct RegComm {
   RegPeers* tab = nullptr;     // the import table: host-pinned, mapped
   RegPeers* tabDev = nullptr;  // ... as the kernels address it
   RegStats* stats = nullptr;   // device-resident counters
+  // The zero-copy all-to-all (VCCL_REG_A2A_THRESHOLD, plan.h reg_a2a_max; the
+  // effective value is ncclComm::regA2aMaxBytes): its counters and the skip
+  // words of a group's eligible calls, device-resident
+  RegA2aDev* a2aDev = nullptr;
 };
 
 // init.cc: before the peer exchange (fills me->regShm / regOk), after the
 // peers are mapped, after the init barrier, and at teardown.
 void reg_create(ncclComm* c, PeerMap* me);
 ncclResult_t reg_connect(ncclComm* c, bool anyNet);
+ncclResult_t reg_a2a_alloc(ncclComm* c);  // RegComm::a2aDev, once (also vcclCommSetRegA2aThreshold)
 void reg_unlink(ncclComm* c);
 void reg_destroy(ncclComm* c);
 // The API bodies on a comm with a registry.

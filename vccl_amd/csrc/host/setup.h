@@ -101,6 +101,11 @@ size_t direct_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool
 // A comm's VCCL_REG_THRESHOLD of `threshold` as it takes effect (plan.h
 // reg_max; inbox: every peer's inbox and direct flags are mapped).
 size_t reg_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool inbox);
+// A comm's VCCL_REG_A2A_THRESHOLD likewise (plan.h reg_a2a_max; hasP2p: the
+// comm has point-to-point connections; allRegistries: every rank created its
+// registry).
+size_t reg_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool inbox, bool hasP2p,
+                      bool allRegistries);
 
 // What a rank publishes about where it runs (a PeerMap's identity fields).
 struct PeerId {

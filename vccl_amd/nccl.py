@@ -60,6 +60,9 @@ EXPORTED = [
     # steps, the registration table on its own, the counters, the live knob
     "vcclRegMax", "vcclRegEligible", "vcclRegPlan", "vcclRegTableNew", "vcclRegTableInsert", "vcclRegTableFind",
     "vcclRegTableRemove", "vcclRegTableFree", "vcclCommRegStats", "vcclCommSetRegThreshold",
+    # zero-copy all-to-all(v) over registered send buffers: the threshold, the eligibility rule, one launch's
+    # steps, the counters, the live knob
+    "vcclRegA2aMax", "vcclRegA2aEligible", "vcclRegA2aPlan", "vcclCommRegA2aStats", "vcclCommSetRegA2aThreshold",
     # out of scope, exported so libnccl-linked binaries load: WARN + ncclInvalidUsage
     "ncclGroupSimulateEnd",
     # memory / registration / scalable init (what a libnccl caller such as
@@ -216,6 +219,13 @@ def lib() -> ctypes.CDLL:
         "vcclRegTableFree": [vp],
         "vcclCommRegStats": [vp] + [ctypes.POINTER(ctypes.c_ulonglong)] * 3 + [ctypes.POINTER(c_int)] * 2,
         "vcclCommSetRegThreshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
+        "vcclRegA2aMax": [ctypes.c_int64, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int64)],
+        "vcclRegA2aEligible": [c_int, c_size, ctypes.c_int64, c_int, ctypes.POINTER(c_int)],
+        "vcclRegA2aPlan": [c_int, c_int, ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size),
+                           c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int),
+                           ctypes.POINTER(ctypes.c_int64)],
+        "vcclCommRegA2aStats": [vp] + [ctypes.POINTER(ctypes.c_ulonglong)] * 3,
+        "vcclCommSetRegA2aThreshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
         "vcclAlgoSelection": [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(c_int),
                               ctypes.POINTER(c_int)],
         "vcclCommSetup": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(u64),
@@ -504,6 +514,52 @@ def reg_plan(coll: int, count: int, dtype: int, nranks: int, rank: int, nblocks:
         k, ep, ph, peer, buf, poff, ooff, nb = steps[8 * i:8 * i + 8]
         out.append((REG_STEP_KINDS[k], ep, ph, peer, REG_BUFS[buf], poff, ooff, nb))
     return {"blk_elts": blk.value, "steps": out}
+
+
+REG_A2A_STEP_KINDS = ("post", "wait", "vote", "pull", "self")
+REG_A2A_MAX_CALLS = 8
+
+
+def reg_a2a_max(threshold: int | None, inbox: bool = True, direct_allowed: bool = True, any_net: bool = False,
+                nranks: int = 8, has_p2p: bool = True, all_registries: bool = True) -> int:
+    """vcclRegA2aMax: VCCL_REG_A2A_THRESHOLD as a comm takes it (None: from the
+    environment; 0 = off)."""
+    eff = ctypes.c_int64()
+    check(lib().vcclRegA2aMax(-1 if threshold is None else threshold, int(inbox), int(direct_allowed), int(any_net),
+                              nranks, int(has_p2p), int(all_registries), ctypes.byref(eff)), "vcclRegA2aMax")
+    return eff.value
+
+
+def reg_a2a_eligible(uniform: bool, pair_bytes: int, effective: int, index: int = 0) -> bool:
+    """vcclRegA2aEligible: whether an all-to-all launches the negotiating
+    zero-copy kernel; index = the eligible all-to-alls of its comm before it in its group."""
+    out = ctypes.c_int()
+    check(lib().vcclRegA2aEligible(int(uniform), pair_bytes, effective, index, ctypes.byref(out)),
+          "vcclRegA2aEligible")
+    return bool(out.value)
+
+
+def reg_a2a_plan(nranks: int, rank: int, send_bytes, send_off, recv_off, uniform: bool, min_ctas: int = 1,
+                 max_ctas: int = 64, direct_max_blocks: int = 64) -> dict:
+    """vcclRegA2aPlan: one zero-copy all-to-all launch as `rank` runs it.
+    send_bytes / send_off: n x n (row r = rank r's bytes / byte offsets per
+    peer); recv_off: this rank's n receive offsets.  Returns n_blocks and steps
+    = [(kind, epoch, phase, peer, peer offset, own offset, bytes, slice
+    bytes)] with kind from REG_A2A_STEP_KINDS."""
+    n = nranks
+    mat = ctypes.c_size_t * (n * n)
+    cap = 6 * n + 8
+    steps = (ctypes.c_int64 * (8 * cap))()
+    ns, nb = ctypes.c_int(), ctypes.c_int()
+    check(lib().vcclRegA2aPlan(n, rank, mat(*[x for row in send_bytes for x in row]),
+                               mat(*[x for row in send_off for x in row]), (ctypes.c_size_t * n)(*recv_off),
+                               int(uniform), min_ctas, max_ctas, direct_max_blocks, ctypes.byref(nb), cap,
+                               ctypes.byref(ns), steps), "vcclRegA2aPlan")
+    out = []
+    for i in range(ns.value):
+        k, ep, ph, peer, poff, ooff, nbytes, blk = steps[8 * i:8 * i + 8]
+        out.append((REG_A2A_STEP_KINDS[k], ep, ph, peer, poff, ooff, nbytes, blk))
+    return {"n_blocks": nb.value, "steps": out}
 
 
 class RegTable:
@@ -801,6 +857,20 @@ class Comm:
         """vcclCommSetRegThreshold: every rank alike, outside a group; the effective value."""
         eff = ctypes.c_int64()
         check(lib().vcclCommSetRegThreshold(self.handle, nbytes, ctypes.byref(eff)), "vcclCommSetRegThreshold")
+        return eff.value
+
+    def reg_a2a_stats(self) -> tuple[int, int, int]:
+        """vcclCommRegA2aStats (synchronises the device): eligible all-to-all
+        launches, zero-copy outcomes, fallback outcomes."""
+        a, b, c = ctypes.c_ulonglong(), ctypes.c_ulonglong(), ctypes.c_ulonglong()
+        check(lib().vcclCommRegA2aStats(self.handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
+              "vcclCommRegA2aStats")
+        return a.value, b.value, c.value
+
+    def set_reg_a2a_threshold(self, nbytes: int) -> int:
+        """vcclCommSetRegA2aThreshold: every rank alike, outside a group; the effective value."""
+        eff = ctypes.c_int64()
+        check(lib().vcclCommSetRegA2aThreshold(self.handle, nbytes, ctypes.byref(eff)), "vcclCommSetRegA2aThreshold")
         return eff.value
 
     def coll_algo(self, coll: int, count: int, dtype: int) -> str:
