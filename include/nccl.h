@@ -199,7 +199,15 @@ ncclResult_t pncclGroupEnd(void);
  * of at most that many bytes — above the rooted LL path and the LL128 window —
  * takes two hops on every link of the xGMI mesh instead: scatter + all-gather
  * from the root, reduce-scatter + gather to the root (the reduce bit-identical
- * to the ring's); NCCL_ALGO=Direct then takes that path at any size. ---- */
+ * to the ring's); NCCL_ALGO=Direct then takes that path at any size.  On a
+ * communicator created with VCCL_REG_ROOTED_THRESHOLD=<bytes> (default 0 = off)
+ * a broadcast or reduce of at least that many bytes, alone or the
+ * communicator's only collective of its group, runs zero-copy over
+ * ncclCommRegister'ed buffers when every buffer a peer reads is registered (a
+ * broadcast: the root's sendbuff and, with more than 2 ranks, the non-roots'
+ * recvbuffs; a reduce: every rank's sendbuff), otherwise the same launch runs
+ * the two-hop path above at any size, decided on the device; the reduce is
+ * bit-identical either way.  vccl_ext.h: vcclCommRegRootedStats. ---- */
 /* nccl.h.in:326-329 (in place) */
 ncclResult_t  ncclBcast(void* buff, size_t count, ncclDataType_t datatype, int root,
     ncclComm_t comm, hipStream_t stream);
@@ -251,7 +259,10 @@ ncclResult_t pncclCommInitRankScalable(ncclComm_t* newcomm, int nranks, int myra
  * out is ncclInvalidArgument.  ncclCommDestroy / ncclCommAbort drop everything.
  * Without the threshold registration does nothing and *handle = buff.  Inside a
  * stream capture nothing new is imported: a graph uses what earlier eager calls
- * imported (anything else falls back).  vccl_ext.h: vcclCommRegStats. */
+ * imported (anything else falls back).  vccl_ext.h: vcclCommRegStats.
+ * VCCL_REG_A2A_THRESHOLD (ncclAllToAll(v)) and VCCL_REG_ROOTED_THRESHOLD
+ * (ncclBroadcast / ncclBcast / ncclReduce, see above) create the same registry
+ * and switch on their own paths only. */
 ncclResult_t  ncclCommRegister(const ncclComm_t comm, void* buff, size_t size, void** handle);
 ncclResult_t pncclCommRegister(const ncclComm_t comm, void* buff, size_t size, void** handle);
 ncclResult_t  ncclCommDeregister(const ncclComm_t comm, void* handle);

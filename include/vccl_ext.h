@@ -424,6 +424,53 @@ ncclResult_t vcclRegA2aPlan(int nRanks, int rank, const size_t* sendBytes, const
 ncclResult_t vcclCommRegA2aStats(ncclComm_t comm, unsigned long long* launches, unsigned long long* zeroCopy,
                                  unsigned long long* fallback);
 ncclResult_t vcclCommSetRegA2aThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
+/* Zero-copy ncclBroadcast / ncclBcast / ncclReduce over ncclCommRegister'ed
+ * buffers (opt-in: VCCL_REG_ROOTED_THRESHOLD=<bytes> at init, default 0 = off;
+ * DESIGN.md 4.16).  A broadcast needs the root's sendbuff and (more than 2
+ * ranks) the non-roots' recvbuffs registered, a reduce every rank's sendbuff.
+ *   vcclRegRootedMax  the threshold as a comm takes it (threshold < 0: from the
+ *                    environment): 0 wherever vcclRegMax gives 0, or when a rank
+ *                    failed to create its registry (allRegistries = 0).  No
+ *                    upper clamp.
+ *   vcclRegRootedEligible  whether a call launches the negotiating kernel:
+ *                    effective > 0, coll 3 (broadcast) or 4 (reduce; any other
+ *                    is ncclInvalidArgument), groupCalls <= 1, and count * size
+ *                    >= effective.  vcclRegEligible is untouched: it refuses
+ *                    both collectives.
+ *   vcclRegRootedPlan  the ordered steps of one launch as `rank` runs it on
+ *                    nBlocks workgroups, regionBytes per inbox region: steps[8 k
+ *                    ..] = kind (0 post, 1 wait, 2 read-fold, 3 read-copy, 4
+ *                    store into region (1, me) of the root, 5 collect region
+ *                    (1, peer)), epoch (0 negotiate; broadcast: 1 data; reduce:
+ *                    1 + c for chunk c of the staged geometry), phase, peer,
+ *                    the peer's buffer read (0 sendbuff, 1 recvbuff), its byte
+ *                    offset, the byte offset in my recvbuff (kind 2 on a
+ *                    non-root owner: -1, the fold lands where the kind-4 step
+ *                    behind it says; kinds 4 / 5: the shard's user offset),
+ *                    bytes — in the kernel's order.  *blkElts: the bytes of a
+ *                    shard one workgroup moves in the zero-copy broadcast (a
+ *                    reduce: 0, its blocks are the staged ones); *chunkElts,
+ *                    *nChunks: the reduce's staged chunking (broadcast: the
+ *                    whole count, 1).  ncclInvalidArgument when cap < *nSteps
+ *                    (*nSteps is set first).
+ *   vcclCommRegRootedStats  synchronises the device, then: eligible launches,
+ *                    zero-copy outcomes, fallback outcomes — counters of their
+ *                    own (device-resident, so graph replays count); rooted calls
+ *                    never move vcclCommRegStats.  All 0 without a registry.
+ *   vcclCommSetRegRootedThreshold  the threshold for later calls; every rank
+ *                    calls it alike, outside a group.  A comm initialised with
+ *                    none of the three VCCL_REG_*THRESHOLD variables has no
+ *                    registry: *effective stays 0. */
+ncclResult_t vcclRegRootedMax(int64_t threshold, int inbox, int directAllowed, int anyNet, int nRanks,
+                              int allRegistries, int64_t* effective);
+ncclResult_t vcclRegRootedEligible(int coll, size_t count, ncclDataType_t datatype, int64_t effective, int groupCalls,
+                                   int* eligible);
+ncclResult_t vcclRegRootedPlan(int coll, size_t count, ncclDataType_t datatype, int nRanks, int rank, int root,
+                               size_t regionBytes, int nBlocks, int64_t* blkElts, int64_t* chunkElts, int* nChunks,
+                               int cap, int* nSteps, int64_t* steps);
+ncclResult_t vcclCommRegRootedStats(ncclComm_t comm, unsigned long long* launches, unsigned long long* zeroCopy,
+                                    unsigned long long* fallback);
+ncclResult_t vcclCommSetRegRootedThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
 /* What initialisation decides for rank `rank` of an nRanks communicator with
  * CTA bounds minCTAs / maxCTAs (a comm's defaults: 1 / 128), from the
  * environment as at init and each rank's identity pid[r], hostHash[r],

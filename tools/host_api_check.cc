@@ -619,6 +619,43 @@ int main() {
     unsetenv("VCCL_REG_A2A_THRESHOLD");
     EXPECT(vcclCommRegA2aStats(nullptr, nullptr, nullptr, nullptr) == ncclInvalidArgument);
     EXPECT(vcclCommSetRegA2aThreshold(nullptr, 4096, nullptr) == ncclInvalidArgument);
+    // the zero-copy broadcast / reduce: threshold, eligibility and step lists
+    // on random counts, roots, regions, grids and invalid arguments
+    for (int trial = 0; trial < 20000; trial++) {
+      if (rng() % 2) setenv("VCCL_REG_ROOTED_THRESHOLD", rng() % 4 ? "32768" : junk[rng() % 11], 1);
+      else unsetenv("VCCL_REG_ROOTED_THRESHOLD");
+      const int n = (int)pick({0, 1, 2, 3, 4, 8, 9}), rank = (int)(rng() % (n + 1)) - (rng() % 32 == 0);
+      const int root = (int)(rng() % (n + 1)) - (rng() % 32 == 0);
+      const int coll = (int)(rng() % 6), dt = rng() % 16 ? dts[rng() % 10] : 12;
+      const size_t count = (size_t)pick({0, 1, 15, 4095, 4096, 4097, 70001, 1000003}) + rng() % 3;
+      int64_t eff = -7;
+      const ncclResult_t r0 = vcclRegRootedMax(pick({-1, 0, 1, 32768, 1ll << 40}), (int)(rng() % 2), (int)(rng() % 2),
+                                               (int)(rng() % 2), n, (int)(rng() % 2), rng() % 16 ? &eff : nullptr);
+      EXPECT(r0 == ncclSuccess || r0 == ncclInvalidArgument);
+      if (r0 == ncclSuccess) EXPECT(eff >= 0 && (eff == 0 || (n >= 2 && n <= 8)));
+      int el = -7;
+      const ncclResult_t r1 = vcclRegRootedEligible(coll, count, (ncclDataType_t)dt, pick({-1, 0, 1, 32768}),
+                                                    (int)pick({-1, 0, 1, 2, 40}), rng() % 16 ? &el : nullptr);
+      EXPECT(r1 == ncclSuccess || r1 == ncclInvalidArgument);
+      if (r1 == ncclSuccess) EXPECT((el == 0 || el == 1) && (coll == 3 || coll == 4));
+      const int nb = (int)pick({0, 1, 5, 16, 128, 129}), cap = (int)pick({0, 8, 80, 4000});
+      const size_t region = (size_t)pick({0, 16, 32, 272, 4112, 65792, 2097408});
+      std::vector<int64_t> steps(8 * (size_t)cap + 8, -1);
+      int ns = -7, nch = -7;
+      int64_t blk = -7, chunk = -7;
+      const ncclResult_t r2 = vcclRegRootedPlan(coll, count, (ncclDataType_t)dt, n, rank, root, region, nb,
+                                                rng() % 8 ? &blk : nullptr, &chunk, &nch, cap, &ns, steps.data());
+      EXPECT(r2 == ncclSuccess || r2 == ncclInvalidArgument);
+      if (r2 == ncclSuccess) {
+        EXPECT(ns > 0 && ns <= cap && nch >= 1 && chunk >= 1 && (coll == 3 || coll == 4));
+        for (int k = 0; k < ns; k++) EXPECT(steps[8 * k] >= 0 && steps[8 * k] <= 5 && steps[8 * k + 7] >= 0);
+      }
+      EXPECT(steps[8 * (size_t)cap] == -1);
+      regOps++;
+    }
+    unsetenv("VCCL_REG_ROOTED_THRESHOLD");
+    EXPECT(vcclCommRegRootedStats(nullptr, nullptr, nullptr, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclCommSetRegRootedThreshold(nullptr, 4096, nullptr) == ncclInvalidArgument);
   }
   printf("host_api_check: %ld registration table operations, thresholds and zero-copy plans\n", regOps);
   printf("host_api_check: %ld all-to-all limits and plans\n", a2a);

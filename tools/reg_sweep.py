@@ -24,6 +24,13 @@ behind one negotiation launch; off: vcclCommSetRegA2aThreshold 0), every row
 checked and its path confirmed by vcclCommRegA2aStats
 (profiles/reg_sweep/reg_a2a_sweep.jsonl).
 
+With --rooted the sweep is ncclBroadcast (u8) and ncclReduce (f32 sum) from / to
+rank 0, on a communicator created with VCCL_REG_ROOTED_THRESHOLD set: 64 KiB -
+256 MiB (x4 steps), the same three modes (fallback: the staged direct rooted
+part behind one negotiation epoch; off: vcclCommSetRegRootedThreshold 0), every
+row checked and its path confirmed by vcclCommRegRootedStats
+(profiles/reg_sweep/reg_rooted_sweep.jsonl).
+
 The parent spawns the rank processes (bench.py's launcher; ranks share a GPU
 when the box has fewer than ranks — then the rows are rehearsal rows: they show
 HBM traffic and phase count, and nothing about xGMI) and prints one JSON line
@@ -44,8 +51,9 @@ def arg(name, default):
 
 
 A2A = "--a2a" in sys.argv
+ROOTED = "--rooted" in sys.argv
 MIN_BYTES = int(arg("--min-bytes", 64 << 10))
-MAX_BYTES = int(arg("--max-bytes", 64 << 20 if A2A else 1 << 30))
+MAX_BYTES = int(arg("--max-bytes", 64 << 20 if A2A else 256 << 20 if ROOTED else 1 << 30))
 STEPS = max(5, int(arg("--steps", 10 if A2A else 20)))
 RANKS = [int(x) for x in arg("--ranks", "4,8").split(",")]
 WARMUP = 2 if A2A else 3
@@ -67,7 +75,8 @@ def parent():
         env = dict(os.environ)
         env.pop("WORLD_SIZE", None)
         env["REG_SWEEP_CHILD"] = "1"
-        env["VCCL_REG_A2A_THRESHOLD" if A2A else "VCCL_REG_THRESHOLD"] = str(THRESH)
+        env["VCCL_REG_A2A_THRESHOLD" if A2A else "VCCL_REG_ROOTED_THRESHOLD" if ROOTED else "VCCL_REG_THRESHOLD"] = \
+            str(THRESH)
         env.setdefault("VCCL_SPIN_TIMEOUT_S", "30")
         plan = bench.rank_launch_plan(["--gpus", str(n)] + sys.argv[1:], env, script=os.path.abspath(__file__))
         rc = rc or bench._spawn_ranks(plan)
@@ -105,7 +114,8 @@ def child():
     comm = nccl.Comm.init_rank(n, nccl.unique_id_from_bytes(obj[0]), rank)
     sp = torch.cuda.current_stream().cuda_stream
     F32, U8 = nccl.ncclFloat32, nccl.ncclUint8
-    if (comm.set_reg_a2a_threshold(THRESH) if A2A else comm.set_reg_threshold(THRESH)) != THRESH:
+    if (comm.set_reg_a2a_threshold(THRESH) if A2A else comm.set_reg_rooted_threshold(THRESH) if ROOTED
+            else comm.set_reg_threshold(THRESH)) != THRESH:
         raise SystemExit("this communicator has no buffer registry (the threshold did not take effect)")
 
     def row(**kw):
@@ -174,8 +184,59 @@ def child():
         comm.set_reg_a2a_threshold(THRESH)
         return good
 
+    def rooted_rows():
+        """--rooted: ncclBroadcast (u8) from and ncclReduce (f32 sum) to rank 0.  Only
+        what a peer reads is registered: the root's sendbuff and the non-roots'
+        recvbuffs of a broadcast, every sendbuff of a reduce."""
+        good = True
+        for coll in ("broadcast", "reduce"):
+            for nbytes in sizes(MIN_BYTES, MAX_BYTES):
+                for mode in ("zero_copy", "fallback", "off"):
+                    if coll == "broadcast":
+                        i = torch.arange(nbytes, device="cuda", dtype=torch.int32)
+                        want = (i % 251).to(torch.uint8)
+                        x = want.clone() if rank == 0 else None
+                        y = torch.empty(nbytes, device="cuda", dtype=torch.uint8)
+                        del i
+                        mine = x if rank == 0 else y
+
+                        def call():
+                            comm.broadcast(x.data_ptr() if rank == 0 else 0, y.data_ptr(), nbytes, U8, 0, sp)
+                    else:
+                        cnt = nbytes // 4
+                        i = torch.arange(cnt, device="cuda", dtype=torch.int32)
+                        x = (i % 13 + rank).float()
+                        y = torch.empty_like(x) if rank == 0 else None
+                        want = ((i % 13) * n + n * (n - 1) // 2).float() if rank == 0 else None
+                        del i
+                        mine = x
+
+                        def call():
+                            comm.reduce(x.data_ptr(), y.data_ptr() if rank == 0 else 0, cnt, F32, nccl.ncclSum, 0, sp)
+                    handle = comm.register(mine.data_ptr(), mine.numel() * mine.element_size()) \
+                        if mode == "zero_copy" else None
+                    comm.set_reg_rooted_threshold(0 if mode == "off" else THRESH)
+                    torch.cuda.synchronize()
+                    dist.barrier()  # every rank's registrations precede every import
+                    base = comm.reg_rooted_stats()
+                    if y is not None:
+                        y.zero_()
+                    us = timed(call, torch.cuda.synchronize)
+                    d = [a - b for a, b in zip(comm.reg_rooted_stats(), base)]
+                    calls = WARMUP + STEPS
+                    path_ok = d == {"zero_copy": [calls, calls, 0], "fallback": [calls, 0, calls],
+                                    "off": [0, 0, 0]}[mode]
+                    value_ok = y is None or bool(torch.equal(y, want))
+                    good &= row(coll=coll, ranks=n, bytes=nbytes, mode=mode, min_us=us[0], median_us=us[len(us) // 2],
+                                steps=STEPS, shared_gpu=shared, ok=value_ok and path_ok and comm.async_error() == 0)
+                    if handle is not None:
+                        comm.deregister(handle)
+                    del x, y, want, mine
+        comm.set_reg_rooted_threshold(THRESH)
+        return good
+
     good = True
-    for coll in () if A2A else ("allreduce", "reducescatter", "allgather"):
+    for coll in () if A2A or ROOTED else ("allreduce", "reducescatter", "allgather"):
         for nbytes in sizes(MIN_BYTES, MAX_BYTES):
             for mode in ("zero_copy", "fallback", "off"):
                 x, y, call, check = buffers(coll, nbytes)
@@ -198,6 +259,8 @@ def child():
                 del x, y
     if A2A:
         good = a2a_rows()
+    elif ROOTED:
+        good = rooted_rows()
     else:
         comm.set_reg_threshold(THRESH)
     torch.cuda.synchronize()

@@ -243,10 +243,18 @@ struct DirectRegWork {
   const RegPeers* reg;   // host-pinned, mapped
   RegStats* stats;       // device-resident
   RegDesc mine;
-  int64_t zcBlkElts;     // host/plan.cc reg_plan on w.nBlocks
-  int needRecv;          // all-reduce: peers read my recvbuff too
+  int64_t zcBlkElts;     // host/plan.cc reg_plan / reg_rooted_plan on w.nBlocks
+  // Which buffers the negotiation covers, as kRegSend | kRegRecv bits: `mine`
+  // — my own buffers some peer will read (they must be registered); `peer` /
+  // `rootPeer` — what I read of a peer that is not / that is rank w.root (it
+  // must resolve in my import table).  All-reduce: send | recv everywhere;
+  // reduce-scatter / all-gather: send everywhere; the rooted kernels differ by
+  // role (host/launch.cc launch_direct_reg_rooted).
+  uint8_t needMine, needPeer, needRootPeer;
+  uint8_t pad8;
   int pad;
 };
+enum : uint8_t { kRegSend = 1, kRegRecv = 2 };
 static_assert(sizeof(DirectRegWork) <= 4096, "DirectRegWork must fit the kernel-argument budget");
 
 // Zero-copy all-to-all(v) over registered send buffers (direct_reg.hpp

@@ -130,6 +130,30 @@
 //                    (the call's bytes move in the FIFO launch behind it, which
 //                    uses no inbox and no direct flag).  Positions per launch:
 //                    2 or 1, the same on every rank since the verdict is.
+//    zero-copy      (direct_reg.hpp reg_broadcast_zc, a launch of its own over
+//    broadcast       the root's registered sendbuff and the non-roots' registered
+//                    recvbuffs) one position of negotiation as above, then
+//                    EITHER one position that touches no region: an owner pulls
+//                    its shard from the root, post (0) after it, wait (0) on
+//                    every peer, pulls of the other shards from their owners'
+//                    recvbuffs, post (1) after them (R1: it follows wait (0)),
+//                    wait (1) closing it (R2) — the root only posts and waits;
+//                    OR direct_broadcast_part unchanged.  Positions per launch:
+//                    2, or 1 + nChunks.
+//    zero-copy      (direct_reg.hpp reg_reduce_zc, every rank's sendbuff
+//    reduce          registered) one position of negotiation, then per chunk of
+//                    the staged geometry EITHER the staged chunk minus its
+//                    scatter: post (0) — no data, but the root's post follows its
+//                    collect of the previous chunk — wait (0) on every peer; the
+//                    owner folds from the n user inputs, a non-root owner into
+//                    region (1, o) AT THE ROOT (R1: after wait (0)); post (1),
+//                    also "I have finished reading your inputs of this chunk";
+//                    wait (1) closes the chunk on every rank (R2); the root
+//                    collects its (1, *) regions before its next post; OR
+//                    direct_reduce_part unchanged.  (0, *) regions are not
+//                    touched, (1, *) regions exactly as the staged reduce
+//                    touches them.  Positions per launch: 1 + nChunks either
+//                    way.
 #pragma once
 #include "coll_types.hpp"
 #include "ll.hpp"

@@ -127,13 +127,19 @@ __device__ __forceinline__ bool reg_negotiate(const DirectRegWork& rw, uint32_t 
     const char* s = nullptr;
     const char* r = nullptr;
     if (t == me) {
-      ok = rw.mine.sendEntry != kRegNone && (!rw.needRecv || rw.mine.recvEntry != kRegNone);
+      ok = (!(rw.needMine & kRegSend) || rw.mine.sendEntry != kRegNone) &&
+           (!(rw.needMine & kRegRecv) || rw.mine.recvEntry != kRegNone);
     } else if (live) {
+      // what I will read of rank t (the rooted kernels: by t's role)
+      const uint8_t need = t == w.root ? rw.needRootPeer : rw.needPeer;
       const char* line = myFlags + direct_flag_off(0, 0, t, b);
-      s = reg_resolve(rw.reg, t, reg_ld32(line, 40), reg_ld32(line, 44), reg_ld64(line, 8), reg_ld64(line, 24),
-                      rw.mine.sendBytes);
-      ok = s != nullptr;
-      if (rw.needRecv) {
+      ok = 1;
+      if (need & kRegSend) {
+        s = reg_resolve(rw.reg, t, reg_ld32(line, 40), reg_ld32(line, 44), reg_ld64(line, 8), reg_ld64(line, 24),
+                        rw.mine.sendBytes);
+        ok = s != nullptr;
+      }
+      if (need & kRegRecv) {
         r = reg_resolve(rw.reg, t, reg_ld32(line, 48), reg_ld32(line, 52), reg_ld64(line, 16), reg_ld64(line, 32),
                         rw.mine.recvBytes);
         ok = ok && r != nullptr;
@@ -281,8 +287,176 @@ __device__ __forceinline__ void reg_allreduce_zc(const DirectRegWork& rw, const 
   (void)direct_wait(w, P.flags[me], 1, 0, b, e, shFail);
 }
 
-// One launch: negotiate, then `zc` (zero-copy, one epoch) or `staged` (the
-// direct_*_part of the collective).  The counters are workgroup 0's.
+// ------------------------------------------------------- broadcast / reduce
+// Zero-copy rooted collectives (opt-in, VCCL_REG_ROOTED_THRESHOLD; DESIGN.md
+// §4.16): the two-hop kernels of direct.hpp with the user buffers in the place
+// of the inbox.  Which buffers a rank announces and resolves follows its role
+// (DirectRegWork::needMine / needPeer / needRootPeer, host/launch.cc): the
+// broadcast root announces sendbuff, a non-root recvbuff (nothing at n = 2:
+// nobody reads it) and never looks at its own sendbuff; a reduce announces
+// sendbuff on every rank and recvbuff nowhere.  The step lists are host/plan.cc
+// reg_rooted_plan's, kept side by side with these orders.
+//
+// Broadcast, D = 1, epoch k + 1 — one position, no inbox, any size.  Shards are
+// direct_broadcast_part's of the WHOLE byte count (n - 1 shards of whole 16-byte
+// units, shard j owned by direct_bcast_owner(root, j, n)); workgroup b moves
+// bytes [b * zcBlkElts, (b + 1) * zcBlkElts) of a shard:
+//   non-root o   pull my block of my shard from the ROOT's sendbuff into my
+//                recvbuff (write-through, drained by the post);
+//                post (0) "my shard in my recvbuff is final, and I have finished
+//                reading the root";  wait (0) on every peer;
+//                pull block b of every other shard from its OWNER's recvbuff;
+//                post (1) "finished reading your recvbuff";  wait (1);
+//   root         copy send -> recv locally when they differ; post (0); wait (0)
+//                — only now is its sendbuff released; post (1); wait (1).
+// Every rank writes only its own recvbuff, flags aside.  In place (ncclBcast)
+// needs no extra care: shard o of a rank's buffer is read only from its owner
+// o, and only after o's (0).  Alignments differ freely (direct_rc's shifted path).
+__device__ __forceinline__ void reg_broadcast_zc(const DirectRegWork& rw, const RegResolved& rs, uint32_t e,
+                                                 int* shFail) {
+  using Fn = FnCopy<uint8_t>;
+  const Fn fn(0);
+  const DirectWork& w = rw.w;
+  const DirectPeers& P = *w.peers;
+  const int n = w.nRanks, me = w.rank, root = w.root, b = blockIdx.x;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int64_t count = (int64_t)w.count;  // bytes
+  const int64_t shard = direct_shard_elts(count, n - 1, 16);
+  auto block_of = [&](int j, int64_t* off, int64_t* len) {  // block b of shard j
+    int64_t shardEnd = (int64_t)(j + 1) * shard;
+    shardEnd = shardEnd < count ? shardEnd : count;
+    const int64_t lo = (int64_t)j * shard + (int64_t)b * rw.zcBlkElts;
+    const int64_t hi = lo + rw.zcBlkElts < shardEnd ? lo + rw.zcBlkElts : shardEnd;
+    *off = lo;
+    *len = hi > lo ? hi - lo : 0;
+  };
+  char* out = (char*)w.recvbuff;
+  if (me != root) {
+    int64_t off, len;
+    block_of(direct_bcast_shard_of(root, me, n), &off, &len);
+    const char* s[kDirectMaxRanks] = {rs.send[root] + off};
+    char* d[kDirectMaxRanks] = {out + off};
+    direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+  } else if ((const char*)w.sendbuff != out) {
+    for (int j = 0; j < n - 1; j++) {
+      int64_t off, len;
+      block_of(j, &off, &len);
+      const char* s[kDirectMaxRanks] = {(const char*)w.sendbuff + off};
+      char* d[kDirectMaxRanks] = {out + off};
+      direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+    }
+  }
+  direct_post(w, P, 0, 0, b, e);
+  if (direct_wait(w, P.flags[me], 0, 0, b, e, shFail) && me != root) {
+    for (int k = 1; k < n; k++) {
+      const int o = me + k < n ? me + k : me + k - n;
+      if (o == root) continue;
+      int64_t off, len;
+      block_of(direct_bcast_shard_of(root, o, n), &off, &len);
+      const char* s[kDirectMaxRanks] = {rs.recv[o] + off};
+      char* d[kDirectMaxRanks] = {out + off};
+      direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+    }
+  }
+  direct_post(w, P, 1, 0, b, e);
+  (void)direct_wait(w, P.flags[me], 1, 0, b, e, shFail);
+}
+
+// Reduce, D = 1 — direct_reduce_part minus its scatter, on the same DirectWork
+// chunk geometry (so either outcome consumes 1 + nChunks positions; `e` enters
+// as chunk 0's epoch and leaves as the last chunk's).  Per chunk:
+//   post (0); wait (0)   no data moves: the round keeps R1 and orders the root's
+//                collect of the previous chunk before anyone rewrites a (1, *)
+//                region;
+//   fold         owner o folds block b of shard o from the n USER INPUTS (peer
+//                pointers for q != me, sendbuff for q = me) in exactly
+//                direct_reduce_part's order — the channel from the call's cbd
+//                under SIMPLE, ringAt[ch mod nRings], from the root's successor
+//                round to the root, preOp on every input, postOp once; the root
+//                straight into recvbuff, any other owner into region (1, o) of
+//                the ROOT's inbox (the staged push, unchanged);
+//   post (1)     "my shard is delivered, and I have finished reading your
+//                inputs of this chunk";  wait (1);
+//   collect      the root copies its regions (1, o) into recvbuff.
+// A non-root never touches recvbuff.  In place at the root is legal: shard o of
+// the root's input is read by o alone and overwritten only after o's (1).
+template <class Fn>
+__device__ __forceinline__ void reg_reduce_zc(const DirectRegWork& rw, const RegResolved& rs, uint32_t& e,
+                                              int* shFail) {
+  using T = typename Fn::EltType;
+  constexpr int64_t esz = (int64_t)sizeof(T);
+  const DirectWork& w = rw.w;
+  const Fn fn(load_op_arg(w.redArgPtr, w.redArgBytes, w.redArg));
+  const DirectPeers& P = *w.peers;
+  const int n = w.nRanks, me = w.rank, root = w.root, b = blockIdx.x;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int64_t eltAlign = 16 / sizeof(T) ? 16 / sizeof(T) : 1;
+  const int64_t count = (int64_t)w.count;
+  char* myBuf = P.buf[me];
+  const char* myFlags = P.flags[me];
+  const int64_t inOff = (int64_t)b * w.blkElts * esz;  // block offset in a region
+  for (int c = 0; c < w.nChunks; c++) {
+    if (c) e = epoch_after(e);
+    if (*shFail) continue;
+    const int64_t c0 = (int64_t)c * w.chunkElts;
+    const int64_t cc = count - c0 < w.chunkElts ? count - c0 : w.chunkElts;
+    const int64_t shardElts = direct_shard_elts(cc, n, eltAlign);
+    auto block_of = [&](int o, int64_t* off, int64_t* len) {  // block b of shard o, chunk-relative
+      int64_t shardEnd = (int64_t)(o + 1) * shardElts;
+      shardEnd = shardEnd < cc ? shardEnd : cc;
+      const int64_t lo = (int64_t)o * shardElts + (int64_t)b * w.blkElts;
+      const int64_t hi = lo + w.blkElts < shardEnd ? lo + w.blkElts : shardEnd;
+      *off = lo;
+      *len = hi > lo ? hi - lo : 0;
+    };
+    direct_post(w, P, 0, 0, b, e);
+    if (direct_wait(w, myFlags, 0, 0, b, e, shFail)) {
+      int64_t off, len;
+      block_of(me, &off, &len);
+      for (int64_t cur = 0; cur < len;) {
+        int64_t end;
+        const int ch = cbd_channel_of(w.cbd, c0 + off + cur, &end);
+        end -= c0 + off;
+        end = end < len ? end : len;
+        const int8_t* R = w.comm->ringAt[ch % w.comm->nRings];
+        int k = 0;  // the root's position on this ring
+#pragma unroll
+        for (int p = 0; p < kDirectMaxRanks; p++)
+          if (p < n && R[p] == root) k = p;
+        k = __builtin_amdgcn_readfirstlane(k);
+        const char* s[kDirectMaxRanks];
+        char* d[kDirectMaxRanks] = {
+            me == root ? (char*)w.recvbuff + (c0 + off + cur) * esz
+                       : P.buf[root] + direct_region_off(1, 0, me, n, w.regionBytes) + inOff + cur * esz};
+#pragma unroll
+        for (int j = 0; j < kDirectMaxRanks; j++) {
+          int pos = k + 1 + j;
+          pos = pos >= n ? pos - n : pos;
+          pos = pos >= n ? pos - n : pos;
+          const int q = j < n ? __builtin_amdgcn_readfirstlane(R[pos]) : me;
+          s[j] = (q == me ? (const char*)w.sendbuff : rs.send[q]) + (c0 + off + cur) * esz;
+        }
+        direct_rc<Fn, kDirectUnroll, kSys, kSys, kSys>(fn, s, n, w.preOp ? n : 0, true, d, 1, end - cur, tid, nt);
+        cur = end;
+      }
+    }
+    direct_post(w, P, 1, 0, b, e);
+    if (direct_wait(w, myFlags, 1, 0, b, e, shFail) && me == root) {
+      for (int k = 1; k < n; k++) {
+        const int o = me + k < n ? me + k : me + k - n;
+        int64_t off, len;
+        block_of(o, &off, &len);
+        const char* s[kDirectMaxRanks] = {myBuf + direct_region_off(1, 0, o, n, w.regionBytes) + inOff};
+        char* d[kDirectMaxRanks] = {(char*)w.recvbuff + (c0 + off) * esz};
+        direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+      }
+    }
+  }
+}
+
+// One launch: negotiate, then `zc` (zero-copy: one epoch, the reduce one per
+// chunk — it advances `e` itself) or `staged` (the direct_*_part of the
+// collective).  The counters are workgroup 0's.
 template <class ZC, class Staged>
 __device__ __forceinline__ void direct_reg_run(const DirectRegWork& rw, ZC zc, Staged staged) {
   __shared__ int shFail;

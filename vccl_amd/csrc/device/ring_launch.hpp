@@ -84,6 +84,15 @@ inline hipError_t direct_reg_launch(int coll, int devOp, const DirectRegWork& rw
                                 : direct_reg_launch_rsag<K>(coll, devOp, rw, stream, stop);
 }
 
+// Zero-copy broadcast / reduce over registered buffers (direct_reg.hpp
+// reg_broadcast_zc / reg_reduce_zc), the staged rooted part of direct.hpp as the
+// in-kernel fallback: one call per launch, rw.w.nBlocks workgroups.  A third
+// object per kernel type (direct_reg_kernels.hip, VCCL_REG_PART 2); the
+// byte-copy broadcast only in the K_U8 unit.
+template <int K>
+hipError_t direct_reg_launch_rooted(int coll, int devOp, const DirectRegWork& rw, hipStream_t stream,
+                                    hipEvent_t stop);
+
 // Zero-copy all-to-all(v) over registered send buffers (direct_reg.hpp
 // direct_reg_alltoall): a byte copy, built once in the K_U8 unit of
 // direct_reg_kernels.hip (part 1); w.nBlocks workgroups of kDirectThreads threads.

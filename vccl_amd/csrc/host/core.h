@@ -141,12 +141,16 @@ struct ncclComm : vccl::CommSetup {
   char* p2pFlags = nullptr;
   vccl::P2pConn* p2pConns = nullptr;
   // ncclCommRegister'ed buffers and the peers' imported ones (regcomm.h);
-  // null unless VCCL_REG_THRESHOLD or VCCL_REG_A2A_THRESHOLD took effect at init
+  // null unless VCCL_REG_THRESHOLD, VCCL_REG_A2A_THRESHOLD or
+  // VCCL_REG_ROOTED_THRESHOLD took effect at init
   vccl::RegComm* reg = nullptr;
   // Smallest ordered pair of a uniform ncclAllToAll on the zero-copy path over
   // registered send buffers, and the size vote of a v-call
   // (VCCL_REG_A2A_THRESHOLD, plan.h reg_a2a_max; default 0 = off)
   size_t regA2aMaxBytes = 0;
+  // Smallest ncclBroadcast / ncclReduce on the zero-copy path over registered
+  // buffers (VCCL_REG_ROOTED_THRESHOLD, plan.h reg_rooted_max; default 0 = off)
+  size_t regRootedMaxBytes = 0;
   vccl::NetProxy* net = nullptr;  // inter-node ring connections (proxy.cc)
   int netListenFd = -1;        // proxy listener, open from init until connections are made
   vccl::DevComm* devComm = nullptr;

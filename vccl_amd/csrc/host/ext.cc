@@ -531,6 +531,82 @@ VCCL_EXPORT ncclResult_t vcclCommSetRegThreshold(ncclComm_t comm, int64_t bytes,
   return ncclSuccess;
 }
 
+// -------------------------------------- rooted collectives over registered buffers
+// A comm's VCCL_REG_ROOTED_THRESHOLD as it takes effect (the arithmetic).
+VCCL_EXPORT ncclResult_t vcclRegRootedMax(int64_t threshold, int inbox, int directAllowed, int anyNet, int nRanks,
+                                          int allRegistries, int64_t* effective) {
+  if (!effective || nRanks < 1) return ncclInvalidArgument;
+  if (threshold < 0) threshold = param_int("REG_ROOTED_THRESHOLD", 0);
+  *effective = (int64_t)reg_rooted_max(threshold, inbox != 0, directAllowed != 0, anyNet != 0, nRanks,
+                                       allRegistries != 0);
+  return ncclSuccess;
+}
+
+VCCL_EXPORT ncclResult_t vcclRegRootedEligible(int coll, size_t count, ncclDataType_t datatype, int64_t effective,
+                                               int groupCalls, int* eligible) {
+  if (!eligible || (coll != kBroadcast && coll != kReduce) || type_size(datatype) < 1 || effective < 0 ||
+      groupCalls < 0 || count > (size_t)1 << 56)
+    return ncclInvalidArgument;
+  *eligible = reg_rooted_eligible(coll, (int64_t)count, type_size(datatype), (uint64_t)effective, groupCalls);
+  return ncclSuccess;
+}
+
+// The ordered steps of one zero-copy broadcast / reduce launch as `rank` runs it on nBlocks workgroups.
+VCCL_EXPORT ncclResult_t vcclRegRootedPlan(int coll, size_t count, ncclDataType_t datatype, int nRanks, int rank,
+                                           int root, size_t regionBytes, int nBlocks, int64_t* blkElts,
+                                           int64_t* chunkElts, int* nChunks, int cap, int* nSteps, int64_t* steps) {
+  if ((coll != kBroadcast && coll != kReduce) || nRanks < 2 || nRanks > kDirectMaxRanks || rank < 0 ||
+      rank >= nRanks || root < 0 || root >= nRanks || type_size(datatype) < 1 || count == 0 ||
+      count > (size_t)1 << 56 || regionBytes < 32 || regionBytes > (size_t)1 << 40 || nBlocks < 1 ||
+      nBlocks > kDirectMaxBlocks || !nSteps || cap < 0 || (cap && !steps))
+    return ncclInvalidArgument;
+  const CallSize sz = call_size(coll, count, datatype);
+  RegRootedPlanOut out;
+  NCCLCHECK(reg_rooted_plan(coll, nRanks, rank, root, sz.count, sz.eltSize, (int64_t)regionBytes, nBlocks, &out));
+  if (blkElts) *blkElts = out.blkElts;
+  if (chunkElts) *chunkElts = out.chunkElts;
+  if (nChunks) *nChunks = out.nChunks;
+  *nSteps = (int)out.steps.size();
+  if (*nSteps > cap) return ncclInvalidArgument;
+  for (size_t k = 0; k < out.steps.size(); k++) {
+    const RegStep& d = out.steps[k];
+    const int64_t v[8] = {d.kind, d.epoch, d.phase, d.peer, d.buf, d.peerOff, d.ownOff, d.bytes};
+    for (int j = 0; j < 8; j++) steps[8 * k + j] = v[j];
+  }
+  return ncclSuccess;
+}
+
+// Synchronises the device, then reads the three device-resident counters.
+VCCL_EXPORT ncclResult_t vcclCommRegRootedStats(ncclComm_t comm, unsigned long long* launches,
+                                                unsigned long long* zeroCopy, unsigned long long* fallback) {
+  NCCLCHECK(comm_check(comm, "vcclCommRegRootedStats"));
+  unsigned long long w[3] = {0, 0, 0};
+  if (comm->reg && comm->reg->rootedStats) {
+    DeviceGuard dev(comm->device);
+    HIPCHECK(dev.status);
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpy(w, comm->reg->rootedStats, sizeof(w), hipMemcpyDeviceToHost));
+  }
+  if (launches) *launches = w[0];
+  if (zeroCopy) *zeroCopy = w[1];
+  if (fallback) *fallback = w[2];
+  return ncclSuccess;
+}
+
+// A tuning / measurement knob: every rank must call it alike, outside a group.
+// A comm initialised without a registry has none to switch on: 0 stays 0.
+VCCL_EXPORT ncclResult_t vcclCommSetRegRootedThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective) {
+  NCCLCHECK(comm_check(comm, "vcclCommSetRegRootedThreshold"));
+  if (bytes < 0) return ncclInvalidArgument;
+  if (comm->reg) {  // a registry exists only where every rank has one and no peer is behind the net proxy
+    const size_t eff = reg_rooted_max_of(*comm, bytes, comm->nRanks, false, comm->dPeers != nullptr, true);
+    if (eff > 0) NCCLCHECK(reg_rooted_alloc(comm));
+    comm->regRootedMaxBytes = eff;
+  }
+  if (effective) *effective = (int64_t)comm->regRootedMaxBytes;
+  return ncclSuccess;
+}
+
 // ------------------------------------------- all-to-all over registered buffers
 // A comm's VCCL_REG_A2A_THRESHOLD as it takes effect (the arithmetic).
 VCCL_EXPORT ncclResult_t vcclRegA2aMax(int64_t threshold, int inbox, int directAllowed, int anyNet, int nRanks,

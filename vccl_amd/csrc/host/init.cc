@@ -400,7 +400,7 @@ static ncclResult_t init_rank(ncclComm* c, const ncclUniqueId* id) {
   NCCLCHECK(create_flags_and_events(c));
   PeerMap me{};
   NCCLCHECK(alloc_buffers(c, sizes, &me));
-  reg_create(c, &me);  // VCCL_REG_THRESHOLD: this rank's buffer registry, named in `me`
+  reg_create(c, &me);  // VCCL_REG_THRESHOLD / _A2A_ / _ROOTED_: this rank's buffer registry, named in `me`
   NCCLCHECK(exchange_peers(c, &me));
   MeshSetup mesh;
   NCCLCHECK(apply_mesh(c, &mesh));
@@ -637,7 +637,8 @@ VCCL_EXPORT ncclResult_t ncclMemFree(void* ptr) {
 // addressable by the comm's other ranks (regcomm.h) — local, non-collective —
 // and the direct all-reduce / reduce-scatter / all-gather of at least the
 // threshold run zero-copy when every rank's buffers are registered (DESIGN.md
-// §4.14).  Without it registration is accepted and does nothing, as before.
+// §4.14); VCCL_REG_A2A_THRESHOLD and VCCL_REG_ROOTED_THRESHOLD do the same for
+// the all-to-all (§4.15) and for broadcast / reduce (§4.16).  Without them registration is accepted and does nothing, as before.
 VCCL_EXPORT ncclResult_t ncclCommRegister(const ncclComm_t comm, void* buff, size_t size, void** handle) {
   NCCLCHECK(comm_check(comm, "ncclCommRegister"));
   if (!handle) return ncclInvalidArgument;

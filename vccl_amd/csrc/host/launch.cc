@@ -499,36 +499,94 @@ static bool reg_task_eligible(const Task& t) {
   return c->reg && c->dPeers &&
          reg_eligible(t.coll, (int64_t)t.count, type_size(t.datatype), c->nRanks, c->reg->threshold, t.groupColls);
 }
-// The staged geometry is direct_work_of's (the fallback runs it as it is), the
-// zero-copy block length plan.cc reg_plan's on the same grid; the descriptors
-// are this rank's registrations of the call's buffers as of now, and the
-// import table is brought up to date first (nothing in the steady state).
-static ncclResult_t launch_direct_reg(const Task& t, hipEvent_t stop) {
+// The rooted calls' rule (plan.cc reg_rooted_eligible), on the comm's own
+// threshold: a broadcast or reduce, alone or its comm's only collective of its
+// group; the fallback is the staged direct rooted part at any size, whether or
+// not VCCL_DIRECT_ROOTED_THRESHOLD is set.
+static bool reg_rooted_task_eligible(const Task& t) {
+  const ncclComm* c = t.comm;
+  return c->reg && c->reg->rootedStats && c->dPeers &&
+         reg_rooted_eligible(t.coll, (int64_t)t.count, type_size(t.datatype), c->regRootedMaxBytes, t.groupColls);
+}
+// What the two zero-copy launches share.  The staged geometry is
+// direct_work_of's (the fallback runs it as it is); the import table is brought
+// up to date first (nothing in the steady state, nothing inside a capture).
+static ncclResult_t reg_work_of(const Task& t, DirectRegWork* rw, int* kt, int* devOp) {
   ncclComm* comm = t.comm;
   CaptureState cs{false, 0};
   NCCLCHECK(capture_state(t.stream, &cs));
   NCCLCHECK(reg_refresh(comm, cs.active));
+  NCCLCHECK(direct_work_of(t, &rw->w, kt, devOp));
+  rw->reg = comm->reg->tabDev;
+  return ncclSuccess;
+}
+// The descriptor: this rank's registrations, as of now, of the buffers of
+// `needMine` — those some peer will read; the others travel as kRegNone and
+// are never looked up (a broadcast non-root's sendbuff may be NULL).
+static void reg_describe_mine(const Task& t, DirectRegWork* rw, uint64_t sendBytes, uint64_t recvBytes) {
+  RegDesc& d = rw->mine;
+  d.sendBytes = sendBytes;
+  d.recvBytes = recvBytes;
+  d.sendEntry = d.recvEntry = kRegNone;
+  if (rw->needMine & kRegSend) reg_describe(t.comm, t.sendbuff, sendBytes, &d.sendEntry, &d.sendGen, &d.sendOff);
+  if (rw->needMine & kRegRecv) reg_describe(t.comm, t.recvbuff, recvBytes, &d.recvEntry, &d.recvGen, &d.recvOff);
+}
+// The zero-copy block length is plan.cc reg_plan's on the staged grid.
+static ncclResult_t launch_direct_reg(const Task& t, hipEvent_t stop) {
+  ncclComm* comm = t.comm;
   DirectRegWork rw{};
   int kt = -1, devOp = -1;
-  NCCLCHECK(direct_work_of(t, &rw.w, &kt, &devOp));
+  NCCLCHECK(reg_work_of(t, &rw, &kt, &devOp));
   const auto [count, esz] = call_size(t.coll, t.count, t.datatype);
   RegPlanOut rp;
   NCCLCHECK(reg_plan(t.coll, comm->nRanks, comm->rank, count, esz, rw.w.nBlocks, &rp));
-  rw.reg = comm->reg->tabDev;
   rw.stats = comm->reg->stats;
   rw.zcBlkElts = rp.blkElts;
-  rw.needRecv = t.coll == kAllReduce;
   // what the peers read of mine: the whole input; the all-reduce's output too
-  rw.mine.sendBytes = (uint64_t)(t.coll == kReduceScatter ? count * comm->nRanks : count) * (uint64_t)esz;
-  rw.mine.recvBytes = rw.needRecv ? (uint64_t)count * (uint64_t)esz : 0;
-  reg_describe(comm, t.sendbuff, rw.mine.sendBytes, &rw.mine.sendEntry, &rw.mine.sendGen, &rw.mine.sendOff);
-  rw.mine.recvEntry = kRegNone;
-  if (rw.needRecv)
-    reg_describe(comm, t.recvbuff, rw.mine.recvBytes, &rw.mine.recvEntry, &rw.mine.recvGen, &rw.mine.recvOff);
+  rw.needMine = rw.needPeer = rw.needRootPeer = t.coll == kAllReduce ? kRegSend | kRegRecv : kRegSend;
+  reg_describe_mine(t, &rw, (uint64_t)(t.coll == kReduceScatter ? count * comm->nRanks : count) * (uint64_t)esz,
+                    t.coll == kAllReduce ? (uint64_t)count * (uint64_t)esz : 0);
   const hipError_t e =
       by_kernel_type(kt, [&]<int K>() { return direct_reg_launch<K>(t.coll, devOp, rw, t.stream, stop); });
   if (e != hipSuccess) {
     VWARN("zero-copy direct kernel launch failed: %s", hipGetErrorString(e));
+    return ncclUnhandledCudaError;
+  }
+  return ncclSuccess;
+}
+// Broadcast / reduce (device/direct_reg.hpp reg_broadcast_zc / reg_reduce_zc):
+// plan.cc reg_rooted_plan gives the broadcast's block length on the staged grid
+// and must agree with the staged chunking the reduce runs on.  Roles: the
+// broadcast root announces sendbuff and reads nobody; a non-root announces
+// recvbuff (n > 2: the other non-roots pull its shard from there), reads the
+// root's sendbuff and the other non-roots' recvbuffs; a reduce announces and
+// reads sendbuff everywhere.
+static ncclResult_t launch_direct_reg_rooted(const Task& t, hipEvent_t stop) {
+  ncclComm* comm = t.comm;
+  const int n = comm->nRanks;
+  DirectRegWork rw{};
+  int kt = -1, devOp = -1;
+  NCCLCHECK(reg_work_of(t, &rw, &kt, &devOp));
+  const auto [count, esz] = call_size(t.coll, t.count, t.datatype);
+  RegRootedPlanOut rp;
+  NCCLCHECK(reg_rooted_plan(t.coll, n, comm->rank, t.root, count, esz, comm->dRegionBytes, rw.w.nBlocks, &rp));
+  if (t.coll == kReduce && (rp.nChunks != rw.w.nChunks || rp.chunkElts != rw.w.chunkElts)) return ncclInternalError;
+  rw.stats = comm->reg->rootedStats;
+  rw.zcBlkElts = rp.blkElts;
+  const bool isRoot = comm->rank == t.root;
+  if (t.coll == kReduce) {
+    rw.needMine = rw.needPeer = rw.needRootPeer = kRegSend;
+  } else {
+    rw.needMine = isRoot ? kRegSend : n > 2 ? kRegRecv : 0;
+    rw.needPeer = isRoot ? 0 : kRegRecv;
+    rw.needRootPeer = isRoot ? 0 : kRegSend;
+  }
+  const uint64_t bytes = (uint64_t)count * (uint64_t)esz;
+  reg_describe_mine(t, &rw, bytes, bytes);
+  const hipError_t e =
+      by_kernel_type(kt, [&]<int K>() { return direct_reg_launch_rooted<K>(t.coll, devOp, rw, t.stream, stop); });
+  if (e != hipSuccess) {
+    VWARN("zero-copy rooted kernel launch failed: %s", hipGetErrorString(e));
     return ncclUnhandledCudaError;
   }
   return ncclSuccess;
@@ -541,8 +599,14 @@ static int choose_algo(const Task& t) {
 
 // 1 .. max_parts(algo) fusable calls as one launch of path `algo`.
 constexpr int kAlgoDirectReg = 100;  // launch.cc only: one eligible call, the zero-copy kernel
+constexpr int kAlgoDirectRegRooted = 101;  // ... a broadcast / reduce
+// The zero-copy path of a call that is eligible for one, else `algo`.
+static int reg_algo_or(const Task& t, int algo) {
+  return reg_task_eligible(t) ? kAlgoDirectReg : reg_rooted_task_eligible(t) ? kAlgoDirectRegRooted : algo;
+}
 static ncclResult_t launch_path(int algo, const Task* ts, int n, hipEvent_t stop) {
   if (algo == kAlgoDirectReg) return n == 1 ? launch_direct_reg(ts[0], stop) : ncclInternalError;
+  if (algo == kAlgoDirectRegRooted) return n == 1 ? launch_direct_reg_rooted(ts[0], stop) : ncclInternalError;
   return algo == kAlgoLL ? launch_ll(ts, n, stop)
          : algo == kAlgoDirect ? launch_direct(ts, n, stop) : launch_ring(ts, n, algo == kAlgoRingLL128, stop);
 }
@@ -561,8 +625,10 @@ ncclResult_t launch_task(const Task& t) {
   } else {
     CaptureState cs{false, 0};
     r = stream_order(comm, t.stream, &cs);
-    if (r == ncclSuccess)
-      r = launch_path(reg_task_eligible(t) ? kAlgoDirectReg : choose_algo(t), &t, 1, stop_event(comm, cs));
+    if (r == ncclSuccess) {
+      const int reg = reg_algo_or(t, -1);
+      r = launch_path(reg >= 0 ? reg : choose_algo(t), &t, 1, stop_event(comm, cs));
+    }
     if (r == ncclSuccess) r = stream_mark(comm, t.stream, cs);
   }
   comm->opCount++;  // whatever the outcome
@@ -677,9 +743,9 @@ static ncclResult_t launch_planned(std::vector<Task>& tasks, const std::vector<i
     Task t = tasks[idx[k]];
     // the comm's only collective of the group, eligible for the zero-copy
     // kernel: its partition is the call's alone, as outside a group
-    const bool zeroCopy = reg_task_eligible(t);
+    const int a = reg_algo_or(t, plan.algo[k]);
+    const bool zeroCopy = a == kAlgoDirectReg || a == kAlgoDirectRegRooted;
     if (zeroCopy) t.planned = false;
-    const int a = zeroCopy ? kAlgoDirectReg : plan.algo[k];
     const int64_t lines = a == kAlgoLL ? ll_lines_of(t) : 0;
     if (fusePlanned && !runs.empty() && runPlan.back() == plan.planOf[k] && runAlgo.back() == a &&
         runs.back().size() < (size_t)max_parts(a) && fusable(runs.back()[0], t) &&

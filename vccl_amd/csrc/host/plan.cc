@@ -619,6 +619,99 @@ ncclResult_t reg_plan(int coll, int nRanks, int rank, int64_t count, int64_t elt
   return ncclSuccess;
 }
 
+// -------------------------------------- rooted collectives over registered buffers
+uint64_t reg_rooted_max(int64_t threshold, bool inbox, bool directAllowed, bool anyNet, int nRanks,
+                        bool allRegistries) {
+  if (!allRegistries) return 0;
+  return reg_max(threshold, inbox, directAllowed, anyNet, nRanks);
+}
+bool reg_rooted_eligible(int coll, int64_t count, int64_t typeSize, uint64_t effective, int groupCalls) {
+  if (effective == 0 || groupCalls > 1) return false;
+  if (coll != kBroadcast && coll != kReduce) return false;
+  return (uint64_t)(count * typeSize) >= effective;
+}
+
+// The steps below are reg_broadcast_zc's / reg_reduce_zc's order
+// (device/direct_reg.hpp), rank by rank; the peer loops run in the direct
+// kernels' rotation, (rank + k) mod n.
+ncclResult_t reg_rooted_plan(int coll, int nRanks, int rank, int root, int64_t count, int64_t eltSize,
+                             int64_t regionBytes, int nBlocks, RegRootedPlanOut* out) {
+  if (coll != kBroadcast && coll != kReduce) return ncclInvalidArgument;
+  const int n = nRanks;
+  if (n < 2 || n > kDirectMaxRanks || rank < 0 || rank >= n || root < 0 || root >= n || nBlocks < 1 || count < 1)
+    return ncclInvalidArgument;
+  const int64_t esz = eltSize, eltAlign = std::max<int64_t>(1, 16 / esz);
+  auto& st = out->steps;
+  st.clear();
+  auto post = [&](int epoch, int phase) { st.push_back(RegStep{kRStepPost, epoch, phase, 0, 0, 0, 0, 0}); };
+  auto wait = [&](int epoch, int phase) {
+    for (int k = 1; k < n; k++) st.push_back(RegStep{kRStepWait, epoch, phase, (rank + k) % n, 0, 0, 0, 0});
+  };
+  // epoch 0: descriptors out, descriptors in, verdicts out, verdicts in
+  post(0, 0);
+  wait(0, 0);
+  post(0, 1);
+  wait(0, 1);
+  if (coll == kBroadcast) {
+    // shard j = bytes [j * shard, min((j + 1) * shard, count)), owned by direct_bcast_owner(root, j, n)
+    const int64_t shard = direct_shard_elts(count, n - 1, 16);
+    out->shardElts = shard;
+    out->blkElts = ((shard + nBlocks - 1) / nBlocks + 15) / 16 * 16;
+    out->nChunks = 1;
+    out->chunkElts = count;
+    auto lo_of = [&](int j) { return std::min((int64_t)j * shard, count); };
+    auto len_of = [&](int j) { return std::min((int64_t)(j + 1) * shard, count) - lo_of(j); };
+    if (rank != root) {  // my shard, from the root's sendbuff
+      const int j = direct_bcast_shard_of(root, rank, n);
+      st.push_back(RegStep{kRStepCopy, 1, 0, root, kRBufSend, lo_of(j), lo_of(j), len_of(j)});
+    } else {  // send -> recv, shard by shard (nothing in place)
+      for (int j = 0; j < n - 1; j++)
+        st.push_back(RegStep{kRStepCopy, 1, 0, rank, kRBufSend, lo_of(j), lo_of(j), len_of(j)});
+    }
+    post(1, 0);  // "my shard in my recvbuff is final, and I have finished reading the root"
+    wait(1, 0);
+    if (rank != root) {
+      for (int k = 1; k < n; k++) {  // the other shards, from their owners' recvbuff
+        const int o = (rank + k) % n;
+        if (o == root) continue;
+        const int j = direct_bcast_shard_of(root, o, n);
+        st.push_back(RegStep{kRStepCopy, 1, 0, o, kRBufRecv, lo_of(j), lo_of(j), len_of(j)});
+      }
+    }
+    post(1, 1);  // "finished reading your recvbuff"
+    wait(1, 1);
+    return ncclSuccess;
+  }
+  DirectRootedPlanOut geo;
+  if (direct_rooted_plan(kReduce, n, rank, root, count, esz, regionBytes, -1, &geo) != ncclSuccess)
+    return ncclInvalidArgument;
+  out->chunkElts = geo.chunkElts;
+  out->nChunks = geo.nChunks;
+  out->shardElts = direct_shard_elts(geo.chunkElts, n, eltAlign);
+  out->blkElts = 0;
+  for (int c = 0; c < geo.nChunks; c++) {
+    const int ep = 1 + c;
+    const int64_t c0 = (int64_t)c * geo.chunkElts, cc = std::min(geo.chunkElts, count - c0);
+    const int64_t shard = direct_shard_elts(cc, n, eltAlign);
+    auto off_of = [&](int o) { return (c0 + std::min((int64_t)o * shard, cc)) * esz; };
+    auto len_of = [&](int o) { return (c0 + std::min((int64_t)(o + 1) * shard, cc)) * esz - off_of(o); };
+    post(ep, 0);  // no data: R1, and my collect of the previous chunk precedes it
+    wait(ep, 0);
+    for (int k = 0; k < n; k++)  // fold my shard from the n user inputs
+      st.push_back(RegStep{kRStepFold, ep, 0, (rank + k) % n, kRBufSend, off_of(rank),
+                           rank == root ? off_of(rank) : (int64_t)-1, len_of(rank)});
+    if (rank != root) st.push_back(RegStep{kRStepStoreRoot, ep, 1, root, 0, 0, off_of(rank), len_of(rank)});
+    post(ep, 1);  // "my shard is delivered, and I have finished reading your inputs of this chunk"
+    wait(ep, 1);
+    if (rank == root)
+      for (int k = 1; k < n; k++) {
+        const int o = (rank + k) % n;
+        st.push_back(RegStep{kRStepCollect, ep, 1, o, 0, 0, off_of(o), len_of(o)});
+      }
+  }
+  return ncclSuccess;
+}
+
 // ------------------------------------------- all-to-all over registered buffers
 uint64_t reg_a2a_max(int64_t threshold, bool inbox, bool directAllowed, bool anyNet, int nRanks, bool hasP2p,
                      bool allRegistries) {

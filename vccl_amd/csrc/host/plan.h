@@ -240,6 +240,57 @@ struct RegPlanOut {
 };
 ncclResult_t reg_plan(int coll, int nRanks, int rank, int64_t count, int64_t eltSize, int nBlocks, RegPlanOut* out);
 
+// -------------------------------------- rooted collectives over registered buffers
+// The zero-copy ncclBroadcast / ncclBcast / ncclReduce (device/direct_reg.hpp
+// reg_broadcast_zc / reg_reduce_zc): the host's half.
+// A comm's VCCL_REG_ROOTED_THRESHOLD (bytes) as it takes effect: 0 wherever
+// reg_max gives 0, or when any rank failed to create its registry.  No upper
+// clamp: the broadcast uses no inbox, the reduce moves through it in chunks.
+uint64_t reg_rooted_max(int64_t threshold, bool inbox, bool directAllowed, bool anyNet, int nRanks,
+                        bool allRegistries);
+// From the call's own arguments and comm-wide values alone: effective > 0, a
+// broadcast or a reduce of count * typeSize >= effective bytes, alone or its
+// comm's only collective of its group (groupCalls <= 1).  An eligible call
+// launches the negotiating kernel ahead of select_algo's choice at any size;
+// its on-device fallback is the staged direct rooted part, never the ring.
+bool reg_rooted_eligible(int coll, int64_t count, int64_t typeSize, uint64_t effective, int groupCalls);
+// One launch as `rank` runs it on nBlocks workgroups — device/direct_reg.hpp
+// reg_broadcast_zc / reg_reduce_zc keep this order and name this list.  Epoch 0
+// negotiates as in reg_plan; the broadcast then spends ONE more position on the
+// whole byte count, the reduce one per chunk of the staged geometry
+// (direct_rooted_plan on regionBytes): epoch 1 + c is chunk c.  RegStep's words,
+// with two more kinds:
+//   kRStepPost / kRStepWait  as reg_plan's
+//   kRStepCopy  {epoch, peer, buf, peerOff, ownOff, bytes}: peer's buffer `buf`
+//               -> recvbuff[ownOff ..]: a non-root's pull of its own shard from
+//               the root's sendbuff, of another shard from its owner's recvbuff;
+//               peer == rank, buf send: the broadcast root's local send -> recv
+//               copy (skipped by the kernel in place)
+//   kRStepFold  {epoch, peer, buf send, peerOff, ownOff, bytes}: one source of
+//               the owner's n-source fold of its shard of the chunk, listed in
+//               rank rotation (the fold order is the ring reduce's, from the
+//               comm's tables).  On the root the fold lands at recvbuff[ownOff
+//               ..]; on any other owner ownOff is -1 and the result goes where
+//               the kRStepStoreRoot that follows the n fold steps says
+//   kRStepStoreRoot  {epoch, peer = the root, ownOff = the shard's user offset,
+//               bytes}: the folded shard -> region (1, rank) of the root's inbox
+//   kRStepCollect    {epoch, peer = o, ownOff, bytes}: the root copies its region
+//               (1, o) -> recvbuff[ownOff ..]
+// Offsets and lengths in bytes; a step covers a whole shard, of which workgroup
+// b moves [b * blk, (b + 1) * blk): blkElts is the broadcast's zero-copy block
+// length, alignUp(ceil(shard / nBlocks), 16) bytes of its n - 1 shards of the
+// whole count (shardElts), and the reduce's 0 (its blocks are the staged
+// geometry's).  count in elements of eltSize (a broadcast: bytes, eltSize 1).
+enum { kRStepStoreRoot = 4, kRStepCollect = 5 };
+struct RegRootedPlanOut {
+  int64_t shardElts = 0, blkElts = 0;
+  int nChunks = 0;           // reduce: the staged chunk count; broadcast: 1
+  int64_t chunkElts = 0;
+  std::vector<RegStep> steps;
+};
+ncclResult_t reg_rooted_plan(int coll, int nRanks, int rank, int root, int64_t count, int64_t eltSize,
+                             int64_t regionBytes, int nBlocks, RegRootedPlanOut* out);
+
 // ------------------------------------------- all-to-all over registered buffers
 // The zero-copy ncclAllToAll(v) (device/direct_reg.hpp direct_reg_alltoall,
 // DESIGN.md §4.15): the host's half.

@@ -20,7 +20,9 @@ static bool same_process(const ncclComm* c, int p) {
 void reg_create(ncclComm* c, PeerMap* me) {
   me->regOk = 0;
   me->regShm[0] = 0;
-  if (c->nRanks < 2 || (param_int("REG_THRESHOLD", 0) <= 0 && param_int("REG_A2A_THRESHOLD", 0) <= 0)) return;
+  if (c->nRanks < 2 || (param_int("REG_THRESHOLD", 0) <= 0 && param_int("REG_A2A_THRESHOLD", 0) <= 0 &&
+                        param_int("REG_ROOTED_THRESHOLD", 0) <= 0))
+    return;
   static std::atomic<unsigned> serial{0};
   char name[sizeof(me->regShm)];
   snprintf(name, sizeof(name), "/vccl-reg-%d-%u-%d", (int)getpid(), serial.fetch_add(1), c->rank);
@@ -58,7 +60,9 @@ ncclResult_t reg_connect(ncclComm* c, bool anyNet) {
   const uint64_t eff = all ? reg_max_of(*c, param_int("REG_THRESHOLD", 0), n, anyNet, c->dPeers != nullptr) : 0;
   const uint64_t effA2a = reg_a2a_max_of(*c, param_int("REG_A2A_THRESHOLD", 0), n, anyNet, c->dPeers != nullptr,
                                          c->p2pConns != nullptr, all);
-  if (eff == 0 && effA2a == 0) {
+  const uint64_t effRooted =
+      reg_rooted_max_of(*c, param_int("REG_ROOTED_THRESHOLD", 0), n, anyNet, c->dPeers != nullptr, all);
+  if (eff == 0 && effA2a == 0 && effRooted == 0) {
     reg_destroy(c);
     return ncclSuccess;
   }
@@ -86,10 +90,12 @@ ncclResult_t reg_connect(ncclComm* c, bool anyNet) {
   HIPCHECK(hipMalloc((void**)&r->stats, sizeof(RegStats)));
   HIPCHECK(hipMemset(r->stats, 0, sizeof(RegStats)));
   if (effA2a > 0) NCCLCHECK(reg_a2a_alloc(c));
+  if (effRooted > 0) NCCLCHECK(reg_rooted_alloc(c));
   r->threshold = eff;
   c->regA2aMaxBytes = (size_t)effA2a;
-  VINFO("rank %d: buffer registry %s, zero-copy threshold %llu B, all-to-all %llu B per pair", c->rank,
-        r->shmName.c_str(), (unsigned long long)eff, (unsigned long long)effA2a);
+  c->regRootedMaxBytes = (size_t)effRooted;
+  VINFO("rank %d: buffer registry %s, zero-copy threshold %llu B, all-to-all %llu B per pair, rooted %llu B", c->rank,
+        r->shmName.c_str(), (unsigned long long)eff, (unsigned long long)effA2a, (unsigned long long)effRooted);
   return ncclSuccess;
 }
 
@@ -102,6 +108,18 @@ ncclResult_t reg_a2a_alloc(ncclComm* c) {
   HIPCHECK(dev.status);
   HIPCHECK(hipMalloc((void**)&r->a2aDev, sizeof(RegA2aDev)));
   HIPCHECK(hipMemset(r->a2aDev, 0, sizeof(RegA2aDev)));
+  return ncclSuccess;
+}
+
+// The rooted path's counters, likewise only where the path is switched on (at
+// init or through vcclCommSetRegRootedThreshold).
+ncclResult_t reg_rooted_alloc(ncclComm* c) {
+  RegComm* r = c->reg;
+  if (!r || r->rootedStats) return ncclSuccess;
+  DeviceGuard dev(c->device);
+  HIPCHECK(dev.status);
+  HIPCHECK(hipMalloc((void**)&r->rootedStats, sizeof(RegStats)));
+  HIPCHECK(hipMemset(r->rootedStats, 0, sizeof(RegStats)));
   return ncclSuccess;
 }
 
@@ -122,7 +140,9 @@ void reg_destroy(ncclComm* c) {
   if (r->tab) (void)hipHostFree(r->tab);
   if (r->stats) (void)hipFree(r->stats);
   if (r->a2aDev) (void)hipFree(r->a2aDev);
+  if (r->rootedStats) (void)hipFree(r->rootedStats);
   c->regA2aMaxBytes = 0;
+  c->regRootedMaxBytes = 0;
   for (RegHandle* h : r->handles) delete h;
   delete r;
   c->reg = nullptr;

@@ -1,7 +1,7 @@
 // A communicator's buffer registry and import cache: what
 // ncclCommRegister / ncclCommDeregister do on a comm created with
-// VCCL_REG_THRESHOLD or VCCL_REG_A2A_THRESHOLD set (either builds the
-// registry; each switches on its own path only), and what an eligible call
+// VCCL_REG_THRESHOLD, VCCL_REG_A2A_THRESHOLD or VCCL_REG_ROOTED_THRESHOLD set
+// (any of them builds the registry; each switches on its own path only), and what an eligible call
 // reads at its enqueue.
 //
 // Registry: one per rank and comm, in POSIX shared memory created at init (its
@@ -79,6 +79,10 @@ struct RegComm {
   // effective value is ncclComm::regA2aMaxBytes): its counters and the skip
   // words of a group's eligible calls, device-resident
   RegA2aDev* a2aDev = nullptr;
+  // The zero-copy broadcast / reduce (VCCL_REG_ROOTED_THRESHOLD, plan.h
+  // reg_rooted_max; the effective value is ncclComm::regRootedMaxBytes): its
+  // three counters, device-resident, apart from `stats`
+  RegStats* rootedStats = nullptr;
 };
 
 // init.cc: before the peer exchange (fills me->regShm / regOk), after the
@@ -86,6 +90,7 @@ struct RegComm {
 void reg_create(ncclComm* c, PeerMap* me);
 ncclResult_t reg_connect(ncclComm* c, bool anyNet);
 ncclResult_t reg_a2a_alloc(ncclComm* c);  // RegComm::a2aDev, once (also vcclCommSetRegA2aThreshold)
+ncclResult_t reg_rooted_alloc(ncclComm* c);  // RegComm::rootedStats, once (also vcclCommSetRegRootedThreshold)
 void reg_unlink(ncclComm* c);
 void reg_destroy(ncclComm* c);
 // The API bodies on a comm with a registry.

@@ -406,6 +406,11 @@ size_t reg_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool an
                              allRegistries);
 }
 
+size_t reg_rooted_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool inbox,
+                         bool allRegistries) {
+  return (size_t)reg_rooted_max(threshold, inbox, (s.algoAllowed & kAllowDirect) != 0, anyNet, nRanks, allRegistries);
+}
+
 static bool same_gpu(const PeerId& a, const PeerId& b) { return a.hostHash == b.hostHash && a.busId == b.busId; }
 
 ncclResult_t setup_mesh(int rank, const std::vector<PeerId>& peers, CommSetup* s, MeshSetup* m) {

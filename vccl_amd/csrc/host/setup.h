@@ -106,6 +106,9 @@ size_t reg_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet
 // registry).
 size_t reg_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool inbox, bool hasP2p,
                       bool allRegistries);
+// A comm's VCCL_REG_ROOTED_THRESHOLD likewise (plan.h reg_rooted_max).
+size_t reg_rooted_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool inbox,
+                         bool allRegistries);
 
 // What a rank publishes about where it runs (a PeerMap's identity fields).
 struct PeerId {

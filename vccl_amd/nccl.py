@@ -63,6 +63,10 @@ EXPORTED = [
     # zero-copy all-to-all(v) over registered send buffers: the threshold, the eligibility rule, one launch's
     # steps, the counters, the live knob
     "vcclRegA2aMax", "vcclRegA2aEligible", "vcclRegA2aPlan", "vcclCommRegA2aStats", "vcclCommSetRegA2aThreshold",
+    # zero-copy broadcast / reduce over registered buffers: the threshold, the eligibility rule, one launch's
+    # steps, the counters, the live knob
+    "vcclRegRootedMax", "vcclRegRootedEligible", "vcclRegRootedPlan", "vcclCommRegRootedStats",
+    "vcclCommSetRegRootedThreshold",
     # out of scope, exported so libnccl-linked binaries load: WARN + ncclInvalidUsage
     "ncclGroupSimulateEnd",
     # memory / registration / scalable init (what a libnccl caller such as
@@ -219,6 +223,13 @@ def lib() -> ctypes.CDLL:
         "vcclRegTableFree": [vp],
         "vcclCommRegStats": [vp] + [ctypes.POINTER(ctypes.c_ulonglong)] * 3 + [ctypes.POINTER(c_int)] * 2,
         "vcclCommSetRegThreshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
+        "vcclRegRootedMax": [ctypes.c_int64, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int64)],
+        "vcclRegRootedEligible": [c_int, c_size, c_int, ctypes.c_int64, c_int, ctypes.POINTER(c_int)],
+        "vcclRegRootedPlan": [c_int, c_size, c_int, c_int, c_int, c_int, c_size, c_int,
+                              ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int),
+                              c_int, ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_int64)],
+        "vcclCommRegRootedStats": [vp] + [ctypes.POINTER(ctypes.c_ulonglong)] * 3,
+        "vcclCommSetRegRootedThreshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
         "vcclRegA2aMax": [ctypes.c_int64, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int64)],
         "vcclRegA2aEligible": [c_int, c_size, ctypes.c_int64, c_int, ctypes.POINTER(c_int)],
         "vcclRegA2aPlan": [c_int, c_int, ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size),
@@ -514,6 +525,51 @@ def reg_plan(coll: int, count: int, dtype: int, nranks: int, rank: int, nblocks:
         k, ep, ph, peer, buf, poff, ooff, nb = steps[8 * i:8 * i + 8]
         out.append((REG_STEP_KINDS[k], ep, ph, peer, REG_BUFS[buf], poff, ooff, nb))
     return {"blk_elts": blk.value, "steps": out}
+
+
+REG_ROOTED_STEP_KINDS = REG_STEP_KINDS + ("store_root", "collect")
+
+
+def reg_rooted_max(threshold: int | None, inbox: bool = True, direct_allowed: bool = True, any_net: bool = False,
+                   nranks: int = 8, all_registries: bool = True) -> int:
+    """vcclRegRootedMax: VCCL_REG_ROOTED_THRESHOLD as a comm takes it (None:
+    from the environment); 0 = the zero-copy broadcast / reduce is off."""
+    eff = ctypes.c_int64()
+    check(lib().vcclRegRootedMax(-1 if threshold is None else threshold, int(inbox), int(direct_allowed),
+                                 int(any_net), nranks, int(all_registries), ctypes.byref(eff)), "vcclRegRootedMax")
+    return eff.value
+
+
+def reg_rooted_eligible(coll: int, count: int, dtype: int, effective: int, group_calls: int = 0) -> bool:
+    """vcclRegRootedEligible: whether a broadcast / reduce launches the
+    negotiating zero-copy kernel."""
+    out = ctypes.c_int()
+    check(lib().vcclRegRootedEligible(coll, count, dtype, effective, group_calls, ctypes.byref(out)),
+          "vcclRegRootedEligible")
+    return bool(out.value)
+
+
+def reg_rooted_plan(coll: int, count: int, dtype: int, nranks: int, rank: int, root: int, region_bytes: int,
+                    nblocks: int) -> dict:
+    """vcclRegRootedPlan: one zero-copy broadcast / reduce launch as `rank`
+    runs it on nblocks workgroups.  Returns blk_elts (the broadcast's block
+    length; 0 for a reduce), chunk_elts, n_chunks and steps = [(kind, epoch,
+    phase, peer, buf, peer offset, own offset, bytes)] with kind from
+    REG_ROOTED_STEP_KINDS and buf from REG_BUFS."""
+    blk, chunk, nch, ns = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int(), ctypes.c_int()
+    args = (coll, count, dtype, nranks, rank, root, region_bytes, nblocks, ctypes.byref(blk), ctypes.byref(chunk),
+            ctypes.byref(nch))
+    rc = lib().vcclRegRootedPlan(*args, 0, ctypes.byref(ns), None)  # the step count first
+    if ns.value == 0:
+        check(rc, "vcclRegRootedPlan")
+    cap = ns.value
+    steps = (ctypes.c_int64 * (8 * cap))()
+    check(lib().vcclRegRootedPlan(*args, cap, ctypes.byref(ns), steps), "vcclRegRootedPlan")
+    out = []
+    for i in range(ns.value):
+        k, ep, ph, peer, buf, poff, ooff, nb = steps[8 * i:8 * i + 8]
+        out.append((REG_ROOTED_STEP_KINDS[k], ep, ph, peer, REG_BUFS[buf], poff, ooff, nb))
+    return {"blk_elts": blk.value, "chunk_elts": chunk.value, "n_chunks": nch.value, "steps": out}
 
 
 REG_A2A_STEP_KINDS = ("post", "wait", "vote", "pull", "self")
@@ -857,6 +913,21 @@ class Comm:
         """vcclCommSetRegThreshold: every rank alike, outside a group; the effective value."""
         eff = ctypes.c_int64()
         check(lib().vcclCommSetRegThreshold(self.handle, nbytes, ctypes.byref(eff)), "vcclCommSetRegThreshold")
+        return eff.value
+
+    def reg_rooted_stats(self) -> tuple[int, int, int]:
+        """vcclCommRegRootedStats (synchronises the device): eligible broadcast
+        / reduce launches, zero-copy, fallback."""
+        a, b, c = ctypes.c_ulonglong(), ctypes.c_ulonglong(), ctypes.c_ulonglong()
+        check(lib().vcclCommRegRootedStats(self.handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
+              "vcclCommRegRootedStats")
+        return a.value, b.value, c.value
+
+    def set_reg_rooted_threshold(self, nbytes: int) -> int:
+        """vcclCommSetRegRootedThreshold: every rank alike, outside a group; the effective value."""
+        eff = ctypes.c_int64()
+        check(lib().vcclCommSetRegRootedThreshold(self.handle, nbytes, ctypes.byref(eff)),
+              "vcclCommSetRegRootedThreshold")
         return eff.value
 
     def reg_a2a_stats(self) -> tuple[int, int, int]:
