@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """One rank of the zero-copy direct tests (tests/test_gpu_direct_reg.py).
 
-argv: rank nranks uid_hex case        (case "single": one process, ncclCommInitAll)
+argv: rank nranks uid_hex case [outdir]   (case "single": one process, ncclCommInitAll;
+                                           case "payload" saves its outputs to outdir/rank<r>.npz)
 The parent sets the shared-GPU geometry of the all-to-all tests plus
 VCCL_REG_THRESHOLD=32768 (or leaves it out, case "off").  A call is run twice:
 on registered buffers (the zero-copy path) and on unregistered copies of the
@@ -22,6 +23,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from tests import _mp  # noqa: E402
+from tests import _payloads as P  # noqa: E402
 from vccl_amd import nccl  # noqa: E402
 
 U8, I32, F32, BF16 = nccl.ncclUint8, nccl.ncclInt32, nccl.ncclFloat32, nccl.ncclBfloat16
@@ -105,20 +107,26 @@ class Buf:
 
 class Call:
     """One collective on buffers of its own.  spec = (coll, dt, op, count,
-    in_place, off): count as the API takes it (RS recvcount, AG sendcount)."""
+    in_place, off): count as the API takes it (RS recvcount, AG sendcount).
+    gen(dt, op, count, rank, n) -> bytes replaces make_input; such a call knows
+    no exact value (want = None: its fold order matters, the parent checks it)."""
 
-    def __init__(self, rank, n, spec, tag):
+    def __init__(self, rank, n, spec, tag, gen=None):
         self.rank, self.n, self.spec = rank, n, spec
         coll, dt, op, count, inplace, off = spec
         esz = nccl.TYPE_SIZE[dt]
-        rows = [make_input(dt, op, count * (n if coll == RS else 1), r, tag) for r in range(n)]
+        total = count * (n if coll == RS else 1)
+        if gen is not None:
+            rows = [gen(dt, op, total, r, n) for r in range(n)]
+        else:
+            rows = [make_input(dt, op, total, r, tag) for r in range(n)]
         mine = rows[rank]
         if coll == AR:
             self.recv = Buf(count * esz, off)
             self.send = self.recv if inplace else Buf(count * esz, off)
             self.send.put(mine)
             self.sptr, self.rptr = self.send.ptr, self.recv.ptr
-            self.want, self.at = exact(dt, op, rows), 0
+            self.want, self.at = (None if gen is not None else exact(dt, op, rows)), 0
         elif coll == RS:
             blk = count * esz
             self.send = Buf(n * blk, off)
@@ -126,7 +134,7 @@ class Call:
             self.recv = self.send if inplace else Buf(blk, off)
             self.sptr = self.send.ptr
             self.rptr = self.send.ptr + rank * blk if inplace else self.recv.ptr
-            w = exact(dt, op, rows)
+            w = None if gen is not None else exact(dt, op, rows)
             self.want, self.at = (None if w is None else w[rank * blk:(rank + 1) * blk]), (rank * blk if inplace else 0)
         else:
             blk = count * esz
@@ -144,6 +152,11 @@ class Call:
 
     def bufs(self):
         return [self.send] if self.send is self.recv else [self.send, self.recv]
+
+    def output(self):
+        """The call's output bytes (all-reduce: count elements, reduce-scatter: my block)."""
+        coll, dt, _, count, _, _ = self.spec
+        return self.recv.data()[self.at:self.at + count * nccl.TYPE_SIZE[dt]].copy()
 
     def refill(self, tag):
         """Fresh input in the same buffers (graph replays)."""
@@ -483,6 +496,48 @@ def case_off(comm, rank, n, sp):
     return bad
 
 
+# Order-sensitive data (tests/_payloads.py): the zero-copy kernels promise the
+# ring's owner-map fold order; small integers could not tell any order apart.
+PAYLOAD_SEED = P.SEED + 2
+PAYLOAD_SPECS = [(AR, F32, SUM, 8209, True, 0), (AR, F32, SUM, 8209, False, 4), (AR, BF16, SUM, 16_411, False, 0),
+                 (AR, BF16, AVG, 16_411, False, 0), (AR, F32, PROD, 8209, False, 0), (RS, F32, SUM, 8209, False, 0),
+                 (RS, BF16, SUM, 8209, True, 0)]
+
+
+def payload_input(dt, op, count, rank, n):
+    return P.hard_input(dt, op, count, rank, n, PAYLOAD_SEED).view(np.uint8)
+
+
+def case_payload(comm, rank, n, sp, res):
+    """Every PAYLOAD_SPECS call registered and unregistered: guards intact, the
+    two bit-identical, every call eligible (zero-copy, its twin the fallback);
+    both outputs go to `res` for the parent's oracle check."""
+    st = Stats(comm)
+    zc = [Call(rank, n, s, 1300 + i, gen=payload_input) for i, s in enumerate(PAYLOAD_SPECS)]
+    fb = [Call(rank, n, s, 1300 + i, gen=payload_input) for i, s in enumerate(PAYLOAD_SPECS)]
+    for c in zc:
+        for b in c.bufs():
+            b.register(comm)
+    warmup(comm, sp)
+    for a, b in zip(zc, fb):
+        a.issue(comm, sp)
+        b.issue(comm, sp)
+        st.expect(a, True)
+        st.expect(b, False)
+    torch.cuda.synchronize()
+    bad = []
+    for i, (a, b) in enumerate(zip(zc, fb)):
+        bad += [(PAYLOAD_SPECS[i], w) for w in a.check(b) + ["staged: " + w for w in b.check()]]
+        res[f"zc{i}"], res[f"fb{i}"] = a.output(), b.output()
+    for c in zc:
+        for b in c.bufs():
+            b.deregister(comm)
+    k = len(PAYLOAD_SPECS)
+    if st.want != [2 * k, k, k]:
+        bad.append(("planned", st.want))
+    return bad + st.bad()
+
+
 CASES = {"allreduce": case_allreduce, "reducescatter": case_reducescatter, "allgather": case_allgather,
          "mixed": case_mixed, "reregister": case_reregister, "b2b": case_b2b, "capture": case_capture,
          "wrap": case_wrap, "fences": case_fences, "off": case_off}
@@ -551,7 +606,12 @@ def main():
         _mp.bind(rank, n)
         comm = nccl.Comm.init_rank(n, uid, rank)
         sp = torch.cuda.current_stream().cuda_stream
-        bad = CASES[case](comm, rank, n, sp)
+        if case == "payload":
+            res = {}
+            bad = case_payload(comm, rank, n, sp, res)
+            np.savez(os.path.join(sys.argv[5], f"rank{rank}.npz"), **res)
+        else:
+            bad = CASES[case](comm, rank, n, sp)
         torch.cuda.synchronize()
         err = comm.async_error()
         comm.destroy()

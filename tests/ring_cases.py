@@ -221,6 +221,22 @@ def expected_ar(op, dt, ins, n_ranks, nch, slot_bytes, ll_max, direct_max, direc
                                     work=work)
 
 
+def expected_on_path(path, coll, op, dt, ins, nch, slot_bytes, root=None, nthreads=512):
+    """Expected output(s) of one call whose path was forced (vcclCommSetAlgo):
+    path "ll" | "direct" | "ring" | "ll128", coll "ar" (one array) | "rs" (one
+    per rank) | "red" (root's).  LL: the chain fold (all-reduce) or the LL
+    partition's ring fold; ring and direct: the SIMPLE ring's fold; LL128:
+    its partition's."""
+    n = len(ins)
+    proto = {"ll": _ring.S.PROTO_LL, "ll128": _ring.S.PROTO_LL128}.get(path, _ring.S.PROTO_SIMPLE)
+    if coll == "ar":
+        return expected_ar(op, dt, ins, n, nch, slot_bytes, 0, 0, 0, nthreads, proto,
+                           path="ll" if path == "ll" else "ring")
+    if coll == "rs":
+        return _ring.expected_reducescatter(op, dt, ins, nch, slot_bytes, nthreads=nthreads, proto=proto)
+    return _ring.expected_reduce(op, dt, ins, root, nch, slot_bytes, nthreads=nthreads, proto=proto)
+
+
 def expected(case_idx, n_ranks, nch, slot_bytes, ll_max=0, direct_max=0, direct_chunk=16 << 20,
              nthreads=512, proto=2, chain=None, ll_rs_max=None):
     """proto: the ring's protocol (2 SIMPLE, 1 LL128 — VCCL's LL128 partition)."""

@@ -30,7 +30,7 @@ CLEARED = ("REG_THRESHOLD", "DIRECT_A2A_THRESHOLD", "LL_A2A_THRESHOLD", "LL_ROOT
            "DIRECT_ROOTED_THRESHOLD", "FENCES")
 
 
-def run_case(n, case, extra=REG, single=False):
+def run_case(n, case, extra=REG, single=False, outdir=None):
     hexid = nccl.unique_id_to_bytes(nccl.get_unique_id()).hex()
     env = dict(os.environ)
     for k in CLEARED:
@@ -42,7 +42,7 @@ def run_case(n, case, extra=REG, single=False):
     env["VCCL_SPIN_TIMEOUT_S"] = "20"
     env.update(extra)
     worker = os.path.join(ROOT, "tests", "mp_direct_reg_worker.py")
-    procs = [subprocess.Popen([sys.executable, worker, str(r), str(n), hexid, case], env=env,
+    procs = [subprocess.Popen([sys.executable, worker, str(r), str(n), hexid, case] + ([outdir] if outdir else []), env=env,
                               stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(1 if single else n)]
     outs = [p.communicate(timeout=300)[0].decode(errors="replace")[-2000:] for p in procs]
     assert [p.returncode for p in procs] == [0] * len(procs), "\n".join(outs)
@@ -123,3 +123,37 @@ def test_off_switches(extra):
     NCCL_ALGO: *handle == buff, the stats all zero, the call takes today's
     path, and vcclCommSetRegThreshold stays at 0 (no registry to switch on)."""
     run_case(2, "off", extra=extra)
+
+
+@pytest.mark.parametrize("n", [2, 3, 4])
+def test_payload_fold_order(n):
+    """Order-sensitive payloads (tests/_payloads.py hard_input: specials
+    between finite values of 21 binades) through f32 / bf16 sum, bf16 avg and
+    f32 prod all-reduces and f32 / bf16 sum reduce-scatters, registered and
+    unregistered: the worker holds the two bit-identical and counts the
+    zero-copy and fallback outcomes; here both are held bit-exact to the ring's
+    owner-map fold on GEOM's 14 channels, 256 KiB slots and 512 threads — the
+    order the zero-copy kernels' header comments promise."""
+    import tempfile
+
+    import numpy as np
+
+    from tests import _payloads as P
+    from tests import _ring
+    from tests._util import assert_bitexact
+    from tests.mp_direct_reg_worker import AR, PAYLOAD_SEED, PAYLOAD_SPECS
+    with tempfile.TemporaryDirectory() as d:
+        run_case(n, "payload", outdir=d)
+        res = [np.load(os.path.join(d, f"rank{r}.npz")) for r in range(n)]
+        for i, (coll, dt, op, count, _, _) in enumerate(PAYLOAD_SPECS):
+            total = count * (1 if coll == AR else n)
+            ins = [P.hard_input(dt, op, total, r, n, PAYLOAD_SEED) for r in range(n)]
+            if coll == AR:
+                exp = [_ring.expected_allreduce(op, dt, ins, 14, 256 << 10, nthreads=512)] * n
+            else:
+                exp = _ring.expected_reducescatter(op, dt, ins, 14, 256 << 10, nthreads=512)
+            for r in range(n):
+                P.assert_cap(dt, exp[r], f"spec {i} n={n} rank {r}")
+                for key in ("zc", "fb"):
+                    got = res[r][f"{key}{i}"].view(ins[0].dtype)
+                    assert_bitexact(dt, got, exp[r], what=f"{key} spec {i} {PAYLOAD_SPECS[i]} n={n} rank {r}")

@@ -5,14 +5,16 @@
   several destinations, in-place operation;
 * full-size (256 MiB, BASELINE config 2) 2-source f32 sum: bit-exact to
   numpy's a + b;
-* C-ABI error behaviour (invalid op/type/counts).
+* C-ABI error behaviour (invalid op/type/counts);
+* every pair of each float type's special values through the pack forms and
+  through the per-element functors, and integer avg at its quotient boundaries.
 """
 import numpy as np
 import pytest
 import torch
 
 from oracle import oracle as O
-from tests._util import FLOAT_TYPES, assert_bitexact, golden_rc_cases
+from tests._util import FLOAT_TYPES, assert_bitexact, bits, golden_rc_cases, to_f64
 
 pytestmark = pytest.mark.gpu
 
@@ -283,3 +285,68 @@ def test_lds_staged_variant():
                "order": 2}
         got = _run(0, 7, 0, [a, b], config=cfg)[0]
         assert np.array_equal(got.view(np.uint32), (a + b).view(np.uint32)), (n, grid, st)
+
+
+@pytest.mark.parametrize("t", FLOAT_TYPES)
+@pytest.mark.parametrize("op", [0, 1, 2, 3, 4])
+def test_element_path_special_pairs(t, op):
+    """Every pair of the type's specials (tests/_payloads.py: NaNs, infinities,
+    signed zeros, subnormals, overflow and cancellation pairs, ties) through
+    both forms of the arithmetic: aligned (16-byte packs, pack_reduce), and
+    the first 960 pairs as one launch per 15-element slice into two
+    destinations at different sub-16-byte offsets, so heads and tails run the
+    per-element functors (rc_elems).  Both bit-exact to the oracle, and equal
+    to each other bit for bit wherever the result is not a NaN."""
+    from tests import _payloads as P
+    a, b = P.special_pairs(t, op)
+    dev_op, arg, pre, post = _dev_args(op, t, 2)
+    exp = O.reduce_copy(dev_op, t, arg, [a, b], pre_op_args=[arg] * pre, post_op=post)[0]
+    assert 4 * P.classes(t, exp)["nan"] <= exp.size
+    packs = _run(dev_op, t, arg, [a, b], pre=pre, post=post)[0]
+    assert_bitexact(t, packs, exp, minmax=op in (2, 3), what=f"t{t} op{op} aligned")
+    n, step = 960, 15
+    sz = a.dtype.itemsize
+    doffs = (sz, (3 * sz) % 16) if sz < 8 else (8, 0)
+    (ta, pa), (tb, pb) = to_dev(a[:n]), to_dev(b[:n])
+    outs = [empty_dev(n * sz, offset=o) for o in doffs]
+    for lo in range(0, n, step):
+        nccl.reduce_copy(dev_op, t, arg, [pa + lo * sz, pb + lo * sz], [p + lo * sz for _, p in outs], step,
+                         stream_ptr(), pre_op_srcs=pre, post_op=post)
+    torch.cuda.synchronize()
+    for (tt, _), o in zip(outs, doffs):
+        elems = from_dev(tt, a.dtype, n, o)
+        assert_bitexact(t, elems, exp[:n], minmax=op in (2, 3), what=f"t{t} op{op} slices at +{o}")
+        raw = tt.cpu().numpy()
+        assert (raw[:o] == 0xA5).all() and (raw[o + n * sz:] == 0xA5).all(), "guard bytes written"
+        notnan = ~np.isnan(to_f64(t, exp[:n]))
+        assert np.array_equal(bits(elems)[notnan], bits(packs[:n])[notnan]), f"t{t} op{op}: packs != elements"
+
+
+@pytest.mark.parametrize("t", [0, 1, 2, 3, 4, 5])
+def test_sumpostdiv_boundaries(t):
+    """Integer avg (SumPostDiv: reciprocal multiply + one fix-up) at the
+    dividends where a quotient changes: every byte value for i8 / u8; for the
+    wider types k*d - 1, k*d, k*d + 1 around 0, the signed minimum and maximum
+    and the unsigned maximum.  Divisors 2..8 (d sources, all but the first
+    zero), bit-exact to the oracle."""
+    npdt = np.dtype(O.NP_DTYPE[t])
+    nbits = 8 * npdt.itemsize
+    mask = (1 << nbits) - 1
+    for d in range(2, 9):
+        if nbits == 8:
+            vals = list(range(256))
+        else:
+            vals = []
+            for centre in (0, -(1 << (nbits - 1)), (1 << (nbits - 1)) - 1, mask):
+                for k in (centre // d - 1, centre // d, centre // d + 1):
+                    vals += [k * d - 1, k * d, k * d + 1]
+        x = np.array([v & mask for v in vals], dtype=np.uint64).astype(bits(np.zeros(1, npdt)).dtype).view(npdt)
+        srcs = [x] + [np.zeros_like(x)] * (d - 1)
+        dev_op, arg, pre, post = _dev_args(4, t, d)
+        assert dev_op == nccl.vcclDevSumPostDiv and post and arg >> 1 == d
+        got = _run(dev_op, t, arg, srcs, pre=pre, post=post)[0]
+        exp = O.reduce_copy(dev_op, t, arg, srcs, post_op=True)[0]
+        assert_bitexact(t, got, exp, what=f"t{t} d{d}")
+        # the oracle's quotient is the truncating one
+        sx = [int(v) for v in x.tolist()]
+        assert [int(v) for v in exp.tolist()] == [abs(v) // d * (1 if v >= 0 else -1) for v in sx]
