@@ -519,6 +519,40 @@ ncclResult_t vcclP2pPlan(int rank, int nRanks, int nCalls, const int* kinds, con
                          size_t stepBytes, int gMin, int gCap, int maxWorks, int cap, int* nItems,
                          int* nWgs, int64_t* items);
 
+/* LL protocol for small ncclSend / ncclRecv messages on per-pair LL FIFOs
+ * (opt-in).
+ * vcclP2pLLMax: a comm's VCCL_P2P_LL_THRESHOLD (bytes per message; negative:
+ * from the environment) as it takes effect (host only): 0 with an LL step
+ * (stepBytes, VCCL_P2P_LL_STEP_BYTES) that is not a positive multiple of 8, with
+ * protocol LL excluded by NCCL_PROTO (llAllowed 0), with a peer behind the net
+ * proxy, with fewer than 2 or more than 8 ranks, or without point-to-point
+ * connections; else the threshold itself.
+ * vcclP2pPlanEx: vcclP2pPlan with LL messages (host only): a message of B bytes
+ * with 0 < B <= llMax is ONE item of kind 3 (LL send) / 4 (LL recv), part 0, on
+ * the pair's LL connection, its steps ceil(B / llStepBytes) (a positive multiple
+ * of 8 when llMax > 0); every other message, the empty one included, is planned
+ * as vcclP2pPlan plans it, and llMax 0 IS vcclP2pPlan.
+ * vcclCommP2pStats: cumulative, per ncclSend / ncclRecv (and per residual pair
+ * of an all-to-all) planned on this comm: those that went as LL messages and
+ * the others (empty messages and self pairs included).  Either may be NULL.
+ * vcclCommSetP2pLLThreshold: re-derives the threshold on a live comm from
+ * `bytes`; *effective (may be NULL) = the result.  A comm initialised with the
+ * threshold at 0 has no LL FIFOs and stays at 0.  Every rank must call it
+ * alike, outside a group.
+ * vcclCommDebugSetP2pLLSteps: sets every LL connection's send step, recv step
+ * and head on this rank to `step` (tests of the 32-bit flag wrap; the
+ * counterpart of vcclCommDebugSetEpochs).  Collective: every rank calls it at
+ * the same time with the same step and nothing in flight. */
+ncclResult_t vcclP2pLLMax(int64_t threshold, int64_t stepBytes, int llAllowed, int anyNet, int nRanks, int hasP2p,
+                          int64_t* effective);
+ncclResult_t vcclP2pPlanEx(int rank, int nRanks, int nCalls, const int* kinds, const int* peers,
+                           const size_t* bytes, const uint64_t* buffs, int parts, size_t minPartBytes,
+                           size_t stepBytes, int64_t llMax, int64_t llStepBytes, int gMin, int gCap, int maxWorks,
+                           int cap, int* nItems, int* nWgs, int64_t* items);
+ncclResult_t vcclCommP2pStats(ncclComm_t comm, unsigned long long* llMessages, unsigned long long* fifoMessages);
+ncclResult_t vcclCommSetP2pLLThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
+ncclResult_t vcclCommDebugSetP2pLLSteps(ncclComm_t comm, uint64_t step);
+
 #ifdef __cplusplus
 }
 #endif

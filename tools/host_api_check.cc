@@ -254,6 +254,23 @@ int main() {
         EXPECT(it[10] > 0 && it[9] + it[10] <= (int64_t)nb[it[7]]);
       }
     }
+    // the same group with LL messages (vcclP2pPlanEx): never more items, LL items whole and in ceil(B / step) steps
+    const int64_t llMax = pick({0, 17, 4096, 65540});
+    int nLL = -1;
+    const ncclResult_t rl = vcclP2pPlanEx(rank, n, k, kinds.data(), peers.data(), nb.data(), nullptr, prt, 4096, 16384,
+                                          llMax, 1024, 1, (int)pick({0, 1, 3}), maxWorks, k * prt, &nLL, &nWgs,
+                                          items.data());
+    EXPECT(rl == r);
+    if (rl == ncclSuccess) {
+      EXPECT(nLL >= 0 && nLL <= nItems);
+      for (int i = 0; i < nLL; i++) {
+        const int64_t* it = &items[12 * (size_t)i];
+        EXPECT(it[2] >= 0 && it[2] <= 4 && it[1] >= 0 && it[1] < 2 * nWgs && it[7] >= 0 && it[7] < k);
+        if (it[2] >= 3)
+          EXPECT(it[5] == 0 && it[9] == 0 && it[10] == (int64_t)nb[it[7]] && it[10] <= llMax &&
+                 it[11] == (it[10] + 1023) / 1024 && it[6] != rank);
+      }
+    }
     p2pPlans++;
   }
   EXPECT(ncclSend(nullptr, 4, ncclFloat32, 0, nullptr, nullptr) == ncclInvalidUsage);

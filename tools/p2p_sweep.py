@@ -11,6 +11,14 @@ against), and ncclAllToAll at 4 and 8 ranks.  Every row is byte-checked.
 run.)  The P2P knobs of the environment (NCCL_P2P_NVL_CHUNKSIZE, ...) reach the
 ranks unchanged.
 
+    python tools/p2p_sweep.py --ll [--steps 50] [--max-bytes 65536]
+
+runs only the LL comparison: one 2-rank comm initialised with
+VCCL_P2P_LL_THRESHOLD = --max-bytes (default 64 KiB); per size five repeats, each
+timing the send with the threshold at 0 (proto "fifo": the parent commit's path)
+and then at its value (proto "ll") through vcclCommSetP2pLLThreshold, so both
+protocols alternate inside one run; then the broadcast band as above.
+
 The parent spawns the rank processes (bench.py's launcher; ranks share a GPU
 when the box has fewer than ranks) and prints one JSON line per row: us per
 call (max over ranks) and GB/s of payload.  Measurement tool, not product
@@ -31,8 +39,9 @@ def arg(name, default):
 
 
 MIN_BYTES = int(arg("--min-bytes", 8))
-MAX_BYTES = int(arg("--max-bytes", 256 << 20))
-STEPS = int(arg("--steps", 10))
+LL = "--ll" in sys.argv
+MAX_BYTES = int(arg("--max-bytes", 64 << 10 if LL else 256 << 20))
+STEPS = int(arg("--steps", 50 if LL else 10))
 SKIP = set(arg("--skip", "").split(","))
 BCAST_PARTS = 8
 
@@ -58,6 +67,9 @@ def parent():
                      {"VCCL_P2P_PARTS": str(BCAST_PARTS), "VCCL_NCHANNELS": str(BCAST_PARTS)}))
     if "a2a" not in SKIP:
         jobs += [(n, "a2a", {}) for n in (4, 8)]
+    if LL:
+        jobs = [(2, "send-ll+bcast", {"VCCL_P2P_PARTS": str(BCAST_PARTS), "VCCL_NCHANNELS": str(BCAST_PARTS),
+                                      "VCCL_P2P_LL_THRESHOLD": str(MAX_BYTES)})]
     rc = 0
     for n, mode, extra in jobs:
         env = dict(os.environ)
@@ -127,9 +139,20 @@ def child():
                 fn = lambda: comm.send(src.data_ptr(), nb, U8, 1, sp)  # noqa: E731
             else:
                 fn = lambda: comm.recv(dst.data_ptr(), nb, U8, 0, sp)  # noqa: E731
-            us = timed(fn, STEPS, torch.cuda.synchronize)
-            ok = rank == 0 or torch.equal(dst, src)
-            good &= row(op="send", ranks=world, parts=parts, bytes=nb, us=us, ok=ok)
+            # (repeat, threshold): one plain row, or five fifo / ll pairs on the one comm
+            runs = [(rep, t) for rep in range(5) for t in (0, MAX_BYTES)] if "-ll" in mode else [(0, None)]
+            for rep, thr in runs:
+                proto = {}
+                if thr is not None:
+                    torch.cuda.synchronize()
+                    eff = comm.set_p2p_ll_threshold(thr)
+                    assert eff == thr, f"LL threshold {thr} took effect as {eff}"
+                    proto = {"proto": "ll" if thr else "fifo", "rep": rep}
+                    dst.fill_(0xA5)
+                ll0 = comm.p2p_stats()[0]
+                us = timed(fn, STEPS, torch.cuda.synchronize)
+                ok = (rank == 0 or torch.equal(dst, src)) and (thr is None or (comm.p2p_stats()[0] > ll0) == (thr > 0))
+                good &= row(op="send", ranks=world, parts=parts, bytes=nb, us=us, ok=ok, **proto)
             if mode.endswith("bcast"):
                 for rep in range(5):
                     out = torch.full((nb,), 0x5A, dtype=torch.uint8, device="cuda")

@@ -18,7 +18,13 @@
 // branches come with it.  Slots are used from offset 0, so only the user
 // pointer's own misalignment reaches the engine's realigning path, on each
 // side independently.
+//
+// A message of at most the comm's LL threshold (opt-in, VCCL_P2P_LL_THRESHOLD)
+// arrives as one kP2pLLSend / kP2pLLRecv item instead and runs the LL step of
+// p2p_ll.hpp on the pair's LL FIFO, in the same direction-split workgroups and
+// under the same two invariants.
 #pragma once
+#include "p2p_ll.hpp"
 #include "p2p_types.hpp"
 #include "ring.hpp"
 
@@ -31,6 +37,8 @@ __device__ __forceinline__ void p2p_run(const P2pBatch& b) {
   __shared__ WaveSync ws;
   __shared__ uint64_t shStep[kP2pMaxConns];   // this direction's counters
   __shared__ uint64_t shDirty;                // connections this workgroup advanced
+  __shared__ uint64_t shLLStep[kP2pMaxRanks];  // the same for the LL connections
+  __shared__ uint32_t shLLDirty;
   const int tid = threadIdx.x;
   const int wg = blockIdx.x;
   const bool sendWg = wg < b.nSendWgs;
@@ -40,8 +48,12 @@ __device__ __forceinline__ void p2p_run(const P2pBatch& b) {
     ws.abort = 0;
     ws.poller = 0;
     shDirty = 0;
+    shLLDirty = 0;
   }
   if (tid < b.nConns && tid < kP2pMaxConns) shStep[tid] = sendWg ? b.conns[tid].sendStep : b.conns[tid].recvStep;
+  const int llTid = tid - kP2pMaxConns;  // the threads that carry the LL counters in and out
+  const bool llOwner = b.llConns && llTid >= 0 && llTid < b.nLLConns && llTid < kP2pMaxRanks;
+  if (llOwner) shLLStep[llTid] = sendWg ? b.llConns[llTid].sendStep : b.llConns[llTid].recvStep;
   const DevComm* m = b.comm;
   RingCtx r;
   r.ch = nullptr;
@@ -98,6 +110,19 @@ __device__ __forceinline__ void p2p_run(const P2pBatch& b) {
     }
     if (r.aborted()) break;
     const int ci = w.conn;
+    if (w.kind == kP2pLLSend || w.kind == kP2pLLRecv) {
+      const P2pLLConn& lc = b.llConns[ci];
+      const uint64_t at = shLLStep[ci];
+      const uint64_t to = w.kind == kP2pLLSend ? p2p_ll_send(r, lc, at, w.a, w.bytes, b.llStepLines)
+                                               : p2p_ll_recv(r, lc, at, w.b, w.bytes, b.llStepLines);
+      // every thread read `at` before the item's first barrier, as below
+      if (tid == 0) {
+        shLLStep[ci] = to;
+        shLLDirty |= 1u << ci;
+      }
+      __syncthreads();
+      continue;
+    }
     const P2pConn& c = b.conns[ci];
     const int64_t step = b.stepBytes;
     if (w.kind == kP2pSend) {
@@ -132,6 +157,10 @@ __device__ __forceinline__ void p2p_run(const P2pBatch& b) {
   if (tid < b.nConns && tid < kP2pMaxConns && ((shDirty >> tid) & 1)) {
     if (sendWg) b.conns[tid].sendStep = shStep[tid];
     else b.conns[tid].recvStep = shStep[tid];
+  }
+  if (llOwner && ((shLLDirty >> llTid) & 1)) {
+    if (sendWg) b.llConns[llTid].sendStep = shLLStep[llTid];
+    else b.llConns[llTid].recvStep = shLLStep[llTid];
   }
 }
 

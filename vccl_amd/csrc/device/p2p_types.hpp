@@ -43,7 +43,28 @@ struct P2pConn {
   uint64_t recvStep;
 };
 
-enum : int { kP2pSend = 0, kP2pRecv = 1, kP2pCopy = 2 };
+// The LL connection of an ordered pair (sender, receiver), no parts: a FIFO of
+// kSteps slots of P2pBatch::llStepLines 16-byte lines {data lo, flag, data hi,
+// flag} (ll.hpp's line) in the RECEIVER's uncached memory, and one head flag of
+// one kFlagStride line in the SENDER's memory, written by the receiver (steps
+// consumed).  No tail: a line's flag, (uint32_t)(step + 1), says it arrived
+// (p2p_ll.hpp).  One entry per peer, index peer, device-resident beside
+// P2pConn[]; the step counters persist across launches exactly as P2pConn's do.
+//
+//   LL block of a rank: [sender rank][kSteps slots][llStepLines lines] then
+//                       [peer] head of me -> peer, one kFlagStride line each
+struct P2pLLConn {
+  char* sendFifo;      // peer's LL FIFO [me] (remote)
+  uint64_t* sendHead;  // local: steps the peer consumed
+  char* recvFifo;      // my LL FIFO [peer] (local)
+  uint64_t* peerHead;  // peer's head of peer -> me (remote)
+  uint64_t sendStep;
+  uint64_t recvStep;
+};
+
+// kP2pLLSend / kP2pLLRecv: a whole message of at most the comm's LL threshold
+// on the pair's LL connection (conn = peer).
+enum : int { kP2pSend = 0, kP2pRecv = 1, kP2pCopy = 2, kP2pLLSend = 3, kP2pLLRecv = 4 };
 
 // One work item: `bytes` of one part of one message (or of a self copy).
 //   send: a = user source;  recv: b = user destination;  copy: a -> b.
@@ -51,9 +72,9 @@ struct P2pWork {
   const char* a;
   char* b;
   int64_t bytes;
-  int16_t conn;  // peer * parts + part (unused by a copy)
+  int16_t conn;  // peer * parts + part (unused by a copy); an LL item: peer
   int16_t wg;    // the workgroup that runs it
-  int8_t kind;   // kP2pSend / kP2pRecv / kP2pCopy
+  int8_t kind;   // kP2pSend / kP2pRecv / kP2pCopy / kP2pLLSend / kP2pLLRecv
   int8_t skip;   // 1 .. 8: dropped when P2pBatch::skip[skip - 1] == 1; 0: never
   int8_t pad[2];
 };
@@ -73,10 +94,13 @@ struct P2pBatch {
   // and its items here are dropped — on every rank alike, so both ends drop the
   // same matched messages.  Null: nothing is ever dropped.
   const uint32_t* skip;
+  P2pLLConn* llConns;  // device-resident, nLLConns = nRanks entries (null: no LL FIFOs, no LL item)
   int nWorks;
   int nConns;
   int stepBytes;
   int nSendWgs;
+  int nLLConns;
+  int llStepLines;     // 16-byte lines per LL slot = 8 data bytes each
   P2pWork works[kP2pMaxWorks];
 };
 static_assert(sizeof(P2pBatch) <= 4096, "kernel-argument budget");

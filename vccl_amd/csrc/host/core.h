@@ -83,7 +83,7 @@ struct NetProxy;
 // ----------------------------------------------------------------- comm
 // The buffers a rank publishes to its peers.
 enum { kMapFifo = 0, kMapFlag = 1, kMapLL = 2, kMapDirect = 3, kMapDirectFlag = 4, kMapLL128 = 5, kMapP2p = 6,
-       kMapP2pFlag = 7, kMapCount = 8 };
+       kMapP2pFlag = 7, kMapP2pLL = 8, kMapCount = 9 };
 struct PeerMap {               // what one rank published about itself
   int pid;
   int device;
@@ -140,6 +140,14 @@ struct ncclComm : vccl::CommSetup {
   char* p2pBuf = nullptr;
   char* p2pFlags = nullptr;
   vccl::P2pConn* p2pConns = nullptr;
+  // LL send / recv (p2p_types.hpp P2pLLConn): the LL FIFOs [sender][kSteps
+  // slots] and behind them the head flags [peer], one uncached block mapped by
+  // every peer; the device-resident table, one entry per peer.  All null unless
+  // VCCL_P2P_LL_THRESHOLD took effect at init.  Messages planned so far by
+  // kind, per send or recv (vcclCommP2pStats).
+  char* p2pLLBuf = nullptr;
+  vccl::P2pLLConn* p2pLLConns = nullptr;
+  uint64_t p2pLLMessages = 0, p2pFifoMessages = 0;
   // ncclCommRegister'ed buffers and the peers' imported ones (regcomm.h);
   // null unless VCCL_REG_THRESHOLD, VCCL_REG_A2A_THRESHOLD or
   // VCCL_REG_ROOTED_THRESHOLD took effect at init

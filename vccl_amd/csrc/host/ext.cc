@@ -191,14 +191,24 @@ VCCL_EXPORT ncclResult_t vcclCommGroupAlgos(ncclComm_t comm, int nCalls, const i
                            order.data(), planOf.data(), cbd.data());
 }
 
-// The point-to-point planner on explicit inputs.
-VCCL_EXPORT ncclResult_t vcclP2pPlan(int rank, int nRanks, int nCalls, const int* kinds, const int* peers,
-                                     const size_t* bytes, const uint64_t* buffs, int parts, size_t minPartBytes,
-                                     size_t stepBytes, int gMin, int gCap, int maxWorks, int cap, int* nItems,
-                                     int* nWgs, int64_t* items) {
+// A comm's VCCL_P2P_LL_THRESHOLD as it takes effect.
+VCCL_EXPORT ncclResult_t vcclP2pLLMax(int64_t threshold, int64_t stepBytes, int llAllowed, int anyNet, int nRanks,
+                                      int hasP2p, int64_t* effective) {
+  if (!effective || nRanks < 1) return ncclInvalidArgument;
+  if (threshold < 0) threshold = param_int("P2P_LL_THRESHOLD", 0);
+  *effective = (int64_t)p2p_ll_max(threshold, stepBytes, llAllowed != 0, anyNet != 0, nRanks, hasP2p != 0);
+  return ncclSuccess;
+}
+
+// The point-to-point planner on explicit inputs; llMax 0: no LL message.
+VCCL_EXPORT ncclResult_t vcclP2pPlanEx(int rank, int nRanks, int nCalls, const int* kinds, const int* peers,
+                                       const size_t* bytes, const uint64_t* buffs, int parts, size_t minPartBytes,
+                                       size_t stepBytes, int64_t llMax, int64_t llStepBytes, int gMin, int gCap,
+                                       int maxWorks, int cap, int* nItems, int* nWgs, int64_t* items) {
   if (nRanks < 1 || nRanks > kP2pMaxRanks || rank < 0 || rank >= nRanks || nCalls < 0 || (nCalls && (!kinds || !peers || !bytes)) ||
       parts < 1 || parts > kP2pMaxParts || minPartBytes < 256 || stepBytes < 4096 || stepBytes % 512 || maxWorks < 1 ||
-      maxWorks > kP2pMaxWorks || !nItems || cap < 0 || (cap && !items))
+      maxWorks > kP2pMaxWorks || !nItems || cap < 0 || (cap && !items) || llMax < 0 ||
+      (llMax > 0 && (llStepBytes < 8 || llStepBytes % 8)))
     return ncclInvalidArgument;
   std::vector<P2pCall> calls;
   for (int i = 0; i < nCalls; i++) {
@@ -207,8 +217,9 @@ VCCL_EXPORT ncclResult_t vcclP2pPlan(int rank, int nRanks, int nCalls, const int
     calls.push_back(P2pCall{kinds[i], peers[i], (int64_t)bytes[i], buffs ? buffs[i] : (uint64_t)(2 * i + 1)});
   }
   P2pPlanOut plan;
-  NCCLCHECK(p2p_plan(rank, nRanks, calls, P2pGeometry{parts, (int64_t)minPartBytes, (int64_t)stepBytes}, gMin, gCap,
-                     maxWorks, &plan));
+  NCCLCHECK(p2p_plan(rank, nRanks, calls,
+                     P2pGeometry{parts, (int64_t)minPartBytes, (int64_t)stepBytes, llMax, llMax > 0 ? llStepBytes : 0},
+                     gMin, gCap, maxWorks, &plan));
   *nItems = (int)plan.items.size();
   if (nWgs) *nWgs = plan.nWgs;
   if ((int)plan.items.size() > cap) return ncclInvalidArgument;
@@ -219,6 +230,61 @@ VCCL_EXPORT ncclResult_t vcclP2pPlan(int rank, int nRanks, int nCalls, const int
     for (int j = 0; j < 12; j++) items[12 * k + j] = v[j];
   }
   return ncclSuccess;
+}
+
+VCCL_EXPORT ncclResult_t vcclP2pPlan(int rank, int nRanks, int nCalls, const int* kinds, const int* peers,
+                                     const size_t* bytes, const uint64_t* buffs, int parts, size_t minPartBytes,
+                                     size_t stepBytes, int gMin, int gCap, int maxWorks, int cap, int* nItems,
+                                     int* nWgs, int64_t* items) {
+  return vcclP2pPlanEx(rank, nRanks, nCalls, kinds, peers, bytes, buffs, parts, minPartBytes, stepBytes, 0, 0, gMin,
+                       gCap, maxWorks, cap, nItems, nWgs, items);
+}
+
+// The sends and recvs of this comm planned so far, by kind (launch.cc launch_p2p).
+VCCL_EXPORT ncclResult_t vcclCommP2pStats(ncclComm_t comm, unsigned long long* llMessages,
+                                          unsigned long long* fifoMessages) {
+  NCCLCHECK(comm_check(comm, "vcclCommP2pStats"));
+  if (llMessages) *llMessages = comm->p2pLLMessages;
+  if (fifoMessages) *fifoMessages = comm->p2pFifoMessages;
+  return ncclSuccess;
+}
+
+// A tuning / measurement knob: every rank must call it alike, between calls.
+// A comm initialised without LL FIFOs has none to switch to and stays at 0.
+VCCL_EXPORT ncclResult_t vcclCommSetP2pLLThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective) {
+  NCCLCHECK(comm_check(comm, "vcclCommSetP2pLLThreshold"));
+  if (bytes < 0) return ncclInvalidArgument;
+  comm->p2pLLMaxBytes = p2p_ll_max_of(*comm, bytes, comm->nRanks, comm->p2pOff == kP2pOffNet,
+                                      comm->p2pConns != nullptr && comm->p2pLLConns != nullptr);
+  if (effective) *effective = (int64_t)comm->p2pLLMaxBytes;
+  return ncclSuccess;
+}
+
+// The wrap tests' knob: this rank's LL send steps, recv steps and heads all at
+// `step`, and every line of its LL FIFOs as step - 1 would have left it (flag
+// (uint32_t)step, which no receiver waits for again within 2^32 steps).
+// Collective — every rank at the same time, the same step, nothing in flight:
+// a barrier on either side of the rewrite, so no peer's last head store lands
+// behind it and no peer sends into a FIFO that is still being rewritten.
+VCCL_EXPORT ncclResult_t vcclCommDebugSetP2pLLSteps(ncclComm_t comm, uint64_t step) {
+  NCCLCHECK(comm_check(comm, "vcclCommDebugSetP2pLLSteps"));
+  if (!comm->p2pLLConns) return ncclSuccess;  // the same on every rank
+  DeviceGuard dev(comm->device, /*ignoreQuery=*/true);
+  HIPCHECK(dev.status);
+  NCCLCHECK(comm_wait_own_launches(comm));
+  NCCLCHECK(bootstrap_barrier(comm->bootstrap));
+  const int n = comm->nRanks;
+  std::vector<P2pLLConn> ll((size_t)n);
+  HIPCHECK(hipMemcpy(ll.data(), comm->p2pLLConns, sizeof(P2pLLConn) * ll.size(), hipMemcpyDeviceToHost));
+  for (P2pLLConn& c : ll) c.sendStep = c.recvStep = step;
+  HIPCHECK(hipMemcpy(comm->p2pLLConns, ll.data(), sizeof(P2pLLConn) * ll.size(), hipMemcpyHostToDevice));
+  const size_t fifo = p2p_ll_fifo_bytes(n, comm->p2pLLStepBytes);
+  HIPCHECK(hipMemsetD32((hipDeviceptr_t)comm->p2pLLBuf, (int)(uint32_t)step, fifo / 4));
+  std::vector<uint64_t> heads((size_t)n * kFlagStride / 8, 0);
+  for (int p = 0; p < n; p++) heads[(size_t)p * kFlagStride / 8] = step;
+  HIPCHECK(hipMemcpy(comm->p2pLLBuf + fifo, heads.data(), heads.size() * 8, hipMemcpyHostToDevice));
+  HIPCHECK(hipDeviceSynchronize());
+  return bootstrap_barrier(comm->bootstrap);
 }
 
 // select_algo on an explicit policy with the rooted LL and rooted direct

@@ -121,6 +121,8 @@ static void free_resources(ncclComm* c) {
   free_null(c->p2pBuf);
   free_null(c->p2pFlags);
   free_null(c->p2pConns);
+  free_null(c->p2pLLBuf);
+  free_null(c->p2pLLConns);
   free_null(c->devComm);
   free_null(c->ringTrace);
   free_null(c->devChannels);
@@ -241,6 +243,10 @@ static ncclResult_t alloc_buffers(ncclComm* c, const SetupSizes& z, PeerMap* me)
     NCCLCHECK(alloc_published(me, kMapP2p, &c->p2pBuf, z.p2pBytes, false));
     NCCLCHECK(alloc_published(me, kMapP2pFlag, &c->p2pFlags, z.p2pFlagBytes, true));
   }
+  if (z.p2pLLBytes) {  // zeroed: flag 0 is a line never written, head 0 no step consumed
+    VINFO("rank %d: alloc p2p LL %zu B (%d B of data per step)", c->rank, z.p2pLLBytes, c->p2pLLStepBytes);
+    NCCLCHECK(alloc_published(me, kMapP2pLL, &c->p2pLLBuf, z.p2pLLBytes, true));
+  }
   return ncclSuccess;
 }
 
@@ -261,6 +267,7 @@ static ncclResult_t apply_mesh(ncclComm* c, MeshSetup* mesh) {
   if (c->p2pOff) {  // a net peer: its memory is not mapped
     free_null(c->p2pBuf);
     free_null(c->p2pFlags);
+    free_null(c->p2pLLBuf);
   }
   return ncclSuccess;
 }
@@ -332,6 +339,24 @@ static ncclResult_t connect_p2p(ncclComm* c, const MeshSetup& mesh) {
     }
   HIPCHECK(hipMalloc((void**)&c->p2pConns, sizeof(P2pConn) * conns.size()));
   HIPCHECK(hipMemcpy(c->p2pConns, conns.data(), sizeof(P2pConn) * conns.size(), hipMemcpyHostToDevice));
+  // The LL connections (P2pLLConn): pair (s -> r)'s FIFO is entry s of r's
+  // block, its head flag entry r of the flags behind s's FIFOs.
+  if (!c->p2pLLBuf) return ncclSuccess;
+  std::vector<char*> llOf(n);
+  NCCLCHECK(map_all(c, kMapP2pLL, mesh.netPeer, llOf.data()));
+  const size_t perLL = p2p_ll_fifo_bytes(1, c->p2pLLStepBytes), heads = p2p_ll_fifo_bytes(n, c->p2pLLStepBytes);
+  auto head = [&](int owner, int peer) { return (uint64_t*)(llOf[owner] + heads + (size_t)peer * kFlagStride); };
+  std::vector<P2pLLConn> ll((size_t)n);
+  for (int p = 0; p < n; p++) {
+    memset(&ll[p], 0, sizeof(P2pLLConn));
+    if (p == me) continue;
+    ll[p].sendFifo = llOf[p] + (size_t)me * perLL;
+    ll[p].sendHead = head(me, p);
+    ll[p].recvFifo = llOf[me] + (size_t)p * perLL;
+    ll[p].peerHead = head(p, me);
+  }
+  HIPCHECK(hipMalloc((void**)&c->p2pLLConns, sizeof(P2pLLConn) * ll.size()));
+  HIPCHECK(hipMemcpy(c->p2pLLConns, ll.data(), sizeof(P2pLLConn) * ll.size(), hipMemcpyHostToDevice));
   return ncclSuccess;
 }
 

@@ -763,7 +763,8 @@ static ncclResult_t launch_planned(std::vector<Task>& tasks, const std::vector<i
 }
 
 // ------------------------------------------------------------ point-to-point
-static_assert(kP2pSend == 0 && kP2pRecv == 1 && kP2pCopy == 2, "P2pItem::kind is the device's work kind");
+static_assert(kP2pSend == 0 && kP2pRecv == 1 && kP2pCopy == 2 && kP2pLLSend == 3 && kP2pLLRecv == 4,
+              "P2pItem::kind is the device's work kind");
 
 ncclResult_t p2p_usable(const ncclComm* c, const char* api) {
   if (c->nRanks == 1 || c->p2pConns) return ncclSuccess;
@@ -803,13 +804,18 @@ static ncclResult_t launch_p2p(const std::vector<Task>& ts) {
   const hipStream_t s0 = ts[0].stream;
   const int n = comm->nRanks;
   const bool conns = comm->p2pConns != nullptr;
+  // LL messages only on a comm that has the LL FIFOs (VCCL_P2P_LL_THRESHOLD at init)
+  const bool ll = conns && comm->p2pLLConns != nullptr && comm->p2pLLMaxBytes > 0;
   const P2pGeometry geo{conns ? comm->p2pParts : 1, conns ? comm->p2pMinPartBytes : (int64_t)64 << 10,
-                        conns ? comm->p2pStepBytes : 512 << 10};
+                        conns ? comm->p2pStepBytes : 512 << 10, ll ? (int64_t)comm->p2pLLMaxBytes : 0,
+                        ll ? comm->p2pLLStepBytes : 0};
   std::vector<P2pCall> calls;
   for (const Task& t : ts) {
     const bool send = t.coll == kTaskSend;
     calls.push_back(P2pCall{send ? kP2pCallSend : kP2pCallRecv, t.root, (int64_t)t.count * type_size(t.datatype),
                             (uint64_t)(uintptr_t)(send ? t.sendbuff : (const void*)t.recvbuff)});
+    // as planned (a self pair is a copy; a zero-copy all-to-all may still drop its items on the device)
+    (t.root != comm->rank && p2p_is_ll(calls.back().bytes, geo) ? comm->p2pLLMessages : comm->p2pFifoMessages)++;
   }
   comm->opCount += ts.size();  // whatever the outcome
   // The grid (invariant I4): every rank's send and receive workgroups are
@@ -845,6 +851,11 @@ static ncclResult_t launch_p2p(const std::vector<Task>& ts) {
     b.nConns = conns ? n * geo.parts : 0;
     b.stepBytes = (int)geo.stepBytes;
     b.nSendWgs = plan.nWgs;
+    if (ll) {
+      b.llConns = comm->p2pLLConns;
+      b.nLLConns = n;
+      b.llStepLines = comm->p2pLLStepBytes / 8;
+    }
     const int launch = plan.items[k].launch;
     for (; k < plan.items.size() && plan.items[k].launch == launch; k++) {
       const P2pItem& it = plan.items[k];
@@ -853,11 +864,14 @@ static ncclResult_t launch_p2p(const std::vector<Task>& ts) {
       P2pWork& w = b.works[b.nWorks++];
       w.kind = (int8_t)it.kind;
       w.wg = (int16_t)it.wg;
-      w.conn = (int16_t)(it.peer * geo.parts + it.part);
+      const bool llItem = it.kind == kP2pLLSend || it.kind == kP2pLLRecv;
+      if (llItem && !ll) return ncclInternalError;
+      w.conn = (int16_t)(llItem ? it.peer : it.peer * geo.parts + it.part);
       w.bytes = it.bytes;
       w.skip = (int8_t)ts[it.call].skip;  // a copy: its send's, which is its recv's
-      if (it.kind != kP2pRecv) w.a = (const char*)ts[it.call].sendbuff + it.offset;
-      if (it.kind != kP2pSend) w.b = (char*)ts[it.kind == kP2pCopy ? it.call2 : it.call].recvbuff + it.offset;
+      if (it.kind != kP2pRecv && it.kind != kP2pLLRecv) w.a = (const char*)ts[it.call].sendbuff + it.offset;
+      if (it.kind != kP2pSend && it.kind != kP2pLLSend)
+        w.b = (char*)ts[it.kind == kP2pCopy ? it.call2 : it.call].recvbuff + it.offset;
     }
     const hipEvent_t stop = stop_event(comm, cs);
     const hipError_t e = p2p_launch(b, 2 * plan.nWgs, s0, stop);

@@ -7,6 +7,7 @@
 
 #include "../../../include/vccl_device.h"
 #include "../device/coll_types.hpp"
+#include "../device/p2p_types.hpp"
 
 namespace vccl {
 
@@ -846,6 +847,13 @@ P2pSplit p2p_split(int64_t bytes, const P2pGeometry& g) {
   return P2pSplit{(int)((bytes + len - 1) / len), len};
 }
 
+uint64_t p2p_ll_max(int64_t threshold, int64_t llStepBytes, bool llAllowed, bool anyNet, int nRanks, bool hasP2p) {
+  if (threshold <= 0 || llStepBytes < 8 || llStepBytes % 8 || !llAllowed || anyNet || nRanks < 2 ||
+      nRanks > kP2pMaxRanks || !hasP2p)
+    return 0;
+  return (uint64_t)threshold;
+}
+
 ncclResult_t p2p_plan(int rank, int nRanks, const std::vector<P2pCall>& calls, const P2pGeometry& g, int gMin,
                       int gCap, int maxWorks, P2pPlanOut* out) {
   out->items.clear();
@@ -861,8 +869,14 @@ ncclResult_t p2p_plan(int rank, int nRanks, const std::vector<P2pCall>& calls, c
     if (calls[sends[rank][s]].bytes != calls[recvs[rank][s]].bytes) return ncclInvalidUsage;
   size_t nSweeps = 0;
   for (int p = 0; p < n; p++) nSweeps = std::max({nSweeps, sends[p].size(), recvs[p].size()});
-  // a send-side / receive-side connection -> its index in order of first use
-  std::vector<int> sendIx(n * g.parts, -1), recvIx(n * g.parts, -1);
+  // a send-side / receive-side connection -> its index in order of first use;
+  // the LL connection of peer p sits behind the parts, at n * parts + p
+  std::vector<int> sendIx(n * g.parts + n, -1), recvIx(n * g.parts + n, -1);
+  // an LL message is one part of all its bytes; any other is split as always
+  auto split = [&](int c) {
+    if (c < 0) return P2pSplit{0, 0};
+    return p2p_is_ll(calls[c].bytes, g) ? P2pSplit{1, calls[c].bytes} : p2p_split(calls[c].bytes, g);
+  };
   int nSend = 0, nRecv = 0;
   for (size_t s = 0; s < nSweeps; s++) {
     for (int d = 0; d < n; d++) {
@@ -881,22 +895,24 @@ ncclResult_t p2p_plan(int rank, int nRanks, const std::vector<P2pCall>& calls, c
         }
         continue;
       }
-      const P2pSplit ss = sc >= 0 ? p2p_split(calls[sc].bytes, g) : P2pSplit{0, 0};
-      const P2pSplit rs = rc >= 0 ? p2p_split(calls[rc].bytes, g) : P2pSplit{0, 0};
+      const P2pSplit ss = split(sc), rs = split(rc);
+      const bool sll = sc >= 0 && p2p_is_ll(calls[sc].bytes, g), rll = rc >= 0 && p2p_is_ll(calls[rc].bytes, g);
       for (int q = 0; q < std::max(ss.nParts, rs.nParts); q++) {
         if (q < ss.nParts) {
           const int64_t off = q * ss.partBytes, len = std::min(ss.partBytes, calls[sc].bytes - off);
-          int& ix = sendIx[to * g.parts + q];
+          const int64_t step = sll ? g.llStepBytes : g.stepBytes;
+          int& ix = sendIx[sll ? n * g.parts + to : to * g.parts + q];
           if (ix < 0) ix = nSend++;
-          out->items.push_back(P2pItem{0, ix, 0, (int)s, d, q, to, sc, -1, off, len,
-                                       (len + g.stepBytes - 1) / g.stepBytes});
+          out->items.push_back(P2pItem{0, ix, sll ? kP2pLLSend : kP2pSend, (int)s, d, q, to, sc, -1, off, len,
+                                       (len + step - 1) / step});
         }
         if (q < rs.nParts) {
           const int64_t off = q * rs.partBytes, len = std::min(rs.partBytes, calls[rc].bytes - off);
-          int& ix = recvIx[from * g.parts + q];
+          const int64_t step = rll ? g.llStepBytes : g.stepBytes;
+          int& ix = recvIx[rll ? n * g.parts + from : from * g.parts + q];
           if (ix < 0) ix = nRecv++;
-          out->items.push_back(P2pItem{0, ix, 1, (int)s, d, q, from, rc, -1, off, len,
-                                       (len + g.stepBytes - 1) / g.stepBytes});
+          out->items.push_back(P2pItem{0, ix, rll ? kP2pLLRecv : kP2pRecv, (int)s, d, q, from, rc, -1, off, len,
+                                       (len + step - 1) / step});
         }
       }
     }
@@ -909,7 +925,8 @@ ncclResult_t p2p_plan(int rank, int nRanks, const std::vector<P2pCall>& calls, c
   out->nWgs = G;
   for (size_t k = 0; k < out->items.size(); k++) {
     P2pItem& it = out->items[k];
-    it.wg = it.kind == 1 ? G + it.wg % G : it.wg % G;  // I1: a function of the connection alone
+    const bool recv = it.kind == kP2pRecv || it.kind == kP2pLLRecv;
+    it.wg = recv ? G + it.wg % G : it.wg % G;  // I1: a function of the connection alone
     it.launch = (int)(k / (size_t)maxWorks);
   }
   out->nLaunches = (int)((out->items.size() + maxWorks - 1) / maxWorks);

@@ -441,6 +441,16 @@ ncclResult_t a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const int6
 // With I1-I3 a blocked item waits on a workgroup at a lower or equal key whose
 // own wait is on the other direction, so no cycle exists for any matched set
 // of calls, any grid, and any cut of the list into launches.
+//
+// LL messages (P2pGeometry::llMax > 0; device/p2p_ll.hpp): a message of B bytes
+// with 0 < B <= llMax travels whole — one item, part 0, kind kP2pLLSend /
+// kP2pLLRecv — on the pair's LL connection in ceil(B / llStepBytes) steps.
+// Both ends decide that from B and the two comm-wide constants alone (I3).
+// The LL connection is one more connection of the pair: its two directions get
+// workgroups of their own in order of first use like any other (I1), its items
+// sit in the list at their (sweep, round, 0) key (I2), and its credit is its
+// own head flag — so the argument above covers it word for word.  Every other
+// message, the zero-byte one included, is planned as without LL.
 enum { kP2pCallSend = 0, kP2pCallRecv = 1 };
 struct P2pCall {
   int kind;       // kP2pCallSend / kP2pCallRecv
@@ -451,7 +461,15 @@ struct P2pCall {
 struct P2pGeometry {
   int parts;
   int64_t minPartBytes, stepBytes;
+  int64_t llMax = 0;        // largest LL message (0: none)
+  int64_t llStepBytes = 0;  // data bytes per LL slot (a multiple of 8; read when llMax > 0)
 };
+// A comm's VCCL_P2P_LL_THRESHOLD (bytes per message) as it takes effect: 0 on a
+// comm without point-to-point connections, with protocol LL excluded by
+// NCCL_PROTO, with a peer behind the net proxy, with fewer than 2 or more than
+// kP2pMaxRanks ranks, or with an LL step that is not a positive multiple of 8.
+uint64_t p2p_ll_max(int64_t threshold, int64_t llStepBytes, bool llAllowed, bool anyNet, int nRanks, bool hasP2p);
+inline bool p2p_is_ll(int64_t bytes, const P2pGeometry& g) { return g.llMax > 0 && bytes > 0 && bytes <= g.llMax; }
 struct P2pSplit {
   int nParts;         // parts that carry bytes (0 for an empty message)
   int64_t partBytes;  // part q covers [q * partBytes, min(B, (q + 1) * partBytes))
@@ -459,7 +477,7 @@ struct P2pSplit {
 P2pSplit p2p_split(int64_t bytes, const P2pGeometry& g);
 struct P2pItem {
   int launch, wg;
-  int kind;  // device/p2p_types.hpp kP2pSend / kP2pRecv / kP2pCopy
+  int kind;  // device/p2p_types.hpp kP2pSend / kP2pRecv / kP2pCopy / kP2pLLSend / kP2pLLRecv
   int sweep, round, part, peer;
   int call, call2;  // the call; a copy: the send and its recv
   int64_t offset, bytes, steps;

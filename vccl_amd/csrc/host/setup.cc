@@ -383,7 +383,21 @@ ncclResult_t setup_local(int n, int minCTAs, int maxCTAs, CommSetup* s, SetupSiz
   // inbox): opt-in the same way, bytes per ordered pair, at most one region
   s->directA2aMaxBytes =
       direct_a2a_max_of(*s, param_int("DIRECT_A2A_THRESHOLD", 0), n, false, n > 1 && s->p2pOff == kP2pOn);
+  // LL send / recv (small messages on per-pair LL FIFOs, flag in the line):
+  // opt-in the same way, bytes per message; the FIFOs exist only when it is on
+  int64_t llStep = param_int("P2P_LL_STEP_BYTES", 8 << 10);
+  if (llStep < 8 || llStep % 8 || llStep > (1 << 20)) {
+    VWARN("VCCL_P2P_LL_STEP_BYTES must be a multiple of 8 from 8 to 1 MiB, using 8192");
+    llStep = 8 << 10;
+  }
+  s->p2pLLStepBytes = (int)llStep;
+  s->p2pLLMaxBytes = p2p_ll_max_of(*s, param_int("P2P_LL_THRESHOLD", 0), n, false, n > 1 && s->p2pOff == kP2pOn);
+  if (s->p2pLLMaxBytes > 0) z->p2pLLBytes = p2p_ll_fifo_bytes(n, s->p2pLLStepBytes) + (size_t)n * kFlagStride;
   return ncclSuccess;
+}
+
+size_t p2p_ll_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool hasP2p) {
+  return (size_t)p2p_ll_max(threshold, s.p2pLLStepBytes, (s.algoAllowed & kAllowLLRsAg) != 0, anyNet, nRanks, hasP2p);
 }
 
 size_t ll_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool hasP2p) {
@@ -441,6 +455,7 @@ ncclResult_t setup_mesh(int rank, const std::vector<PeerId>& peers, CommSetup* s
     // vcclCommSetAlgo(LL128) can pick a ring whose channels carry no LL128
     // slots
     if (!s->p2pOff) s->p2pOff = kP2pOffNet;  // p2p FIFOs need every peer's memory mapped too
+    s->p2pLLMaxBytes = 0;
     s->nChannels = std::max(1, std::min(s->nChannels, (int)param_int("NET_NCHANNELS", 8)));
     VINFO("rank %d: inter-node ring through the net proxy, %d channels", rank, s->nChannels);
   }

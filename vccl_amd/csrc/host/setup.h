@@ -74,6 +74,12 @@ struct CommSetup {
   // (VCCL_DIRECT_A2A_THRESHOLD, plan.h direct_a2a_max; default 0 = off; not
   // part of what vcclCommSetup reports either)
   size_t directA2aMaxBytes = 0;
+  // Largest ncclSend / ncclRecv message on the pair's LL FIFO
+  // (VCCL_P2P_LL_THRESHOLD, plan.h p2p_ll_max; default 0 = off: no LL FIFO is
+  // allocated) and the data bytes of one LL slot (VCCL_P2P_LL_STEP_BYTES, a
+  // multiple of 8); not part of what vcclCommSetup reports either
+  size_t p2pLLMaxBytes = 0;
+  int p2pLLStepBytes = 0;
 };
 enum { kP2pOn = 0, kP2pOffEnv = 1, kP2pOffRanks = 2, kP2pOffNet = 3 };
 
@@ -85,7 +91,12 @@ struct SetupSizes {
   size_t fifoBytes = 0, flagBytes = 0, llBytes = 0, inboxBytes = 0, ll128Bytes = 0;
   bool wantLL128 = false;
   size_t p2pBytes = 0, p2pFlagBytes = 0;  // the p2p receive buffer and flag block
+  size_t p2pLLBytes = 0;  // the LL FIFOs and their head flags, one block (0 unless the LL threshold took effect)
 };
+// Where the head flags start in a rank's LL block (p2p_types.hpp P2pLLConn).
+inline size_t p2p_ll_fifo_bytes(int nRanks, int llStepBytes) {
+  return (size_t)nRanks * kSteps * (size_t)(llStepBytes / 8) * 16;
+}
 // Everything one rank decides on its own, in the order the knobs have always
 // been read.  nChannels is 0 and nothing is sized at nRanks == 1.  Fails
 // with algo_proto_select's result.
@@ -97,6 +108,9 @@ size_t ll_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool any
 // CommSetup::directA2aMaxBytes for a VCCL_DIRECT_A2A_THRESHOLD of `threshold`,
 // likewise (setup_local; vcclCommSetDirectA2aThreshold).
 size_t direct_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool hasP2p);
+// CommSetup::p2pLLMaxBytes for a VCCL_P2P_LL_THRESHOLD of `threshold`, likewise
+// (setup_local; vcclCommSetP2pLLThreshold).
+size_t p2p_ll_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool hasP2p);
 
 // A comm's VCCL_REG_THRESHOLD of `threshold` as it takes effect (plan.h
 // reg_max; inbox: every peer's inbox and direct flags are mapped).

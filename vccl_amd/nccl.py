@@ -48,6 +48,9 @@ EXPORTED = [
     "ncclReduce", "ncclBcast", "ncclBroadcast", "ncclCommSplit", "ncclResetDebugInit",
     # point-to-point over per-peer FIFOs (RCCL's all-to-alls grouped from them) and its planner
     "ncclSend", "ncclRecv", "ncclAllToAll", "ncclAllToAllv", "vcclP2pPlan",
+    # LL send / recv on per-pair LL FIFOs: the threshold, the plan with LL messages, the counters, the live knob,
+    # the wrap tests' step setter
+    "vcclP2pLLMax", "vcclP2pPlanEx", "vcclCommP2pStats", "vcclCommSetP2pLLThreshold", "vcclCommDebugSetP2pLLSteps",
     # one-hop LL broadcast / reduce: the selection with its threshold, and the launch's line layout
     "vcclRootedAlgo", "vcclLLRootedPlan",
     # two-hop direct broadcast / reduce: the selection with both thresholds, and one call's geometry and steps
@@ -208,6 +211,13 @@ def lib() -> ctypes.CDLL:
                               ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int),
                               ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
         "vcclCommA2aStatsEx": [vp] + [ctypes.POINTER(ctypes.c_ulonglong)] * 5,
+        "vcclP2pLLMax": [ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int64)],
+        "vcclP2pPlanEx": [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_size),
+                          ctypes.POINTER(u64), c_int, c_size, c_size, ctypes.c_int64, ctypes.c_int64, c_int, c_int,
+                          c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_int64)],
+        "vcclCommP2pStats": [vp] + [ctypes.POINTER(ctypes.c_ulonglong)] * 2,
+        "vcclCommSetP2pLLThreshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
+        "vcclCommDebugSetP2pLLSteps": [vp, u64],
         "vcclCommSetDirectA2aThreshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
         "ncclCommRegister": [vp, vp, c_size, ctypes.POINTER(vp)],
         "ncclCommDeregister": [vp, vp],
@@ -685,19 +695,31 @@ def direct_a2a_plan(nranks: int, rank: int, send_bytes, recv_bytes, uniform: boo
             "res_sends": list(rs[:nrs.value]), "res_recvs": list(rr[:nrr.value])}
 
 
-P2P_SEND, P2P_RECV, P2P_COPY = 0, 1, 2
+P2P_SEND, P2P_RECV, P2P_COPY, P2P_LL_SEND, P2P_LL_RECV = 0, 1, 2, 3, 4
 P2P_ITEM_FIELDS = ("launch", "wg", "kind", "sweep", "round", "part", "peer", "call", "call2", "offset", "bytes",
                    "steps")
 
 
+def p2p_ll_max(threshold: int, step_bytes: int = 8 << 10, ll_allowed: bool = True, any_net: bool = False,
+               nranks: int = 2, has_p2p: bool = True) -> int:
+    """vcclP2pLLMax: VCCL_P2P_LL_THRESHOLD as a comm takes it (host only)."""
+    eff = ctypes.c_int64()
+    check(lib().vcclP2pLLMax(threshold, step_bytes, int(ll_allowed), int(any_net), nranks, int(has_p2p),
+                             ctypes.byref(eff)), "vcclP2pLLMax")
+    return eff.value
+
+
 def p2p_plan(rank: int, nranks: int, calls, parts: int = 4, min_part_bytes: int = 64 << 10,
-             step_bytes: int = 512 << 10, g_min: int = 1, g_cap: int = 0, max_works: int = 120):
+             step_bytes: int = 512 << 10, g_min: int = 1, g_cap: int = 0, max_works: int = 120,
+             ll_max: int | None = None, ll_step_bytes: int = 8 << 10):
     """vcclP2pPlan: the plan of one rank's grouped sends and recvs (host only).
     calls = [(kind P2P_SEND / P2P_RECV, peer, bytes[, buffer address])] in call
     order.  Returns (items, n_wgs): items as dicts of P2P_ITEM_FIELDS in
     execution order, n_wgs workgroups per direction (send workgroups
     [0, n_wgs), recv workgroups [n_wgs, 2 n_wgs)).  Raises VcclError
-    (ncclInvalidUsage) for an unmatched self send or recv."""
+    (ncclInvalidUsage) for an unmatched self send or recv.
+    ll_max not None: vcclP2pPlanEx — messages of 0 < bytes <= ll_max become one
+    P2P_LL_SEND / P2P_LL_RECV item of ceil(bytes / ll_step_bytes) steps."""
     n = len(calls)
     ci = ctypes.c_int * max(n, 1)
     kinds, peers = ci(*[c[0] for c in calls]), ci(*[c[1] for c in calls])
@@ -706,8 +728,14 @@ def p2p_plan(rank: int, nranks: int, calls, parts: int = 4, min_part_bytes: int 
     cap = max(1, n * parts)
     items = (ctypes.c_int64 * (12 * cap))()
     n_items, n_wgs = ctypes.c_int(), ctypes.c_int()
-    check(lib().vcclP2pPlan(rank, nranks, n, kinds, peers, nbytes, buffs, parts, min_part_bytes, step_bytes, g_min,
-                            g_cap, max_works, cap, ctypes.byref(n_items), ctypes.byref(n_wgs), items), "vcclP2pPlan")
+    if ll_max is None:
+        check(lib().vcclP2pPlan(rank, nranks, n, kinds, peers, nbytes, buffs, parts, min_part_bytes, step_bytes,
+                                g_min, g_cap, max_works, cap, ctypes.byref(n_items), ctypes.byref(n_wgs), items),
+              "vcclP2pPlan")
+    else:
+        check(lib().vcclP2pPlanEx(rank, nranks, n, kinds, peers, nbytes, buffs, parts, min_part_bytes, step_bytes,
+                                  ll_max, ll_step_bytes, g_min, g_cap, max_works, cap, ctypes.byref(n_items),
+                                  ctypes.byref(n_wgs), items), "vcclP2pPlanEx")
     return ([dict(zip(P2P_ITEM_FIELDS, items[12 * k:12 * k + 12])) for k in range(n_items.value)], n_wgs.value)
 
 
@@ -860,6 +888,25 @@ class Comm:
         arr = ctypes.c_size_t * n
         check(lib().ncclAllToAllv(send, arr(*sendcounts), arr(*sdispls), recv, arr(*recvcounts), arr(*rdispls),
                                   dtype, self.handle, stream), "ncclAllToAllv")
+
+    def p2p_stats(self) -> tuple[int, int]:
+        """vcclCommP2pStats: (sends + recvs planned as LL messages, all the others)."""
+        a, b = ctypes.c_ulonglong(), ctypes.c_ulonglong()
+        check(lib().vcclCommP2pStats(self.handle, ctypes.byref(a), ctypes.byref(b)), "vcclCommP2pStats")
+        return a.value, b.value
+
+    def set_p2p_ll_threshold(self, nbytes: int) -> int:
+        """vcclCommSetP2pLLThreshold: the largest LL send / recv message for
+        later calls (every rank alike); returns the effective threshold — 0 on a
+        comm initialised without VCCL_P2P_LL_THRESHOLD."""
+        eff = ctypes.c_int64()
+        check(lib().vcclCommSetP2pLLThreshold(self.handle, nbytes, ctypes.byref(eff)), "vcclCommSetP2pLLThreshold")
+        return eff.value
+
+    def debug_set_p2p_ll_steps(self, step: int):
+        """vcclCommDebugSetP2pLLSteps: every LL connection's counters and head
+        at `step` (wrap tests).  Collective: every rank at the same time."""
+        check(lib().vcclCommDebugSetP2pLLSteps(self.handle, step), "vcclCommDebugSetP2pLLSteps")
 
     def a2a_stats(self) -> tuple[int, int, int]:
         """vcclCommA2aStats: (LL all-to-all launches, sends + recvs of this
