@@ -69,6 +69,18 @@ ncclResult_t vcclReduceCopyEx(vcclDevRedOp_t devOp, ncclDataType_t datatype, uin
                               int nDsts, void* const* dsts, size_t nElts, hipStream_t stream,
                               const vcclLaunchConfig* config);
 
+/* The f16 / bf16 / fp8 sum accumulated in binary32:
+ * dst_j[i] = narrow((pre(src_0[i]) + pre(src_1[i])) + ...), every + a binary32
+ * add in source order, pre(x) = widen(x) * widen(scalar) on sources s <
+ * preOpSrcs (the scalar decoded from redArg as vcclDevPreMulSum decodes it),
+ * one RN-even (fp8: saturating) narrowing at the end.  devOp vcclDevSum or
+ * vcclDevPreMulSum; datatype ncclFloat16, ncclBfloat16, ncclFloat8e4m3 or
+ * ncclFloat8e5m2; anything else ncclInvalidArgument.  Counts, NULL and
+ * alignment rules as vcclReduceCopyEx; the tuned default geometry only. */
+ncclResult_t vcclReduceCopyWide(vcclDevRedOp_t devOp, ncclDataType_t datatype, uint64_t redArg,
+                                int preOpSrcs, int nSrcs, const void* const* srcs, int nDsts,
+                                void* const* dsts, size_t nElts, hipStream_t stream);
+
 /* hostToDevRedOp for built-in ops: devOp + 64-bit opArg (xormask for
  * min/max, 1/nRanks bits for float avg, nRanks<<1|signed for integer avg). */
 ncclResult_t vcclHostToDevRedOp(ncclRedOp_t op, ncclDataType_t datatype, int nRanks,

@@ -332,6 +332,15 @@ ncclResult_t vcclCommA2aStatsEx(ncclComm_t comm, unsigned long long* llLaunches,
                                 unsigned long long* directLaunches, unsigned long long* directPairs,
                                 unsigned long long* fifoPairs);
 ncclResult_t vcclCommSetDirectA2aThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
+/* fp32-accumulated sums (opt-in: VCCL_SUM_FP32=1 at init, default 0 = off;
+ * DESIGN.md section 4.17): ncclAllReduce / ncclReduceScatter with ncclSum,
+ * ncclAvg or a PreMulSum op over f16, bf16, e4m3 or e5m2 take the staged direct
+ * path at every size and fold in binary32, narrowing once.
+ *   vcclCommSetSumFp32  the same for later calls; every rank calls it alike,
+ *                    outside a group.  *effective = 0 (and nothing changes)
+ *                    without mapped inboxes, outside 2..8 ranks, with a peer
+ *                    behind the net proxy or Direct excluded by NCCL_ALGO. */
+ncclResult_t vcclCommSetSumFp32(ncclComm_t comm, int on, int* effective);
 /* Zero-copy direct all-reduce / reduce-scatter / all-gather over
  * ncclCommRegister'ed buffers (opt-in: VCCL_REG_THRESHOLD=<bytes> at init,
  * default 0 = off).

@@ -509,6 +509,27 @@ int main() {
   unsetenv("VCCL_DIRECT_A2A_THRESHOLD");
   EXPECT(vcclCommA2aStatsEx(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == ncclInvalidArgument);
   EXPECT(vcclCommSetDirectA2aThreshold(nullptr, 4096, nullptr) == ncclInvalidArgument);
+  // the wide sums: the knob without a comm, and every refusal the engine's entry point makes before a launch
+  {
+    int eff = 7;
+    EXPECT(vcclCommSetSumFp32(nullptr, 1, &eff) == ncclInvalidArgument && eff == 7);
+    char buf[64] = {};
+    const void* src[1] = {buf};
+    void* dst[1] = {buf};
+    for (int dt = 0; dt < (int)ncclNumTypes; dt++)
+      for (int op = 0; op <= (int)vcclDevSumPostDiv; op++) {
+        const bool wide = (op == vcclDevSum || op == vcclDevPreMulSum) &&
+                          (dt == ncclFloat16 || dt == ncclBfloat16 || dt == ncclFloat8e4m3 || dt == ncclFloat8e5m2);
+        // zero elements: success for a pair that has a wide kernel, before any pointer is read
+        EXPECT(vcclReduceCopyWide((vcclDevRedOp_t)op, (ncclDataType_t)dt, 0, 0, 1, src, 1, dst, 0, nullptr) ==
+               (wide ? ncclSuccess : ncclInvalidArgument));
+      }
+    EXPECT(vcclReduceCopyWide(vcclDevSum, ncclBfloat16, 0, 0, 0, src, 1, dst, 8, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclReduceCopyWide(vcclDevSum, ncclBfloat16, 0, 0, 9, src, 1, dst, 8, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclReduceCopyWide(vcclDevSum, ncclBfloat16, 0, 0, 1, nullptr, 1, dst, 8, nullptr) == ncclInvalidArgument);
+    src[0] = nullptr;
+    EXPECT(vcclReduceCopyWide(vcclDevSum, ncclBfloat16, 0, 0, 1, src, 1, dst, 8, nullptr) == ncclInvalidArgument);
+  }
   // the registration table (vcclRegTable*) against a reference model under
   // random inserts, lookups and removals, with invalid entries and handles;
   // the zero-copy threshold, eligibility and step lists on random arguments

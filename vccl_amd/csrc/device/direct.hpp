@@ -263,17 +263,13 @@ __device__ __forceinline__ void direct_rc(const Fn& fn, const char* const (&src)
     u32x4 acc[U];
 #pragma unroll
     for (int u = 0; u < U; u++) {
-      acc[u] = v[0][u];
-      if (Fn::kPreOp && preN > 0) acc[u] = pack_preop(fn, acc[u]);
+      // the pack itself, or (wide functors, ops.hpp) its elements in binary32: one source widened and added
+      // at a time, so no widened copy of v[][] is ever live
+      auto w = acc_first(fn, v[0][u], preN > 0);
 #pragma unroll
-      for (int s = 1; s < kDirectMaxRanks; s++) {
-        if (s < nS) {
-          u32x4 t = v[s][u];
-          if (Fn::kPreOp && s < preN) t = pack_preop(fn, t);
-          acc[u] = pack_reduce(fn, acc[u], t);
-        }
-      }
-      if (Fn::kPostOp && post) acc[u] = pack_postop(fn, acc[u]);
+      for (int s = 1; s < kDirectMaxRanks; s++)
+        if (s < nS) acc_add(fn, w, v[s][u], s < preN);
+      acc[u] = acc_done(fn, w, post);
     }
 #pragma unroll
     for (int d = 0; d < kDirectMaxRanks; d++) {
@@ -291,17 +287,11 @@ __device__ __forceinline__ void direct_rc(const Fn& fn, const char* const (&src)
   }
   // Element path: the < 16-byte tail.
   for (int64_t i = nPacks * 16 / (int64_t)sizeof(T) + tid; i < nElts; i += nthreads) {
-    T acc = ldT<LDP, T>(src[0], i);
-    if (Fn::kPreOp && preN > 0) acc = fn.preOp(acc);
+    auto w = elt_first(fn, ldT<LDP, T>(src[0], i), preN > 0);
 #pragma unroll
-    for (int s = 1; s < kDirectMaxRanks; s++) {
-      if (s < nS) {
-        T x = ldT<LDP, T>(src[s], i);
-        if (Fn::kPreOp && s < preN) x = fn.preOp(x);
-        acc = fn.reduce(acc, x);
-      }
-    }
-    if (Fn::kPostOp && post) acc = fn.postOp(acc);
+    for (int s = 1; s < kDirectMaxRanks; s++)
+      if (s < nS) elt_add(fn, w, ldT<LDP, T>(src[s], i), s < preN);
+    const T acc = elt_done(fn, w, post);
 #pragma unroll
     for (int d = 0; d < kDirectMaxRanks; d++) {
       if (d < nD) {
@@ -310,6 +300,21 @@ __device__ __forceinline__ void direct_rc(const Fn& fn, const char* const (&src)
       }
     }
   }
+}
+
+// The functor of a kernel's single-source copies (scatter, gather): the
+// kernel's own, or — a wide sum would widen and narrow every element, which
+// is no copy for a NaN or an infinity — the native sum of its element type.
+template <class Fn>
+__device__ __forceinline__ auto direct_copy_fn(const Fn& fn) {
+  if constexpr (is_wide_fn<Fn>()) return FnSum<typename Fn::EltType>();
+  else return fn;
+}
+// Packs per thread and source in the n-source folds: kDirectUnroll, and 1 for
+// the wide fp8 sums, whose accumulator is 16 registers per pack.
+template <class Fn>
+constexpr int direct_fold_unroll() {
+  return is_wide_fn<Fn>() && sizeof(typename Fn::EltType) == 1 ? 1 : kDirectUnroll;
 }
 
 // Copy nBytes from a 16-byte-aligned source to nD 16-byte-aligned
@@ -424,6 +429,8 @@ template <class Fn>
 __device__ void direct_allreduce_part(const DirectWork& w, uint32_t& e, int& shFail) {
   using T = typename Fn::EltType;
   const Fn fn(load_op_arg(w.redArgPtr, w.redArgBytes, w.redArg));
+  const auto cfn = direct_copy_fn(fn);  // scatter / gather copies
+  using CFn = decltype(direct_copy_fn(fn));
   const DirectPeers& P = *w.peers;
   const int n = w.nRanks, me = w.rank, b = blockIdx.x;
   const int tid = threadIdx.x, nt = blockDim.x;
@@ -461,7 +468,7 @@ __device__ void direct_allreduce_part(const DirectWork& w, uint32_t& e, int& shF
       block_of(cc, shardElts, p, &off, &len);
       const char* s[kDirectMaxRanks] = {in + off * esz};
       char* d[kDirectMaxRanks] = {P.buf[p] + direct_region_off(0, c & 1, me, n, w.regionBytes) + inOff};
-      direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+      direct_rc<CFn, kDirectCopyUnroll, kSys, kSys, kSys>(cfn, s, 1, 0, false, d, 1, len, tid, nt);
     }
   };
 
@@ -523,7 +530,7 @@ __device__ void direct_allreduce_part(const DirectWork& w, uint32_t& e, int& shF
             s[j] = q == me ? in + (off + cur) * esz
                            : myBuf + direct_region_off(0, par, q, n, w.regionBytes) + inOff + cur * esz;
           }
-          direct_rc<Fn, kDirectUnroll, kSys, kPlain, kPlain>(fn, s, n, w.preOp ? n : 0, true, d, 1,
+          direct_rc<Fn, direct_fold_unroll<Fn>(), kSys, kPlain, kPlain>(fn, s, n, w.preOp ? n : 0, true, d, 1,
                                                              end - cur, lane, 64);
         }
         // (b) broadcast: this wave reads back what it just stored (same
@@ -558,7 +565,7 @@ __device__ void direct_allreduce_part(const DirectWork& w, uint32_t& e, int& shF
         block_of(cc, shardElts, o, &off, &len);
         const char* s[kDirectMaxRanks] = {myBuf + direct_region_off(1, par, o, n, w.regionBytes) + inOff};
         char* d[kDirectMaxRanks] = {out + off * esz};
-        direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+        direct_rc<CFn, kDirectCopyUnroll, kSys, kSys, kSys>(cfn, s, 1, 0, false, d, 1, len, tid, nt);
       }
     }
     __syncthreads();  // this chunk's region reads precede later posts
@@ -588,6 +595,8 @@ __device__ void direct_reducescatter_part(const DirectWork& w, uint32_t& e, int&
   using T = typename Fn::EltType;
   constexpr int64_t esz = (int64_t)sizeof(T);
   const Fn fn(load_op_arg(w.redArgPtr, w.redArgBytes, w.redArg));
+  const auto cfn = direct_copy_fn(fn);  // scatter / gather copies
+  using CFn = decltype(direct_copy_fn(fn));
   const DirectPeers& P = *w.peers;
   const int n = w.nRanks, me = w.rank, b = blockIdx.x;
   const int tid = threadIdx.x, nt = blockDim.x;
@@ -611,7 +620,7 @@ __device__ void direct_reducescatter_part(const DirectWork& w, uint32_t& e, int&
       const int p = me + k < n ? me + k : me + k - n;
       const char* s[kDirectMaxRanks] = {in + ((int64_t)p * count + lo) * esz};
       char* d[kDirectMaxRanks] = {P.buf[p] + direct_region_off(0, 0, me, n, w.regionBytes) + rOff};
-      direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+      direct_rc<CFn, kDirectCopyUnroll, kSys, kSys, kSys>(cfn, s, 1, 0, false, d, 1, len, tid, nt);
     }
     direct_post(w, P, 0, 0, b, e);
     // Phase 2: fold per channel part in its ring's order.
@@ -630,7 +639,7 @@ __device__ void direct_reducescatter_part(const DirectWork& w, uint32_t& e, int&
           s[j] = q == me ? in + ((int64_t)me * count + cur) * esz
                          : myBuf + direct_region_off(0, 0, q, n, w.regionBytes) + ro;
         }
-        direct_rc<Fn, kDirectUnroll, kSys, kSys, kSys>(fn, s, n, w.preOp ? n : 0, true, d, 1,
+        direct_rc<Fn, direct_fold_unroll<Fn>(), kSys, kSys, kSys>(fn, s, n, w.preOp ? n : 0, true, d, 1,
                                                        end - cur, tid, nt);
         cur = end;
       }

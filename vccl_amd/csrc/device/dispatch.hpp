@@ -38,6 +38,23 @@ __host__ __device__ inline int kernel_type_of(int devOp, int type) {
   return k;
 }
 
+// The wide sums (ops.hpp FnSumWide / FnPreMulSumWide): device op codes of the
+// library's own, next to vcclDevRedOp_t's — never accepted by kernel_type_of,
+// so the public engine entry points and vcclKernelTypeOf keep refusing them.
+// A call carries one from enqueue to launch, where it selects the wide kernel
+// and, like any other op code, its own bin of the group plan.
+enum : int { OP_SUM_WIDE = 5, OP_PREMULSUM_WIDE = 6 };
+__host__ __device__ inline bool is_wide_op(int devOp) { return devOp == OP_SUM_WIDE || devOp == OP_PREMULSUM_WIDE; }
+__host__ __device__ inline int native_op_of(int devOp) {
+  return devOp == OP_SUM_WIDE ? (int)OP_SUM : devOp == OP_PREMULSUM_WIDE ? (int)OP_PREMULSUM : devOp;
+}
+// The wide counterpart of (devOp, type), or -1: Sum / PreMulSum over f16, bf16, e4m3, e5m2.
+__host__ __device__ inline int wide_op_of(int devOp, int type) {
+  if (type != T_F16 && type != T_BF16 && type != T_F8E4M3 && type != T_F8E5M2) return -1;
+  return devOp == OP_SUM ? (int)OP_SUM_WIDE : devOp == OP_PREMULSUM ? (int)OP_PREMULSUM_WIDE : -1;
+}
+constexpr bool wide_kernel_type(int k) { return k == K_F16 || k == K_BF16 || k == K_F8E4M3 || k == K_F8E5M2; }
+
 template <int K> struct KTypeOf;
 template <> struct KTypeOf<K_U8> { using T = uint8_t; };
 template <> struct KTypeOf<K_U32> { using T = uint32_t; };
@@ -64,6 +81,14 @@ inline bool dispatch_op(int devOp, F&& f) {
       if constexpr (!IsFloat<T>::value) { f.template operator()<FnSumPostDiv<T>>(); return true; }
       return false;
   }
+  return false;
+}
+
+// ... for a wide op code (T one of the four wide kernel types).
+template <class T, class F>
+inline bool dispatch_wide_op(int devOp, F&& f) {
+  if (devOp == OP_SUM_WIDE) { f.template operator()<FnSumWide<T>>(); return true; }
+  if (devOp == OP_PREMULSUM_WIDE) { f.template operator()<FnPreMulSumWide<T>>(); return true; }
   return false;
 }
 

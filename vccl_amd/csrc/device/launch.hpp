@@ -40,5 +40,10 @@ hipError_t reduce_copy_launch(int devOp, int datatype, uint64_t redArg, RCArgs a
 template <int K>
 hipError_t rc_launch(int devOp, const RCArgs& a, int64_t nElts, uint64_t redArg,
                      const LaunchGeom& lg, hipStream_t stream);
+// The wide sums (devOp OP_SUM_WIDE / OP_PREMULSUM_WIDE, K a wide kernel type):
+// the library's default geometry only.
+template <int K>
+hipError_t rc_launch_wide(int devOp, const RCArgs& a, int64_t nElts, uint64_t redArg, const LaunchGeom& lg,
+                          hipStream_t stream);
 
 }  // namespace vccl

@@ -554,4 +554,208 @@ __device__ __forceinline__ u32x4 pack_postop(const Fn& fn, u32x4 a) {
   return x.v;
 }
 
+// ---------------------------------------------------------------- wide sums
+// Opt-in counterparts of FnSum / FnPreMulSum for f16, bf16 and the two fp8
+// types: every input is widened to binary32, the inputs are
+// added left to right in binary32 and the sum is narrowed to T ONCE,
+//   y = narrow_T((pre(x_0) + pre(x_1)) + ... ),  pre(x) = widen(x) * widen(scalar),
+// where the native functors round to T after every step.  The narrowing is the
+// native functors' own: RN-even; fp8 saturating, NaN -> 0x7f.
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+// Per type: one element up / down, and the 2 or 4 elements of a 32-bit word
+// as kPairs packed binary32 pairs (element order kept) and back.
+template <typename T> struct Wide;
+template <> struct Wide<_Float16> {
+  static constexpr int kPairs = 1;
+  static __device__ __forceinline__ float up(_Float16 x) { return (float)x; }
+  static __device__ __forceinline__ _Float16 down(float f) { return (_Float16)f; }  // v_cvt_f16_f32: RN-even
+  static __device__ __forceinline__ void up_word(uint32_t w, f32x2* p) {
+    p[0] = __builtin_convertvector(__builtin_bit_cast(f16x2, w), f32x2);
+  }
+  static __device__ __forceinline__ uint32_t down_word(const f32x2* p) {
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(p[0], f16x2));
+  }
+};
+template <> struct Wide<bf16_t> {
+  static constexpr int kPairs = 1;
+  static __device__ __forceinline__ float up(bf16_t x) { return bf16_to_f32(x.bits); }
+  static __device__ __forceinline__ bf16_t down(float f) { return {f32_to_bf16(f)}; }
+  static __device__ __forceinline__ void up_word(uint32_t w, f32x2* p) {
+    p[0] = f32x2{__builtin_bit_cast(float, w << 16), __builtin_bit_cast(float, w & 0xffff0000u)};
+  }
+  static __device__ __forceinline__ uint32_t down_word(const f32x2* p) {  // v_cvt_pk_bf16_f32
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(p[0], bf16x2));
+  }
+};
+// E4M3: v_cvt_pk_f32_fp8 widens exactly (a NaN code to a NaN); down: v_med3_f32
+// clamps to +-448 (satfinite), v_cvt_pk_fp8_f32 narrows RN-even.  med3 does
+// not keep a NaN, so a NaN sum bypasses the clamp and the converter's NaN code
+// (0xff) has its sign cleared: no clamped value narrows to magnitude 0x7f.
+template <> struct Wide<f8e4m3_t> {
+  static constexpr int kPairs = 2;
+  static __device__ __forceinline__ float sat(float f) {
+    return f != f ? f : __builtin_amdgcn_fmed3f(f, -448.0f, 448.0f);
+  }
+  static __device__ __forceinline__ uint32_t canon(uint32_t r) {
+    return r & ~(((r & 0x7f7f7f7fu) + 0x01010101u) & 0x80808080u);
+  }
+  static __device__ __forceinline__ float up(f8e4m3_t x) { return __builtin_amdgcn_cvt_f32_fp8((int)x.bits, 0); }
+  static __device__ __forceinline__ f8e4m3_t down(float f) {
+    const float s = sat(f);
+    return {(uint8_t)canon((uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(s, s, 0, false) & 0xffu)};
+  }
+  static __device__ __forceinline__ void up_word(uint32_t w, f32x2* p) {
+    p[0] = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+    p[1] = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  }
+  static __device__ __forceinline__ uint32_t down_word(const f32x2* p) {
+    int r = __builtin_amdgcn_cvt_pk_fp8_f32(sat(p[0].x), sat(p[0].y), 0, false);
+    r = __builtin_amdgcn_cvt_pk_fp8_f32(sat(p[1].x), sat(p[1].y), r, true);
+    return canon((uint32_t)r);
+  }
+};
+// E5M2: v_cvt_pk_f32_bf8 / v_cvt_pk_bf8_f32; the converter returns the
+// infinity code for anything past max finite and a NaN code for NaN, so
+// satfinite and the canonical NaN are the byte-wise fix-ups of e5m2x4_add_cvt.
+template <> struct Wide<f8e5m2_t> {
+  static constexpr int kPairs = 2;
+  static __device__ __forceinline__ uint32_t fix(uint32_t r) {
+    const uint32_t mag = r & 0x7f7f7f7fu;
+    const uint32_t inf = ~((mag ^ 0x7c7c7c7cu) + 0x7f7f7f7fu) & 0x80808080u;  // byte == 0x7c
+    const uint32_t n = (mag + 0x03030303u) & 0x80808080u, n7f = n - (n >> 7);  // byte > 0x7c
+    r -= inf >> 7;
+    return (r & ~(n | n7f)) | n7f;
+  }
+  static __device__ __forceinline__ float up(f8e5m2_t x) { return __builtin_amdgcn_cvt_f32_bf8((int)x.bits, 0); }
+  static __device__ __forceinline__ f8e5m2_t down(float f) {
+    return {(uint8_t)fix((uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(f, f, 0, false) & 0xffu)};
+  }
+  static __device__ __forceinline__ void up_word(uint32_t w, f32x2* p) {
+    p[0] = __builtin_amdgcn_cvt_pk_f32_bf8((int)w, false);
+    p[1] = __builtin_amdgcn_cvt_pk_f32_bf8((int)w, true);
+  }
+  static __device__ __forceinline__ uint32_t down_word(const f32x2* p) {
+    int r = __builtin_amdgcn_cvt_pk_bf8_f32(p[0].x, p[0].y, 0, false);
+    r = __builtin_amdgcn_cvt_pk_bf8_f32(p[1].x, p[1].y, r, true);
+    return fix((uint32_t)r);
+  }
+};
+
+// The functors: what the engine reads of them is EltType, kPreOp / kPostOp,
+// kWide and `scalar` (binary32; 1 for the plain sum).  The PreMulSum scalar is
+// decoded from the op argument by the native functor and widened.
+template <typename T> struct FnSumWide {
+  using EltType = T;
+  static constexpr bool kPreOp = false, kPostOp = false, kWide = true;
+  static constexpr float scalar = 1.0f;
+  __device__ FnSumWide(uint64_t = 0) {}
+};
+template <typename T> struct FnPreMulSumWide {
+  using EltType = T;
+  static constexpr bool kPreOp = true, kPostOp = false, kWide = true;
+  float scalar;
+  __device__ FnPreMulSumWide(uint64_t arg = 0) : scalar((float)FnPreMulSum<T>(arg).scalar) {}
+};
+template <class Fn>
+constexpr bool is_wide_fn() {
+  if constexpr (requires { Fn::kWide; }) return Fn::kWide;
+  else return false;
+}
+
+// ---------------------------------------------------------------- accumulators
+// What the fold loops of reduce_copy.hpp / direct.hpp hold between sources:
+// the pack (element) itself for the native functors — acc_first / acc_add /
+// acc_done are then pack_preop / pack_reduce / pack_postop — or, for the wide
+// ones, its 8 (f16 / bf16) or 16 (fp8) elements in binary32, 4 or 8 register
+// pairs added with v_pk_add_f32.  One source is widened and added at a time;
+// `pre`: this source takes the preOp.
+template <typename T> struct WidePack {
+  f32x2 p[8 / sizeof(T)];
+};
+template <class Fn, bool W = is_wide_fn<Fn>()> struct AccOf {
+  using Pack = u32x4;
+  using Elt = typename Fn::EltType;
+};
+template <class Fn> struct AccOf<Fn, true> {
+  using Pack = WidePack<typename Fn::EltType>;
+  using Elt = float;
+};
+
+template <class Fn>
+__device__ __forceinline__ typename AccOf<Fn>::Pack acc_first(const Fn& fn, u32x4 x, bool pre) {
+  if constexpr (is_wide_fn<Fn>()) {
+    using W = Wide<typename Fn::EltType>;
+    typename AccOf<Fn>::Pack a;
+    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      W::up_word(w[i], &a.p[i * W::kPairs]);
+      if (Fn::kPreOp && pre) {
+#pragma unroll
+        for (int j = 0; j < W::kPairs; j++) a.p[i * W::kPairs + j] *= fn.scalar;
+      }
+    }
+    return a;
+  } else {
+    return Fn::kPreOp && pre ? pack_preop(fn, x) : x;
+  }
+}
+template <class Fn>
+__device__ __forceinline__ void acc_add(const Fn& fn, typename AccOf<Fn>::Pack& a, u32x4 x, bool pre) {
+  if constexpr (is_wide_fn<Fn>()) {
+    using W = Wide<typename Fn::EltType>;
+    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      f32x2 t[W::kPairs];
+      W::up_word(w[i], t);
+#pragma unroll
+      for (int j = 0; j < W::kPairs; j++) {
+        if (Fn::kPreOp && pre) t[j] *= fn.scalar;  // rounded to binary32 before the add (-ffp-contract=off)
+        a.p[i * W::kPairs + j] += t[j];
+      }
+    }
+  } else {
+    if (Fn::kPreOp && pre) x = pack_preop(fn, x);
+    a = pack_reduce(fn, a, x);
+  }
+}
+template <class Fn>
+__device__ __forceinline__ u32x4 acc_done(const Fn& fn, const typename AccOf<Fn>::Pack& a, bool post) {
+  if constexpr (is_wide_fn<Fn>()) {
+    using W = Wide<typename Fn::EltType>;
+    return u32x4{W::down_word(&a.p[0]), W::down_word(&a.p[W::kPairs]), W::down_word(&a.p[2 * W::kPairs]),
+                 W::down_word(&a.p[3 * W::kPairs])};
+  } else {
+    return Fn::kPostOp && post ? pack_postop(fn, a) : a;
+  }
+}
+// The same per element (tails and the element path).
+template <class Fn>
+__device__ __forceinline__ typename AccOf<Fn>::Elt elt_first(const Fn& fn, typename Fn::EltType x, bool pre) {
+  if constexpr (is_wide_fn<Fn>()) {
+    const float f = Wide<typename Fn::EltType>::up(x);
+    return Fn::kPreOp && pre ? f * fn.scalar : f;
+  } else {
+    return Fn::kPreOp && pre ? fn.preOp(x) : x;
+  }
+}
+template <class Fn>
+__device__ __forceinline__ void elt_add(const Fn& fn, typename AccOf<Fn>::Elt& a, typename Fn::EltType x, bool pre) {
+  if constexpr (is_wide_fn<Fn>()) {
+    float f = Wide<typename Fn::EltType>::up(x);
+    if (Fn::kPreOp && pre) f *= fn.scalar;
+    a += f;
+  } else {
+    if (Fn::kPreOp && pre) x = fn.preOp(x);
+    a = fn.reduce(a, x);
+  }
+}
+template <class Fn>
+__device__ __forceinline__ typename Fn::EltType elt_done(const Fn& fn, const typename AccOf<Fn>::Elt& a, bool post) {
+  if constexpr (is_wide_fn<Fn>()) return Wide<typename Fn::EltType>::down(a);
+  else return Fn::kPostOp && post ? fn.postOp(a) : a;
+}
+
 }  // namespace vccl

@@ -99,6 +99,43 @@ extern "C" ncclResult_t vcclReduceCopy(vcclDevRedOp_t devOp, ncclDataType_t data
                           nElts, stream, nullptr);
 }
 
+// The wide sums: default geometry, the operand rules of vcclReduceCopyEx.
+extern "C" ncclResult_t vcclReduceCopyWide(vcclDevRedOp_t devOp, ncclDataType_t datatype, uint64_t redArg,
+                                           int preOpSrcs, int nSrcs, const void* const* srcs, int nDsts,
+                                           void* const* dsts, size_t nElts, hipStream_t stream) {
+  if (nSrcs < 1 || nSrcs > kMaxSrcs || nDsts < 1 || nDsts > kMaxDsts) return ncclInvalidArgument;
+  const int wideOp = wide_op_of((int)devOp, (int)datatype);
+  if (wideOp < 0) return ncclInvalidArgument;
+  if (nElts == 0) return ncclSuccess;
+  if (srcs == nullptr || dsts == nullptr) return ncclInvalidArgument;
+  RCArgs a = {};
+  for (int s = 0; s < nSrcs; s++) {
+    if (!srcs[s]) return ncclInvalidArgument;
+    a.srcs[s] = (const char*)srcs[s];
+  }
+  for (int d = 0; d < nDsts; d++) {
+    if (!dsts[d]) return ncclInvalidArgument;
+    a.dsts[d] = (char*)dsts[d];
+  }
+  a.nSrcs = nSrcs;
+  a.nDsts = nDsts;
+  a.preOpSrcs = preOpSrcs < 0 ? 0 : preOpSrcs;
+  const int k = kernel_type_of(native_op_of(wideOp), (int)datatype);
+  a.argBytes = elt_size_of_kt(k);
+  LaunchGeom lg{kRcDefBlock, kRcDefUnroll, 1, kRcDefLd, nDsts >= 2 ? kRcDefSt2 : kRcDefSt, kRcDefOrder};
+  const int64_t hunk = (int64_t)lg.block * lg.unroll * 16;
+  lg.grid = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)nElts * a.argBytes + hunk - 1) / hunk, kRcMaxGrid));
+  hipError_t err = hipErrorInvalidValue;
+  switch (k) {
+    case K_F16: err = rc_launch_wide<K_F16>(wideOp, a, (int64_t)nElts, redArg, lg, stream); break;
+    case K_BF16: err = rc_launch_wide<K_BF16>(wideOp, a, (int64_t)nElts, redArg, lg, stream); break;
+    case K_F8E4M3: err = rc_launch_wide<K_F8E4M3>(wideOp, a, (int64_t)nElts, redArg, lg, stream); break;
+    case K_F8E5M2: err = rc_launch_wide<K_F8E5M2>(wideOp, a, (int64_t)nElts, redArg, lg, stream); break;
+  }
+  if (err == hipErrorInvalidValue) return ncclInvalidArgument;
+  return err == hipSuccess ? ncclSuccess : ncclUnhandledCudaError;
+}
+
 extern "C" int vcclKernelTypeOf(int devOp, ncclDataType_t datatype) {
   return kernel_type_of(devOp, (int)datatype);
 }

@@ -214,4 +214,28 @@ hipError_t rc_launch<VCCL_KT>(int devOp, const RCArgs& a, int64_t nElts, uint64_
   return err;
 }
 
+// The wide sums: the tuned default kernel of each operand shape, nothing else.
+#if VCCL_KT == 3 || VCCL_KT == 6 || VCCL_KT == 7 || VCCL_KT == 8
+static_assert(wide_kernel_type(VCCL_KT), "the wide kernel types");
+template <class Fn, int NS, int ND>
+static hipError_t launch_wide(const RCArgs& a, int64_t nElts, uint64_t redArg, const LaunchGeom& lg, hipStream_t s) {
+  hipLaunchKernelGGL((k_reduce_copy<Fn, NS, ND, kRcDefUnroll, rc_def_pols(ND), kRcDefOrder>), dim3(lg.grid),
+                     dim3(lg.block), 0, s, a, nElts, redArg);
+  return hipGetLastError();
+}
+template <>
+hipError_t rc_launch_wide<VCCL_KT>(int devOp, const RCArgs& a, int64_t nElts, uint64_t redArg, const LaunchGeom& lg,
+                                   hipStream_t stream) {
+  using T = typename KTypeOf<VCCL_KT>::T;
+  hipError_t err = hipErrorInvalidValue;
+  dispatch_wide_op<T>(devOp, [&]<class Fn>() {
+    if (a.nSrcs == 2 && a.nDsts == 1) err = launch_wide<Fn, 2, 1>(a, nElts, redArg, lg, stream);
+    else if (a.nSrcs == 1 && a.nDsts == 1) err = launch_wide<Fn, 1, 1>(a, nElts, redArg, lg, stream);
+    else if (a.nSrcs == 2 && a.nDsts == 2) err = launch_wide<Fn, 2, 2>(a, nElts, redArg, lg, stream);
+    else err = launch_wide<Fn, 0, 0>(a, nElts, redArg, lg, stream);
+  });
+  return err;
+}
+#endif
+
 }  // namespace vccl

@@ -230,22 +230,18 @@ __device__ __forceinline__ void rc_hunks(const Fn& fn, const RCArgs& a, int64_t 
   for (int64_t h = worker; h < nHunks; h += nWorkers) {
     const int64_t off = (h * hunkPacks + tid) * 16;
     const int64_t ustride = (int64_t)nthreads * 16;
-    u32x4 acc[UNROLL];
+    u32x4 first[UNROLL];
 #pragma unroll
-    for (int u = 0; u < UNROLL; u++) acc[u] = ld16<src_pol(POLS, 0)>(a.srcs[0], off + u * ustride);
-    if (Fn::kPreOp && a.preOpSrcs > 0) {
+    for (int u = 0; u < UNROLL; u++) first[u] = ld16<src_pol(POLS, 0)>(a.srcs[0], off + u * ustride);
+    typename AccOf<Fn>::Pack wacc[UNROLL];  // the packs themselves, or their elements in binary32 (ops.hpp)
 #pragma unroll
-      for (int u = 0; u < UNROLL; u++) acc[u] = pack_preop(fn, acc[u]);
-    }
+    for (int u = 0; u < UNROLL; u++) wacc[u] = acc_first(fn, first[u], a.preOpSrcs > 0);
     auto fold_src = [&](int s) __attribute__((always_inline)) {
       u32x4 tmp[UNROLL];
 #pragma unroll
       for (int u = 0; u < UNROLL; u++) tmp[u] = ld16_src<POLS>(a, s, off + u * ustride);
 #pragma unroll
-      for (int u = 0; u < UNROLL; u++) {
-        if (Fn::kPreOp && s < a.preOpSrcs) tmp[u] = pack_preop(fn, tmp[u]);
-        acc[u] = pack_reduce(fn, acc[u], tmp[u]);
-      }
+      for (int u = 0; u < UNROLL; u++) acc_add(fn, wacc[u], tmp[u], s < a.preOpSrcs);
     };
     if constexpr (NS > 1) {
 #pragma unroll
@@ -254,10 +250,9 @@ __device__ __forceinline__ void rc_hunks(const Fn& fn, const RCArgs& a, int64_t 
 #pragma unroll 1
       for (int s = 1; s < nS; s++) fold_src(s);
     }
-    if (Fn::kPostOp && a.postOp) {
+    u32x4 acc[UNROLL];
 #pragma unroll
-      for (int u = 0; u < UNROLL; u++) acc[u] = pack_postop(fn, acc[u]);
-    }
+    for (int u = 0; u < UNROLL; u++) acc[u] = acc_done(fn, wacc[u], a.postOp);
     auto store_dst = [&](int d) __attribute__((always_inline)) {
 #pragma unroll
       for (int u = 0; u < UNROLL; u++) st16_dst<POLS>(a, d, off + u * ustride, acc[u]);
@@ -322,15 +317,10 @@ __device__ __forceinline__ void rc_hunks_pipelined(const Fn& fn, const RCArgs& a
     u32x4 acc[UNROLL];
 #pragma unroll
     for (int u = 0; u < UNROLL; u++) {
-      acc[u] = cur[0][u];
-      if (Fn::kPreOp && a.preOpSrcs > 0) acc[u] = pack_preop(fn, acc[u]);
+      auto w = acc_first(fn, cur[0][u], a.preOpSrcs > 0);
 #pragma unroll
-      for (int s = 1; s < NS; s++) {
-        u32x4 t = cur[s][u];
-        if (Fn::kPreOp && s < a.preOpSrcs) t = pack_preop(fn, t);
-        acc[u] = pack_reduce(fn, acc[u], t);
-      }
-      if (Fn::kPostOp && a.postOp) acc[u] = pack_postop(fn, acc[u]);
+      for (int s = 1; s < NS; s++) acc_add(fn, w, cur[s][u], s < a.preOpSrcs);
+      acc[u] = acc_done(fn, w, a.postOp);
     }
     const int64_t off = (h * hunkPacks + tid) * 16;
 #pragma unroll
@@ -353,14 +343,9 @@ __device__ __forceinline__ void rc_elems(const Fn& fn, const RCArgs& a, int64_t 
                                          int64_t eEnd, int64_t gtid, int64_t gthreads) {
   using T = typename Fn::EltType;
   for (int64_t i = eBegin + gtid; i < eEnd; i += gthreads) {
-    T acc = ldT<src_pol(POLS, 0), T>(a.srcs[0], i);
-    if (Fn::kPreOp && a.preOpSrcs > 0) acc = fn.preOp(acc);
-    for (int s = 1; s < a.nSrcs; s++) {
-      T v = ldT_src<POLS, T>(a, s, i);
-      if (Fn::kPreOp && s < a.preOpSrcs) v = fn.preOp(v);
-      acc = fn.reduce(acc, v);
-    }
-    if (Fn::kPostOp && a.postOp) acc = fn.postOp(acc);
+    auto w = elt_first(fn, ldT<src_pol(POLS, 0), T>(a.srcs[0], i), a.preOpSrcs > 0);
+    for (int s = 1; s < a.nSrcs; s++) elt_add(fn, w, ldT_src<POLS, T>(a, s, i), s < a.preOpSrcs);
+    const T acc = elt_done(fn, w, a.postOp);
     for (int d = 0; d < a.nDsts; d++) stT_dst<POLS, T>(a, d, i, acc);
   }
 }
@@ -627,15 +612,10 @@ __device__ __forceinline__ void rc_hunks_shifted(const Fn& fn, const RCArgs& a, 
         if (!k[s]) return cur[s][u];
         return realign(cur[s][u], u + 1 < UNROLL ? lane0_of(cur[s][u + 1]) : extLast[s], k[s]);
       };
-      acc[u] = src(0);
-      if (Fn::kPreOp && a.preOpSrcs > 0) acc[u] = pack_preop(fn, acc[u]);
+      auto w = acc_first(fn, src(0), a.preOpSrcs > 0);
 #pragma unroll
-      for (int s = 1; s < NS; s++) {
-        u32x4 v = src(s);
-        if (Fn::kPreOp && s < a.preOpSrcs) v = pack_preop(fn, v);
-        acc[u] = pack_reduce(fn, acc[u], v);
-      }
-      if (Fn::kPostOp && a.postOp) acc[u] = pack_postop(fn, acc[u]);
+      for (int s = 1; s < NS; s++) acc_add(fn, w, src(s), s < a.preOpSrcs);
+      acc[u] = acc_done(fn, w, a.postOp);
     }
     // Halo: the previous span's last pack (pw - 1), recomputed here — the
     // same loads and fold, so the same bits — lets lane 0 store the aligned
@@ -654,15 +634,10 @@ __device__ __forceinline__ void rc_hunks_shifted(const Fn& fn, const RCArgs& a, 
           const u32x4 raw = ld16_body_src<POLS>(a, s, k[s], pw - 1, nPacks);
           return k[s] ? funnel16(raw, lane0_of(cur[s][0]), k[s]) : raw;
         };
-        halo = hsrc(0);
-        if (Fn::kPreOp && a.preOpSrcs > 0) halo = pack_preop(fn, halo);
+        auto w = acc_first(fn, hsrc(0), a.preOpSrcs > 0);
 #pragma unroll
-        for (int s = 1; s < NS; s++) {
-          u32x4 v = hsrc(s);
-          if (Fn::kPreOp && s < a.preOpSrcs) v = pack_preop(fn, v);
-          halo = pack_reduce(fn, halo, v);
-        }
-        if (Fn::kPostOp && a.postOp) halo = pack_postop(fn, halo);
+        for (int s = 1; s < NS; s++) acc_add(fn, w, hsrc(s), s < a.preOpSrcs);
+        halo = acc_done(fn, w, a.postOp);
         useHalo = true;
       }
     }
@@ -699,14 +674,9 @@ __device__ __forceinline__ void rc_hunks_shifted_rt(const Fn& fn, const RCArgs& 
       if (__lane_id() == 63) ext = ld16_succ_src<POLS>(a, s, k, (p + 1 < nPacks ? p + 1 : nPacks) * 16);
       return realign(cur, ext, k);
     };
-    u32x4 acc = load(0);
-    if (Fn::kPreOp && a.preOpSrcs > 0) acc = pack_preop(fn, acc);
-    for (int s = 1; s < a.nSrcs; s++) {
-      u32x4 v = load(s);
-      if (Fn::kPreOp && s < a.preOpSrcs) v = pack_preop(fn, v);
-      acc = pack_reduce(fn, acc, v);
-    }
-    if (Fn::kPostOp && a.postOp) acc = pack_postop(fn, acc);
+    auto w = acc_first(fn, load(0), a.preOpSrcs > 0);
+    for (int s = 1; s < a.nSrcs; s++) acc_add(fn, w, load(s), s < a.preOpSrcs);
+    const u32x4 acc = acc_done(fn, w, a.postOp);
     for (int d = 0; d < a.nDsts; d++) {
       if constexpr (DSTR)
         st16_dst_realigned<POLS>(a, d, (int)((uintptr_t)dst_ptr(a, d) & 15), p, acc, acc, false,
@@ -741,14 +711,9 @@ __device__ __forceinline__ void reduce_copy_aligned(const Fn& fn, const RCArgs& 
   // Remaining packs (< one hunk): one pack per thread, grid-strided.
   for (int64_t p = fullPacks + gtid; p < nPacks; p += gthreads) {
     const int64_t off = p * 16;
-    u32x4 acc = ld16<src_pol(POLS, 0)>(a.srcs[0], off);
-    if (Fn::kPreOp && a.preOpSrcs > 0) acc = pack_preop(fn, acc);
-    for (int s = 1; s < a.nSrcs; s++) {
-      u32x4 v = ld16_src<POLS>(a, s, off);
-      if (Fn::kPreOp && s < a.preOpSrcs) v = pack_preop(fn, v);
-      acc = pack_reduce(fn, acc, v);
-    }
-    if (Fn::kPostOp && a.postOp) acc = pack_postop(fn, acc);
+    auto w = acc_first(fn, ld16<src_pol(POLS, 0)>(a.srcs[0], off), a.preOpSrcs > 0);
+    for (int s = 1; s < a.nSrcs; s++) acc_add(fn, w, ld16_src<POLS>(a, s, off), s < a.preOpSrcs);
+    const u32x4 acc = acc_done(fn, w, a.postOp);
     for (int d = 0; d < a.nDsts; d++) st16_dst<POLS>(a, d, off, acc);
   }
   // Element tail (< 16 bytes).

@@ -238,6 +238,16 @@ hipError_t direct_launch<VCCL_KT>(int coll, int devOp, const DirectBatch& b, hip
     return hipErrorInvalidValue;
   }
   hipError_t err = hipErrorInvalidValue;
+  // the wide sums (ops.hpp): the all-reduce and the reduce-scatter over the four wide kernel types
+  if (is_wide_op(devOp)) {
+    if constexpr (wide_kernel_type(VCCL_KT)) {
+      dispatch_wide_op<T>(devOp, [&]<class Fn>() {
+        if (coll == kCollAllReduce) err = launch_k(k_direct_allreduce<Fn>, grid, block, stream, stop, b);
+        else if (coll == kCollReduceScatter) err = launch_k(k_direct_reducescatter<Fn>, grid, block, stream, stop, b);
+      });
+    }
+    return err;
+  }
   dispatch_op<T>(devOp, [&]<class Fn>() {
     if constexpr (!std::is_same<Fn, FnCopy<T>>::value) {
       err = coll == kCollAllReduce ? launch_k(k_direct_allreduce<Fn>, grid, block, stream, stop, b)

@@ -86,7 +86,9 @@ VCCL_EXPORT ncclResult_t vcclCommCollAlgo(ncclComm_t comm, int coll, size_t coun
     return ncclSuccess;
   }
   // the public collective codes are the Coll values (vccl_ext.h)
-  *algo = public_algo(select_algo(policy_of(comm), coll, type_size(datatype), (int64_t)count));
+  // VCCL_SUM_FP32: the path of the sum (or avg) the opt-in serves; any other op over these types is chosen as ever
+  const bool wide = is_wide_op(sum_fp32_op(sum_fp32_on(comm), coll, OP_SUM, datatype));
+  *algo = public_algo(wide ? (int)kAlgoDirect : select_algo(policy_of(comm), coll, type_size(datatype), (int64_t)count));
   return ncclSuccess;
 }
 
@@ -122,7 +124,8 @@ VCCL_EXPORT ncclResult_t vcclRingChunkOf(size_t count, ncclDataType_t datatype, 
 // The group planner on explicit inputs.
 static ncclResult_t group_plan_export(int nCalls, const int* colls, const size_t* counts, const int* datatypes,
                                       const int* ops, int nRanks, int nChannels, const PlanGeometry& geo,
-                                      const AlgoPolicy* pol, int* algos, int* order, int* planOf, int64_t* cbd) {
+                                      const AlgoPolicy* pol, int* algos, int* order, int* planOf, int64_t* cbd,
+                                      bool sumFp32 = false) {
   if (nCalls < 1 || !colls || !counts || !datatypes || !ops || !order || !planOf || !cbd || nRanks < 1 ||
       nChannels < 1 || nChannels > kMaxChannels || geo.stepBytes < 4096 || geo.nThreads < 64 ||
       geo.ll128StepBytes < 1920 * 16 || geo.ll128Threads < 64)
@@ -137,7 +140,7 @@ static ncclResult_t group_plan_export(int nCalls, const int* colls, const size_t
     if (!is_copy_coll(c)) NCCLCHECK(host_to_dev_redop((ncclRedOp_t)ops[i], dt, nRanks, &devOp, &arg));
     const int kt = kernel_type_of_call(c, devOp, dt);
     if (kt < 0) return ncclInvalidArgument;
-    g.push_back(group_task_of(c, counts[i], dt, devOp, kt));
+    g.push_back(group_task_of(c, counts[i], dt, sum_fp32_op(sumFp32, c, devOp, dt), kt));
   }
   GroupPlanOut p;
   group_plan(g, nRanks, nChannels, geo, pol, &p);
@@ -188,7 +191,7 @@ VCCL_EXPORT ncclResult_t vcclCommGroupAlgos(ncclComm_t comm, int nCalls, const i
   const PlanGeometry geo{comm->stepBytes, comm->nThreads, ll128 ? comm->ll128StepBytes : kDefaultLL128.stepBytes,
                          ll128 ? comm->ll128Threads : kDefaultLL128.nThreads};
   return group_plan_export(nCalls, colls, counts, datatypes, ops, comm->nRanks, comm->nChannels, geo, &pol, algos,
-                           order.data(), planOf.data(), cbd.data());
+                           order.data(), planOf.data(), cbd.data(), sum_fp32_on(comm));
 }
 
 // A comm's VCCL_P2P_LL_THRESHOLD as it takes effect.
@@ -487,6 +490,16 @@ VCCL_EXPORT ncclResult_t vcclCommSetDirectA2aThreshold(ncclComm_t comm, int64_t 
   comm->directA2aMaxBytes = direct_a2a_max_of(*comm, bytes, comm->nRanks, comm->p2pOff == kP2pOffNet,
                                               comm->p2pConns != nullptr && comm->dPeers != nullptr);
   if (effective) *effective = (int64_t)comm->directA2aMaxBytes;
+  return ncclSuccess;
+}
+
+// fp32-accumulated f16 / bf16 / fp8 sums for later calls (as VCCL_SUM_FP32 at
+// init): every rank must call it alike, outside a group.
+VCCL_EXPORT ncclResult_t vcclCommSetSumFp32(ncclComm_t comm, int on, int* effective) {
+  NCCLCHECK(comm_check(comm, "vcclCommSetSumFp32"));
+  // a comm with a net peer maps no inbox: dPeers says both
+  comm->sumFp32 = sum_fp32_of(*comm, on != 0, comm->nRanks, comm->dPeers == nullptr, comm->dPeers != nullptr);
+  if (effective) *effective = comm->sumFp32;
   return ncclSuccess;
 }
 

@@ -33,6 +33,8 @@ static_assert((int)OP_SUM == (int)vcclDevSum && (int)OP_PROD == (int)vcclDevProd
                   (int)OP_MINMAX == (int)vcclDevMinMax && (int)OP_PREMULSUM == (int)vcclDevPreMulSum &&
                   (int)OP_SUMPOSTDIV == (int)vcclDevSumPostDiv,
               "OP_* and vcclDevRedOp_t are one enumeration");
+static_assert((int)OP_SUM_WIDE == kSumWideOp && (int)OP_PREMULSUM_WIDE == kPreMulSumWideOp,
+              "the wide op codes of plan.h are dispatch.hpp's");
 
 // Order launches of one comm across different user streams (the reference
 // serialises through its internal strong stream, enqueue.cc:1445-1548).
@@ -187,7 +189,7 @@ AlgoPolicy policy_of(const ncclComm* c) {
 }
 
 int kernel_type_of_call(int coll, int devOp, ncclDataType_t datatype) {
-  return is_copy_coll(coll) ? (int)K_U8 : kernel_type_of(devOp, (int)datatype);
+  return is_copy_coll(coll) ? (int)K_U8 : kernel_type_of(native_op_of(devOp), (int)datatype);
 }
 
 // A call's partition: its place in its group's plan (launch_planned, under
@@ -210,7 +212,7 @@ static void fill_op_fields(Work& w, const Task& t) {
   w.redArg = t.arg;
   w.redArgPtr = t.argPtr;  // ncclScalarDevice: dereferenced by the kernel (nccl.h.in:255-262)
   w.redArgBytes = type_size(t.datatype);
-  w.preOp = t.devOp == OP_PREMULSUM;
+  w.preOp = native_op_of(t.devOp) == OP_PREMULSUM;
   w.nRanks = t.comm->nRanks;
 }
 
@@ -441,7 +443,7 @@ static ncclResult_t direct_work_of(const Task& t, DirectWork* out, int* ktOut, i
   w.regionBytes = comm->dRegionBytes;
   if (shard0 * esz > w.regionBytes || w.nBlocks > kDirectMaxBlocks || w.nBlocks < 1)
     return ncclInternalError;
-  const int kt = ag ? K_U8 : kernel_type_of(t.devOp, (int)t.datatype);
+  const int kt = ag ? K_U8 : kernel_type_of(native_op_of(t.devOp), (int)t.datatype);  // a wide op: its type's unit
   if (kt < 0) return ncclInvalidArgument;
   *out = w;
   *ktOut = kt;
@@ -594,6 +596,7 @@ static ncclResult_t launch_direct_reg_rooted(const Task& t, hipEvent_t stop) {
 
 // A call's path: select_algo on the comm's thresholds.
 static int choose_algo(const Task& t) {
+  if (is_wide_op(t.devOp)) return kAlgoDirect;  // the wide sums exist on the staged direct path only
   return select_algo(policy_of(t.comm), t.coll, type_size(t.datatype), (int64_t)t.count);
 }
 
@@ -602,6 +605,7 @@ constexpr int kAlgoDirectReg = 100;  // launch.cc only: one eligible call, the z
 constexpr int kAlgoDirectRegRooted = 101;  // ... a broadcast / reduce
 // The zero-copy path of a call that is eligible for one, else `algo`.
 static int reg_algo_or(const Task& t, int algo) {
+  if (is_wide_op(t.devOp)) return algo;  // the zero-copy fold is the native one: such calls do not negotiate
   return reg_task_eligible(t) ? kAlgoDirectReg : reg_rooted_task_eligible(t) ? kAlgoDirectRegRooted : algo;
 }
 static ncclResult_t launch_path(int algo, const Task* ts, int n, hipEvent_t stop) {

@@ -56,6 +56,9 @@ struct Task {
   int skip;
 };
 
+// VCCL_SUM_FP32 / vcclCommSetSumFp32 as the comm's calls take it: the setup's
+// verdict, and every peer's inbox mapped.
+inline bool sum_fp32_on(const ncclComm* c) { return c->sumFp32 != 0 && c->dPeers != nullptr; }
 // The one place that reads a comm into the planner's thresholds.
 AlgoPolicy policy_of(const ncclComm* c);
 // The kernel element type of a call (K_U8 for the byte copies), -1: no kernel.

@@ -296,6 +296,15 @@ int select_algo(const AlgoPolicy& p, int coll, int64_t eltSize, int64_t count) {
   if (directFits) return kAlgoDirect;
   return kAlgoRing;
 }
+bool sum_fp32_effective(bool on, bool inbox, bool directAllowed, bool anyNet, int nRanks) {
+  return on && inbox && directAllowed && !anyNet && nRanks >= 2 && nRanks <= kDirectMaxRanks;
+}
+int sum_fp32_op(bool effective, int coll, int devOp, ncclDataType_t datatype) {
+  if (!effective || (coll != kAllReduce && coll != kReduceScatter)) return devOp;
+  if (datatype != ncclFloat16 && datatype != ncclBfloat16 && datatype != ncclFloat8e4m3 && datatype != ncclFloat8e5m2)
+    return devOp;
+  return devOp == OP_SUM ? kSumWideOp : devOp == OP_PREMULSUM ? kPreMulSumWideOp : devOp;
+}
 uint64_t ll_rooted_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks) {
   if (threshold <= 0 || llSlotBytes <= 0 || !llAllowed || anyNet || nRanks > kOrderMaxRanks) return 0;
   return (uint64_t)std::min(threshold, llSlotBytes);
@@ -338,7 +347,8 @@ GroupTask group_task_of(int coll, size_t count, ncclDataType_t datatype, int dev
   const bool ag = is_copy_coll(coll);
   const CallSize sz = call_size(coll, count, datatype);
   const int key = (coll * 16 + (ag ? (int)OP_SUM : devOp)) * 32;
-  return GroupTask{coll, sz.count, sz.eltSize, key + (ag ? (int)ncclInt8 : (int)datatype), key + kernelType};
+  return GroupTask{coll, sz.count, sz.eltSize, key + (ag ? (int)ncclInt8 : (int)datatype), key + kernelType,
+                   !ag && is_wide_sum_op(devOp)};
 }
 uint32_t u32fp_encode(uint32_t x, int bitsPerPow2) {  // bitops.h:252-262
   const int log2x = 31 - __builtin_clz(x | 1);
@@ -383,7 +393,7 @@ void group_plan(const std::vector<GroupTask>& ts, int nRanks, int commChannels, 
       int64_t aggCount = ts[lst[a]].count;
       while (e < lst.size() && traffic[lst[e]] < 4 * traffic[lst[a]]) aggCount += ts[lst[e++]].count;
       const GroupTask& h = ts[lst[a]];
-      const int algo = pol ? select_algo(*pol, h.coll, h.eltSize, aggCount) : kAlgoRing;
+      const int algo = !pol ? kAlgoRing : h.wide ? kAlgoDirect : select_algo(*pol, h.coll, h.eltSize, aggCount);
       const int pr = proto_of_algo(algo);
       const int nc = ring_nmax_channels(h.coll, aggCount, h.eltSize, nRanks, commChannels, pr,
                                         pr == kProtoLL128 ? geo.ll128Threads : geo.nThreads);

@@ -97,6 +97,20 @@ uint64_t ll_rooted_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, b
 // proxy, or above kDirectMaxRanks ranks.
 uint64_t direct_rooted_max(int64_t threshold, bool inbox, bool directAllowed, bool anyNet, int nRanks);
 int select_algo(const AlgoPolicy& p, int coll, int64_t eltSize, int64_t count);
+// fp32-accumulated sums (VCCL_SUM_FP32 / vcclCommSetSumFp32).
+// The request as it takes effect: only where the staged direct path can run —
+// mapped inboxes, 2 .. kDirectMaxRanks ranks, no peer behind the net proxy,
+// Direct not excluded by NCCL_ALGO.
+bool sum_fp32_effective(bool on, bool inbox, bool directAllowed, bool anyNet, int nRanks);
+// The device op a call runs with: the wide op code (device/dispatch.hpp) for
+// an all-reduce or reduce-scatter with Sum / PreMulSum (ncclAvg's encoding
+// included) over f16, bf16, e4m3 or e5m2 on a comm where the opt-in is
+// effective; devOp unchanged for every other call.  A call with a wide op
+// takes the staged direct path at every size (group_plan, launch.cc
+// choose_algo) and never the zero-copy one.
+constexpr int kSumWideOp = 5, kPreMulSumWideOp = 6;  // dispatch.hpp OP_SUM_WIDE / OP_PREMULSUM_WIDE (tied in launch.cc)
+inline bool is_wide_sum_op(int devOp) { return devOp == kSumWideOp || devOp == kPreMulSumWideOp; }
+int sum_fp32_op(bool effective, int coll, int devOp, ncclDataType_t datatype);
 int proto_of_algo(int algo);
 
 struct GroupTask {
@@ -104,6 +118,7 @@ struct GroupTask {
   int64_t count, eltSize;  // AG in bytes
   int binKey;              // (func, devOp, type): ncclPrepareTasks' bins
   int funcKey;             // the device function (batches merge per function)
+  bool wide = false;       // a wide op code: the staged direct path whatever the aggregate's size
 };
 // A call as the group planner takes it.  kernelType: dispatch.hpp
 // kernel_type_of (K_U8 for a byte copy), passed in so no kernel header is

@@ -393,7 +393,14 @@ ncclResult_t setup_local(int n, int minCTAs, int maxCTAs, CommSetup* s, SetupSiz
   s->p2pLLStepBytes = (int)llStep;
   s->p2pLLMaxBytes = p2p_ll_max_of(*s, param_int("P2P_LL_THRESHOLD", 0), n, false, n > 1 && s->p2pOff == kP2pOn);
   if (s->p2pLLMaxBytes > 0) z->p2pLLBytes = p2p_ll_fifo_bytes(n, s->p2pLLStepBytes) + (size_t)n * kFlagStride;
+  // fp32-accumulated sums for f16 / bf16 / fp8 (the staged direct all-reduce
+  // and reduce-scatter at every size): opt-in, it changes the result's bits
+  s->sumFp32 = sum_fp32_of(*s, param_int("SUM_FP32", 0) != 0, n, false, s->dRegionBytes > 0);
   return ncclSuccess;
+}
+
+int sum_fp32_of(const CommSetup& s, bool on, int nRanks, bool anyNet, bool inbox) {
+  return sum_fp32_effective(on, inbox, (s.algoAllowed & kAllowDirect) != 0, anyNet, nRanks) ? 1 : 0;
 }
 
 size_t p2p_ll_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool hasP2p) {
@@ -456,6 +463,7 @@ ncclResult_t setup_mesh(int rank, const std::vector<PeerId>& peers, CommSetup* s
     // slots
     if (!s->p2pOff) s->p2pOff = kP2pOffNet;  // p2p FIFOs need every peer's memory mapped too
     s->p2pLLMaxBytes = 0;
+    s->sumFp32 = 0;
     s->nChannels = std::max(1, std::min(s->nChannels, (int)param_int("NET_NCHANNELS", 8)));
     VINFO("rank %d: inter-node ring through the net proxy, %d channels", rank, s->nChannels);
   }

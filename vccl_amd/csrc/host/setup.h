@@ -80,6 +80,11 @@ struct CommSetup {
   // multiple of 8); not part of what vcclCommSetup reports either
   size_t p2pLLMaxBytes = 0;
   int p2pLLStepBytes = 0;
+  // fp32-accumulated f16 / bf16 / fp8 sums on the staged direct all-reduce and
+  // reduce-scatter (VCCL_SUM_FP32, plan.h sum_fp32_effective; default 0 = off;
+  // not part of what vcclCommSetup reports either).  Calls also need the
+  // peers' inboxes mapped (launch.h sum_fp32_on).
+  int sumFp32 = 0;
 };
 enum { kP2pOn = 0, kP2pOffEnv = 1, kP2pOffRanks = 2, kP2pOffNet = 3 };
 
@@ -111,6 +116,10 @@ size_t direct_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool
 // CommSetup::p2pLLMaxBytes for a VCCL_P2P_LL_THRESHOLD of `threshold`, likewise
 // (setup_local; vcclCommSetP2pLLThreshold).
 size_t p2p_ll_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool hasP2p);
+
+// CommSetup::sumFp32 for a VCCL_SUM_FP32 of `on`, likewise (setup_local;
+// vcclCommSetSumFp32).
+int sum_fp32_of(const CommSetup& s, bool on, int nRanks, bool anyNet, bool inbox);
 
 // A comm's VCCL_REG_THRESHOLD of `threshold` as it takes effect (plan.h
 // reg_max; inbox: every peer's inbox and direct flags are mapped).

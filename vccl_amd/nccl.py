@@ -70,6 +70,8 @@ EXPORTED = [
     # steps, the counters, the live knob
     "vcclRegRootedMax", "vcclRegRootedEligible", "vcclRegRootedPlan", "vcclCommRegRootedStats",
     "vcclCommSetRegRootedThreshold",
+    # fp32-accumulated sums for f16 / bf16 / fp8: the engine's entry point and the comm's live knob
+    "vcclReduceCopyWide", "vcclCommSetSumFp32",
     # out of scope, exported so libnccl-linked binaries load: WARN + ncclInvalidUsage
     "ncclGroupSimulateEnd",
     # memory / registration / scalable init (what a libnccl caller such as
@@ -164,6 +166,9 @@ def lib() -> ctypes.CDLL:
                            ctypes.POINTER(vp), c_size, vp],
         "vcclReduceCopyEx": [c_int, c_int, u64, c_int, c_int, c_int, ctypes.POINTER(vp), c_int,
                              ctypes.POINTER(vp), c_size, vp, ctypes.POINTER(vcclLaunchConfig)],
+        "vcclReduceCopyWide": [c_int, c_int, u64, c_int, c_int, ctypes.POINTER(vp), c_int, ctypes.POINTER(vp),
+                               c_size, vp],
+        "vcclCommSetSumFp32": [vp, c_int, ctypes.POINTER(c_int)],
         "vcclHostToDevRedOp": [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(u64)],
         "vcclKernelTypeOf": [c_int, c_int],
         "vcclBootstrapAllGather": [ctypes.POINTER(ncclUniqueId), c_int, c_int, vp, c_size],
@@ -800,6 +805,16 @@ def reduce_copy(dev_op: int, dtype: int, red_arg: int, srcs, dsts, n_elts: int, 
     check(rc, "vcclReduceCopy")
 
 
+def reduce_copy_wide(dev_op: int, dtype: int, red_arg: int, srcs, dsts, n_elts: int, stream: int = 0,
+                     pre_op_srcs: int = 0) -> None:
+    """vcclReduceCopyWide on raw device pointers: the f16 / bf16 / fp8 sum (or PreMulSum) accumulated in
+    binary32 and narrowed once."""
+    s = (ctypes.c_void_p * len(srcs))(*srcs)
+    d = (ctypes.c_void_p * len(dsts))(*dsts)
+    check(lib().vcclReduceCopyWide(dev_op, dtype, red_arg, pre_op_srcs, len(srcs), s, len(dsts), d, n_elts, stream),
+          "vcclReduceCopyWide")
+
+
 class Comm:
     """Owning wrapper over ncclComm_t."""
 
@@ -1067,6 +1082,13 @@ class Comm:
         check(lib().vcclCommSetRingWave(self.handle, -1 if on is None else int(bool(on)), ctypes.byref(n)),
               "vcclCommSetRingWave")
         return int(n.value)
+
+    def set_sum_fp32(self, on: bool) -> bool:
+        """vcclCommSetSumFp32: fp32-accumulated f16 / bf16 / fp8 sums on the staged direct all-reduce and
+        reduce-scatter for later calls (VCCL_SUM_FP32); returns whether it took effect."""
+        eff = ctypes.c_int(0)
+        check(lib().vcclCommSetSumFp32(self.handle, int(bool(on)), ctypes.byref(eff)), "vcclCommSetSumFp32")
+        return bool(eff.value)
 
     def debug_set_epochs(self, ll_epoch: int, direct_epoch: int):
         """vcclCommDebugSetEpochs: overwrite the LL / direct call epochs (wrap tests)."""
