@@ -335,11 +335,19 @@ ncclResult_t vcclCommSetDirectA2aThreshold(ncclComm_t comm, int64_t bytes, int64
 /* fp32-accumulated sums (opt-in: VCCL_SUM_FP32=1 at init, default 0 = off;
  * DESIGN.md section 4.17): ncclAllReduce / ncclReduceScatter with ncclSum,
  * ncclAvg or a PreMulSum op over f16, bf16, e4m3 or e5m2 take the staged direct
- * path at every size and fold in binary32, narrowing once.
+ * path at every size and fold in binary32, narrowing once.  VCCL_SUM_FP32=2
+ * (level 2) also folds so in the one-hop LL all-reduce / reduce-scatter (a call
+ * on its own that the LL threshold admits), in the zero-copy kernels over
+ * ncclCommRegister'ed buffers (VCCL_REG_THRESHOLD / VCCL_REG_ROOTED_THRESHOLD;
+ * their fallback is the staged wide kernel) and in ncclReduce, which then runs
+ * the staged two-hop direct reduce at every size.  Level 1 is unchanged; the
+ * cost of the level-2 folds over xGMI is unmeasured and both stay opt-in.
  *   vcclCommSetSumFp32  the same for later calls; every rank calls it alike,
- *                    outside a group.  *effective = 0 (and nothing changes)
- *                    without mapped inboxes, outside 2..8 ranks, with a peer
- *                    behind the net proxy or Direct excluded by NCCL_ALGO. */
+ *                    outside a group.  on: the level, 0 off, 2 level 2, any
+ *                    other value level 1.  *effective = the level in force: 0
+ *                    (and nothing changes) without mapped inboxes, outside
+ *                    2..8 ranks, with a peer behind the net proxy or Direct
+ *                    excluded by NCCL_ALGO. */
 ncclResult_t vcclCommSetSumFp32(ncclComm_t comm, int on, int* effective);
 /* Zero-copy direct all-reduce / reduce-scatter / all-gather over
  * ncclCommRegister'ed buffers (opt-in: VCCL_REG_THRESHOLD=<bytes> at init,

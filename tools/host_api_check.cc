@@ -10,6 +10,7 @@
 // seed; prints a summary and exits non-zero on an unexpected result (the
 // sanitizers abort on any memory or UB error).
 #include <algorithm>
+#include <climits>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -513,6 +514,12 @@ int main() {
   {
     int eff = 7;
     EXPECT(vcclCommSetSumFp32(nullptr, 1, &eff) == ncclInvalidArgument && eff == 7);
+    // ... at every level, level 2 and values that are no level included: refused before `effective` is written,
+    // with or without a place for it
+    for (int level : {0, 2, 3, -1, INT_MAX, INT_MIN}) {
+      EXPECT(vcclCommSetSumFp32(nullptr, level, &eff) == ncclInvalidArgument && eff == 7);
+      EXPECT(vcclCommSetSumFp32(nullptr, level, nullptr) == ncclInvalidArgument);
+    }
     char buf[64] = {};
     const void* src[1] = {buf};
     void* dst[1] = {buf};

@@ -856,6 +856,8 @@ __device__ void direct_reduce_part(const DirectWork& w, uint32_t& e, int& shFail
   using T = typename Fn::EltType;
   constexpr int64_t esz = (int64_t)sizeof(T);
   const Fn fn(load_op_arg(w.redArgPtr, w.redArgBytes, w.redArg));
+  const auto cfn = direct_copy_fn(fn);  // scatter / collect copies
+  using CFn = decltype(direct_copy_fn(fn));
   const DirectPeers& P = *w.peers;
   const int n = w.nRanks, me = w.rank, root = w.root, b = blockIdx.x;
   const int tid = threadIdx.x, nt = blockDim.x;
@@ -887,7 +889,7 @@ __device__ void direct_reduce_part(const DirectWork& w, uint32_t& e, int& shFail
       block_of(p, &off, &len);
       const char* s[kDirectMaxRanks] = {in + off * esz};
       char* d[kDirectMaxRanks] = {P.buf[p] + direct_region_off(0, 0, me, n, w.regionBytes) + inOff};
-      direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+      direct_rc<CFn, kDirectCopyUnroll, kSys, kSys, kSys>(cfn, s, 1, 0, false, d, 1, len, tid, nt);
     }
     direct_post(w, P, 0, 0, b, e);
     // Phase 2: fold my block per channel part, in the order of the ring
@@ -919,8 +921,8 @@ __device__ void direct_reduce_part(const DirectWork& w, uint32_t& e, int& shFail
           s[j] = q == me ? in + (off + cur) * esz
                          : myBuf + direct_region_off(0, 0, q, n, w.regionBytes) + inOff + cur * esz;
         }
-        direct_rc<Fn, kDirectUnroll, kSys, kSys, kSys>(fn, s, n, w.preOp ? n : 0, true, d, 1, end - cur,
-                                                       tid, nt);
+        direct_rc<Fn, direct_fold_unroll<Fn>(), kSys, kSys, kSys>(fn, s, n, w.preOp ? n : 0, true, d, 1, end - cur,
+                                                                  tid, nt);
         cur = end;
       }
     }
@@ -933,7 +935,7 @@ __device__ void direct_reduce_part(const DirectWork& w, uint32_t& e, int& shFail
         block_of(o, &off, &len);
         const char* s[kDirectMaxRanks] = {myBuf + direct_region_off(1, 0, o, n, w.regionBytes) + inOff};
         char* d[kDirectMaxRanks] = {(char*)w.recvbuff + (c0 + off) * esz};
-        direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+        direct_rc<CFn, kDirectCopyUnroll, kSys, kSys, kSys>(cfn, s, 1, 0, false, d, 1, len, tid, nt);
       }
     }
   }

@@ -193,8 +193,8 @@ __device__ __forceinline__ void reg_reducescatter_zc(const DirectRegWork& rw, co
       const int q = j < n ? order[j] : me;
       s[j] = (q == me ? (const char*)w.sendbuff : rs.send[q]) + ((int64_t)me * count + cur) * esz;
     }
-    direct_rc<Fn, kDirectUnroll, kSys, kSys, kSys>(fn, s, n, w.preOp ? n : 0, true, d, 1, end - cur, threadIdx.x,
-                                                   blockDim.x);
+    direct_rc<Fn, direct_fold_unroll<Fn>(), kSys, kSys, kSys>(fn, s, n, w.preOp ? n : 0, true, d, 1, end - cur,
+                                                              threadIdx.x, blockDim.x);
     cur = end;
   }
   reg_close(w, *w.peers, b, e, shFail);
@@ -228,6 +228,8 @@ __device__ __forceinline__ void reg_allreduce_zc(const DirectRegWork& rw, const 
   const DirectWork& w = rw.w;
   const DirectPeers& P = *w.peers;
   const Fn fn(load_op_arg(w.redArgPtr, w.redArgBytes, w.redArg));
+  const auto cfn = direct_copy_fn(fn);
+  using CFn = decltype(direct_copy_fn(fn));
   const int n = w.nRanks, me = w.rank, b = blockIdx.x;
   const int tid = threadIdx.x, nt = blockDim.x;
   const int64_t eltAlign = 16 / sizeof(T) ? 16 / sizeof(T) : 1;
@@ -268,7 +270,8 @@ __device__ __forceinline__ void reg_allreduce_zc(const DirectRegWork& rw, const 
         const int q = j < n ? __builtin_amdgcn_readfirstlane(R[pos]) : me;
         s[j] = (q == me ? (const char*)w.sendbuff : rs.send[q]) + (off + cur) * esz;
       }
-      direct_rc<Fn, kDirectUnroll, kSys, kSys, kSys>(fn, s, n, w.preOp ? n : 0, true, d, 1, end - cur, lane, 64);
+      direct_rc<Fn, direct_fold_unroll<Fn>(), kSys, kSys, kSys>(fn, s, n, w.preOp ? n : 0, true, d, 1, end - cur, lane,
+                                                                64);
       cur = end;
     }
   }
@@ -280,7 +283,8 @@ __device__ __forceinline__ void reg_allreduce_zc(const DirectRegWork& rw, const 
       block_of(o, &off, &len);
       const char* s[kDirectMaxRanks] = {rs.recv[o] + off * esz};
       char* d[kDirectMaxRanks] = {out + off * esz};
-      direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+      // the pull of a finished shard: the type's native copy functor (direct.hpp direct_copy_fn)
+      direct_rc<CFn, kDirectCopyUnroll, kSys, kSys, kSys>(cfn, s, 1, 0, false, d, 1, len, tid, nt);
     }
   }
   direct_post(w, P, 1, 0, b, e);
@@ -387,6 +391,8 @@ __device__ __forceinline__ void reg_reduce_zc(const DirectRegWork& rw, const Reg
   constexpr int64_t esz = (int64_t)sizeof(T);
   const DirectWork& w = rw.w;
   const Fn fn(load_op_arg(w.redArgPtr, w.redArgBytes, w.redArg));
+  const auto cfn = direct_copy_fn(fn);  // the root's collect copies
+  using CFn = decltype(direct_copy_fn(fn));
   const DirectPeers& P = *w.peers;
   const int n = w.nRanks, me = w.rank, root = w.root, b = blockIdx.x;
   const int tid = threadIdx.x, nt = blockDim.x;
@@ -436,7 +442,8 @@ __device__ __forceinline__ void reg_reduce_zc(const DirectRegWork& rw, const Reg
           const int q = j < n ? __builtin_amdgcn_readfirstlane(R[pos]) : me;
           s[j] = (q == me ? (const char*)w.sendbuff : rs.send[q]) + (c0 + off + cur) * esz;
         }
-        direct_rc<Fn, kDirectUnroll, kSys, kSys, kSys>(fn, s, n, w.preOp ? n : 0, true, d, 1, end - cur, tid, nt);
+        direct_rc<Fn, direct_fold_unroll<Fn>(), kSys, kSys, kSys>(fn, s, n, w.preOp ? n : 0, true, d, 1, end - cur,
+                                                                  tid, nt);
         cur = end;
       }
     }
@@ -448,7 +455,7 @@ __device__ __forceinline__ void reg_reduce_zc(const DirectRegWork& rw, const Reg
         block_of(o, &off, &len);
         const char* s[kDirectMaxRanks] = {myBuf + direct_region_off(1, 0, o, n, w.regionBytes) + inOff};
         char* d[kDirectMaxRanks] = {(char*)w.recvbuff + (c0 + off) * esz};
-        direct_rc<Fn, kDirectCopyUnroll, kSys, kSys, kSys>(fn, s, 1, 0, false, d, 1, len, tid, nt);
+        direct_rc<CFn, kDirectCopyUnroll, kSys, kSys, kSys>(cfn, s, 1, 0, false, d, 1, len, tid, nt);
       }
     }
   }

@@ -34,6 +34,12 @@ hipError_t direct_reg_launch_ar<VCCL_KT>(int devOp, const DirectRegWork& rw, hip
   using T = typename KTypeOf<VCCL_KT>::T;
   const dim3 grid(rw.w.nBlocks), block(kDirectThreads);
   hipError_t err = hipErrorInvalidValue;
+  if (is_wide_op(devOp)) {  // the wide sums (ops.hpp), over the four wide kernel types
+    if constexpr (wide_kernel_type(VCCL_KT))
+      dispatch_wide_op<T>(devOp,
+                          [&]<class Fn>() { err = launch_k(k_direct_reg_allreduce<Fn>, grid, block, stream, stop, rw); });
+    return err;
+  }
   dispatch_op<T>(devOp, [&]<class Fn>() {
     if constexpr (!std::is_same<Fn, FnCopy<T>>::value)
       err = launch_k(k_direct_reg_allreduce<Fn>, grid, block, stream, stop, rw);
@@ -66,6 +72,12 @@ hipError_t direct_reg_launch_rooted<VCCL_KT>(int coll, int devOp, const DirectRe
   }
   hipError_t err = hipErrorInvalidValue;
   if (coll != kCollReduce) return err;
+  if (is_wide_op(devOp)) {  // the wide sums (ops.hpp), over the four wide kernel types
+    if constexpr (wide_kernel_type(VCCL_KT))
+      dispatch_wide_op<T>(devOp,
+                          [&]<class Fn>() { err = launch_k(k_direct_reg_reduce<Fn>, grid, block, stream, stop, rw); });
+    return err;
+  }
   dispatch_op<T>(devOp, [&]<class Fn>() {
     if constexpr (!std::is_same<Fn, FnCopy<T>>::value)
       err = launch_k(k_direct_reg_reduce<Fn>, grid, block, stream, stop, rw);
@@ -99,6 +111,12 @@ hipError_t direct_reg_launch_rsag<VCCL_KT>(int coll, int devOp, const DirectRegW
   }
   hipError_t err = hipErrorInvalidValue;
   if (coll != kCollReduceScatter) return err;
+  if (is_wide_op(devOp)) {  // the wide sums (ops.hpp), over the four wide kernel types
+    if constexpr (wide_kernel_type(VCCL_KT))
+      dispatch_wide_op<T>(
+          devOp, [&]<class Fn>() { err = launch_k(k_direct_reg_reducescatter<Fn>, grid, block, stream, stop, rw); });
+    return err;
+  }
   dispatch_op<T>(devOp, [&]<class Fn>() {
     if constexpr (!std::is_same<Fn, FnCopy<T>>::value)
       err = launch_k(k_direct_reg_reducescatter<Fn>, grid, block, stream, stop, rw);

@@ -80,6 +80,47 @@ __device__ __forceinline__ uint64_t ll_apply(const Fn& fn, uint64_t acc, uint64_
   return a.u;
 }
 
+// What the folds below hold of a line between sources, selected by the
+// functor as AccOf<Fn> selects the pack accumulator (ops.hpp): the 8 data bytes
+// themselves for a native functor, folded with ll_apply — the fold sites keep
+// that code word for word under `if constexpr`, which is what leaves the native
+// kernels instruction-identical (routed through a helper they came out with
+// other register numbers) — or, for a wide one, the line's
+// 4 (f16, bf16) or 8 (fp8) elements in binary32, kept as 2 or 4 register
+// pairs: every arrived line is widened once (Wide<T>::up_word per 32-bit
+// half), scaled by the PreMulSum scalar where it takes the preOp (a rounded
+// binary32 product) and added with v_pk_add_f32 in the order the native fold
+// visits the sources (ll_fold); ll_done narrows once with the native rule.
+// The zero padding of a partial last line widens to +0 and ll_store8 never
+// stores it.
+template <class Fn, bool W = is_wide_fn<Fn>()> struct LLAccOf {
+  using Line = uint64_t;
+};
+template <class Fn> struct LLAccOf<Fn, true> {
+  struct Line {
+    f32x2 p[2 * Wide<typename Fn::EltType>::kPairs];
+  };
+};
+// The wide fold step: acc = first ? pre(x) : acc + pre(x); `pre`: this call applies the preOp.
+template <class Fn>
+__device__ __forceinline__ void ll_fold(const Fn& fn, typename LLAccOf<Fn, true>::Line& acc, uint64_t x, bool first,
+                                        bool pre) {
+  using W = Wide<typename Fn::EltType>;
+  f32x2 t[2 * W::kPairs];
+  W::up_word((uint32_t)x, &t[0]);
+  W::up_word((uint32_t)(x >> 32), &t[W::kPairs]);
+#pragma unroll
+  for (int i = 0; i < 2 * W::kPairs; i++) {
+    if (Fn::kPreOp && pre) t[i] *= fn.scalar;  // rounded to binary32 before the add (-ffp-contract=off)
+    acc.p[i] = first ? t[i] : acc.p[i] + t[i];
+  }
+}
+template <class Fn>
+__device__ __forceinline__ uint64_t ll_done(const Fn&, const typename LLAccOf<Fn, true>::Line& acc) {
+  using W = Wide<typename Fn::EltType>;
+  return (uint64_t)W::down_word(&acc.p[0]) | ((uint64_t)W::down_word(&acc.p[W::kPairs]) << 32);
+}
+
 // Poll one LL line until both halves carry `epoch`; returns the 8 data bytes.
 __device__ __forceinline__ bool ll_read_line(const char* line, uint32_t epoch, const DevComm* comm,
                                              uint64_t* out) {
@@ -194,7 +235,7 @@ __device__ void ll_allreduce(const LLWork& w) {
     pc = ll_advance(sh, nParts, pc, l);
     const LLPart& part = sh.p[pc];
     const int64_t pl = l - part.line0;
-    uint64_t acc = 0;
+    typename LLAccOf<Fn>::Line acc{};  // the line itself, or its elements in binary32
     for (int hi = w.nRanks - 1; hi >= 0 && ok; hi -= kLLBatch) {
       const int lo = hi - kLLBatch + 1 > 0 ? hi - kLLBatch + 1 : 0;
       u32x4 v[kLLBatch];
@@ -222,13 +263,21 @@ __device__ void ll_allreduce(const LLWork& w) {
                             w.comm, &x);
           if (!ok) break;
         }
-        if (Fn::kPreOp && w.preOp) x = ll_apply(fn, 0, x, 1);
-        acc = (pos == w.nRanks - 1) ? x : ll_apply(fn, acc, x, 0);  // LL order: child (+) own
+        if constexpr (is_wide_fn<Fn>()) {
+          ll_fold(fn, acc, x, pos == w.nRanks - 1, w.preOp);
+        } else {
+          if (Fn::kPreOp && w.preOp) x = ll_apply(fn, 0, x, 1);
+          acc = (pos == w.nRanks - 1) ? x : ll_apply(fn, acc, x, 0);  // LL order: child (+) own
+        }
       }
     }
     if (!ok) break;
-    if (Fn::kPostOp) acc = ll_apply(fn, acc, 0, 2);
-    ll_store8(part.recv, pl, part.nbytes, acc);
+    if constexpr (is_wide_fn<Fn>()) {
+      ll_store8(part.recv, pl, part.nbytes, ll_done(fn, acc));
+    } else {
+      if (Fn::kPostOp) acc = ll_apply(fn, acc, 0, 2);
+      ll_store8(part.recv, pl, part.nbytes, acc);
+    }
   }
   ll_epoch_retire(w.comm, e);
 }
@@ -288,7 +337,7 @@ __device__ void ll_reducescatter(const LLWork& w) {
         v[j] = __builtin_amdgcn_raw_buffer_load_b128(a.r, a.voff, 0, kSysAux);
       }
     }
-    uint64_t acc = 0;
+    typename LLAccOf<Fn>::Line acc{};
 #pragma unroll
     for (int j = 0; j < kOrderMaxRanks; j++) {
       if (j >= n) break;
@@ -303,12 +352,20 @@ __device__ void ll_reducescatter(const LLWork& w) {
                           &x);
         if (!ok) break;
       }
-      if (Fn::kPreOp && w.preOp) x = ll_apply(fn, 0, x, 1);
-      acc = j == 0 ? x : ll_apply(fn, acc, x, 0);
+      if constexpr (is_wide_fn<Fn>()) {
+        ll_fold(fn, acc, x, j == 0, w.preOp);
+      } else {
+        if (Fn::kPreOp && w.preOp) x = ll_apply(fn, 0, x, 1);
+        acc = j == 0 ? x : ll_apply(fn, acc, x, 0);
+      }
     }
     if (!ok) break;
-    if (Fn::kPostOp) acc = ll_apply(fn, acc, 0, 2);
-    ll_store8(part.recv, pl, nb, acc);
+    if constexpr (is_wide_fn<Fn>()) {
+      ll_store8(part.recv, pl, nb, ll_done(fn, acc));
+    } else {
+      if (Fn::kPostOp) acc = ll_apply(fn, acc, 0, 2);
+      ll_store8(part.recv, pl, nb, acc);
+    }
   }
   ll_epoch_retire(w.comm, e);
 }

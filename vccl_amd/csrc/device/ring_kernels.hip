@@ -185,6 +185,17 @@ hipError_t ll_launch<VCCL_KT>(int coll, int devOp, const LLWork& w, int grid, hi
     return hipErrorInvalidValue;
   }
   hipError_t err = hipErrorInvalidValue;
+  // the wide sums (ll.hpp LLAccOf): the all-reduce and the reduce-scatter over the four wide kernel types
+  if (is_wide_op(devOp)) {
+    if constexpr (wide_kernel_type(VCCL_KT)) {
+      dispatch_wide_op<T>(devOp, [&]<class Fn>() {
+        if (coll == kCollAllReduce) err = launch_k(k_ll_allreduce<Fn>, dim3(grid), dim3(256), stream, stop, w);
+        else if (coll == kCollReduceScatter)
+          err = launch_k(k_ll_reducescatter<Fn>, dim3(grid), dim3(256), stream, stop, w);
+      });
+    }
+    return err;
+  }
   dispatch_op<T>(devOp, [&]<class Fn>() {
     if constexpr (!std::is_same<Fn, FnCopy<T>>::value) {
       err = coll == kCollAllReduce ? launch_k(k_ll_allreduce<Fn>, dim3(grid), dim3(256), stream, stop, w)
@@ -238,12 +249,13 @@ hipError_t direct_launch<VCCL_KT>(int coll, int devOp, const DirectBatch& b, hip
     return hipErrorInvalidValue;
   }
   hipError_t err = hipErrorInvalidValue;
-  // the wide sums (ops.hpp): the all-reduce and the reduce-scatter over the four wide kernel types
+  // the wide sums (ops.hpp): the all-reduce, the reduce-scatter and the reduce over the four wide kernel types
   if (is_wide_op(devOp)) {
     if constexpr (wide_kernel_type(VCCL_KT)) {
       dispatch_wide_op<T>(devOp, [&]<class Fn>() {
         if (coll == kCollAllReduce) err = launch_k(k_direct_allreduce<Fn>, grid, block, stream, stop, b);
         else if (coll == kCollReduceScatter) err = launch_k(k_direct_reducescatter<Fn>, grid, block, stream, stop, b);
+        else if (coll == kCollReduce) err = launch_k(k_direct_reduce<Fn>, grid, block, stream, stop, b);
       });
     }
     return err;

@@ -101,7 +101,7 @@ static ncclResult_t enqueue_check_impl(int coll, const char* name, const void* s
          .devOp = OP_COPY, .root = root, .comm = comm, .stream = stream};
   if (!is_copy_coll(coll)) {
     NCCLCHECK(resolve_op(comm, op, dt, &t.devOp, &t.arg, &t.argPtr));
-    t.devOp = sum_fp32_op(sum_fp32_on(comm), coll, t.devOp, dt);  // VCCL_SUM_FP32: the wide op code, or unchanged
+    t.devOp = sum_fp32_op(sum_fp32_level(comm), coll, t.devOp, dt);  // VCCL_SUM_FP32: the wide op code, or unchanged
   }
   if (*(volatile int*)comm->errorFlag) {
     const ncclResult_t e = error_word_result(comm);

@@ -87,8 +87,12 @@ VCCL_EXPORT ncclResult_t vcclCommCollAlgo(ncclComm_t comm, int coll, size_t coun
   }
   // the public collective codes are the Coll values (vccl_ext.h)
   // VCCL_SUM_FP32: the path of the sum (or avg) the opt-in serves; any other op over these types is chosen as ever
-  const bool wide = is_wide_op(sum_fp32_op(sum_fp32_on(comm), coll, OP_SUM, datatype));
-  *algo = public_algo(wide ? (int)kAlgoDirect : select_algo(policy_of(comm), coll, type_size(datatype), (int64_t)count));
+  // (level 2: LL where select_algo sends the all-reduce / reduce-scatter there, and the reduce is served too)
+  const int level = sum_fp32_level(comm);
+  const bool wide = is_wide_op(sum_fp32_op(level, coll, OP_SUM, datatype));
+  const AlgoPolicy pol = policy_of(comm);
+  *algo = public_algo(wide ? sum_fp32_algo(level, pol, coll, type_size(datatype), (int64_t)count)
+                           : select_algo(pol, coll, type_size(datatype), (int64_t)count));
   return ncclSuccess;
 }
 
@@ -125,7 +129,7 @@ VCCL_EXPORT ncclResult_t vcclRingChunkOf(size_t count, ncclDataType_t datatype, 
 static ncclResult_t group_plan_export(int nCalls, const int* colls, const size_t* counts, const int* datatypes,
                                       const int* ops, int nRanks, int nChannels, const PlanGeometry& geo,
                                       const AlgoPolicy* pol, int* algos, int* order, int* planOf, int64_t* cbd,
-                                      bool sumFp32 = false) {
+                                      int sumFp32 = 0) {
   if (nCalls < 1 || !colls || !counts || !datatypes || !ops || !order || !planOf || !cbd || nRanks < 1 ||
       nChannels < 1 || nChannels > kMaxChannels || geo.stepBytes < 4096 || geo.nThreads < 64 ||
       geo.ll128StepBytes < 1920 * 16 || geo.ll128Threads < 64)
@@ -143,6 +147,7 @@ static ncclResult_t group_plan_export(int nCalls, const int* colls, const size_t
     g.push_back(group_task_of(c, counts[i], dt, sum_fp32_op(sumFp32, c, devOp, dt), kt));
   }
   GroupPlanOut p;
+  if (pol) sum_fp32_group_rule(g, sumFp32, *pol);
   group_plan(g, nRanks, nChannels, geo, pol, &p);
   for (int i = 0; i < nCalls; i++) {
     order[i] = p.order[i];
@@ -191,7 +196,7 @@ VCCL_EXPORT ncclResult_t vcclCommGroupAlgos(ncclComm_t comm, int nCalls, const i
   const PlanGeometry geo{comm->stepBytes, comm->nThreads, ll128 ? comm->ll128StepBytes : kDefaultLL128.stepBytes,
                          ll128 ? comm->ll128Threads : kDefaultLL128.nThreads};
   return group_plan_export(nCalls, colls, counts, datatypes, ops, comm->nRanks, comm->nChannels, geo, &pol, algos,
-                           order.data(), planOf.data(), cbd.data(), sum_fp32_on(comm));
+                           order.data(), planOf.data(), cbd.data(), sum_fp32_level(comm));
 }
 
 // A comm's VCCL_P2P_LL_THRESHOLD as it takes effect.
@@ -494,11 +499,12 @@ VCCL_EXPORT ncclResult_t vcclCommSetDirectA2aThreshold(ncclComm_t comm, int64_t 
 }
 
 // fp32-accumulated f16 / bf16 / fp8 sums for later calls (as VCCL_SUM_FP32 at
-// init): every rank must call it alike, outside a group.
+// init): every rank must call it alike, outside a group.  `on`: the level, 0
+// off, 2 level 2, any other value level 1.
 VCCL_EXPORT ncclResult_t vcclCommSetSumFp32(ncclComm_t comm, int on, int* effective) {
   NCCLCHECK(comm_check(comm, "vcclCommSetSumFp32"));
   // a comm with a net peer maps no inbox: dPeers says both
-  comm->sumFp32 = sum_fp32_of(*comm, on != 0, comm->nRanks, comm->dPeers == nullptr, comm->dPeers != nullptr);
+  comm->sumFp32 = sum_fp32_of(*comm, on, comm->nRanks, comm->dPeers == nullptr, comm->dPeers != nullptr);
   if (effective) *effective = comm->sumFp32;
   return ncclSuccess;
 }

@@ -371,8 +371,9 @@ static ncclResult_t launch_ll(const Task* ts, int nTasks, hipEvent_t stop) {
     }
   }
   const bool copy = is_copy_coll(t.coll);
-  const int kt = copy ? K_U8 : kernel_type_of(t.devOp, (int)t.datatype);
+  const int kt = copy ? K_U8 : kernel_type_of(native_op_of(t.devOp), (int)t.datatype);  // a wide op: its type's unit
   if (kt < 0) return ncclInvalidArgument;
+  if (is_wide_op(t.devOp) && rooted) return ncclInternalError;  // the wide reduce never takes the rooted LL
   const int grid = ll_grid(comm, lines);
   const int devOp = copy ? OP_COPY : t.devOp;
   const hipError_t e = by_kernel_type(kt, [&]<int K>() { return ll_launch<K>(t.coll, devOp, w, grid, t.stream, stop); });
@@ -596,7 +597,9 @@ static ncclResult_t launch_direct_reg_rooted(const Task& t, hipEvent_t stop) {
 
 // A call's path: select_algo on the comm's thresholds.
 static int choose_algo(const Task& t) {
-  if (is_wide_op(t.devOp)) return kAlgoDirect;  // the wide sums exist on the staged direct path only
+  // the wide sums: the staged direct path, at level 2 the one-hop LL kernel where select_algo answers LL
+  if (is_wide_op(t.devOp))
+    return sum_fp32_algo(sum_fp32_level(t.comm), policy_of(t.comm), t.coll, type_size(t.datatype), (int64_t)t.count);
   return select_algo(policy_of(t.comm), t.coll, type_size(t.datatype), (int64_t)t.count);
 }
 
@@ -605,7 +608,8 @@ constexpr int kAlgoDirectReg = 100;  // launch.cc only: one eligible call, the z
 constexpr int kAlgoDirectRegRooted = 101;  // ... a broadcast / reduce
 // The zero-copy path of a call that is eligible for one, else `algo`.
 static int reg_algo_or(const Task& t, int algo) {
-  if (is_wide_op(t.devOp)) return algo;  // the zero-copy fold is the native one: such calls do not negotiate
+  // level 1 of the wide sums keeps to the staged path: such calls do not negotiate
+  if (is_wide_op(t.devOp) && sum_fp32_level(t.comm) < 2) return algo;
   return reg_task_eligible(t) ? kAlgoDirectReg : reg_rooted_task_eligible(t) ? kAlgoDirectRegRooted : algo;
 }
 static ncclResult_t launch_path(int algo, const Task* ts, int n, hipEvent_t stop) {
@@ -732,6 +736,7 @@ static ncclResult_t launch_planned(std::vector<Task>& tasks, const std::vector<i
   }
   GroupPlanOut plan;
   const AlgoPolicy pol = policy_of(comm);
+  sum_fp32_group_rule(g, sum_fp32_level(comm), pol);
   group_plan(g, comm->nRanks, comm->nChannels,
              PlanGeometry{comm->stepBytes, comm->nThreads, comm->ll128StepBytes, comm->ll128Threads}, &pol, &plan);
   for (size_t k = 0; k < idx.size(); k++) {

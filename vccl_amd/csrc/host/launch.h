@@ -59,6 +59,9 @@ struct Task {
 // VCCL_SUM_FP32 / vcclCommSetSumFp32 as the comm's calls take it: the setup's
 // verdict, and every peer's inbox mapped.
 inline bool sum_fp32_on(const ncclComm* c) { return c->sumFp32 != 0 && c->dPeers != nullptr; }
+// ... and the level in force: 0 off, 1 the staged direct path alone, 2 also the
+// LL, zero-copy and rooted folds (plan.h sum_fp32_op / sum_fp32_algo).
+inline int sum_fp32_level(const ncclComm* c) { return sum_fp32_on(c) ? c->sumFp32 : 0; }
 // The one place that reads a comm into the planner's thresholds.
 AlgoPolicy policy_of(const ncclComm* c);
 // The kernel element type of a call (K_U8 for the byte copies), -1: no kernel.

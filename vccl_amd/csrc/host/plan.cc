@@ -299,11 +299,16 @@ int select_algo(const AlgoPolicy& p, int coll, int64_t eltSize, int64_t count) {
 bool sum_fp32_effective(bool on, bool inbox, bool directAllowed, bool anyNet, int nRanks) {
   return on && inbox && directAllowed && !anyNet && nRanks >= 2 && nRanks <= kDirectMaxRanks;
 }
-int sum_fp32_op(bool effective, int coll, int devOp, ncclDataType_t datatype) {
-  if (!effective || (coll != kAllReduce && coll != kReduceScatter)) return devOp;
+int sum_fp32_op(int level, int coll, int devOp, ncclDataType_t datatype) {
+  if (level <= 0 || (coll != kAllReduce && coll != kReduceScatter && !(coll == kReduce && level >= 2))) return devOp;
   if (datatype != ncclFloat16 && datatype != ncclBfloat16 && datatype != ncclFloat8e4m3 && datatype != ncclFloat8e5m2)
     return devOp;
   return devOp == OP_SUM ? kSumWideOp : devOp == OP_PREMULSUM ? kPreMulSumWideOp : devOp;
+}
+int sum_fp32_algo(int level, const AlgoPolicy& p, int coll, int64_t eltSize, int64_t count) {
+  if (level >= 2 && (coll == kAllReduce || coll == kReduceScatter) && select_algo(p, coll, eltSize, count) == kAlgoLL)
+    return kAlgoLL;
+  return kAlgoDirect;
 }
 uint64_t ll_rooted_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks) {
   if (threshold <= 0 || llSlotBytes <= 0 || !llAllowed || anyNet || nRanks > kOrderMaxRanks) return 0;
@@ -349,6 +354,10 @@ GroupTask group_task_of(int coll, size_t count, ncclDataType_t datatype, int dev
   const int key = (coll * 16 + (ag ? (int)OP_SUM : devOp)) * 32;
   return GroupTask{coll, sz.count, sz.eltSize, key + (ag ? (int)ncclInt8 : (int)datatype), key + kernelType,
                    !ag && is_wide_sum_op(devOp)};
+}
+void sum_fp32_group_rule(std::vector<GroupTask>& g, int level, const AlgoPolicy& pol) {
+  if (g.size() == 1 && g[0].wide && sum_fp32_algo(level, pol, g[0].coll, g[0].eltSize, g[0].count) == kAlgoLL)
+    g[0].wide = false;
 }
 uint32_t u32fp_encode(uint32_t x, int bitsPerPow2) {  // bitops.h:252-262
   const int log2x = 31 - __builtin_clz(x | 1);

@@ -105,12 +105,20 @@ bool sum_fp32_effective(bool on, bool inbox, bool directAllowed, bool anyNet, in
 // The device op a call runs with: the wide op code (device/dispatch.hpp) for
 // an all-reduce or reduce-scatter with Sum / PreMulSum (ncclAvg's encoding
 // included) over f16, bf16, e4m3 or e5m2 on a comm where the opt-in is
-// effective; devOp unchanged for every other call.  A call with a wide op
-// takes the staged direct path at every size (group_plan, launch.cc
-// choose_algo) and never the zero-copy one.
+// effective (`level` 1 or 2; 0: off), at level 2 for such a reduce too; devOp
+// unchanged for every other call.  At level 1 a call with a wide op takes the
+// staged direct path at every size (group_plan, launch.cc choose_algo) and
+// never the zero-copy one.  At level 2 a call on its own also takes the other
+// paths where one rank holds all n inputs of an element (sum_fp32_algo below,
+// launch.cc reg_algo_or): the one-hop LL kernels and the zero-copy kernels;
+// inside a group of several collectives it keeps level 1's rule.
 constexpr int kSumWideOp = 5, kPreMulSumWideOp = 6;  // dispatch.hpp OP_SUM_WIDE / OP_PREMULSUM_WIDE (tied in launch.cc)
 inline bool is_wide_sum_op(int devOp) { return devOp == kSumWideOp || devOp == kPreMulSumWideOp; }
-int sum_fp32_op(bool effective, int coll, int devOp, ncclDataType_t datatype);
+int sum_fp32_op(int level, int coll, int devOp, ncclDataType_t datatype);
+// The path of a call with a wide op on its own: LL where level 2 is in force
+// and select_algo answers LL for an all-reduce or reduce-scatter (never the
+// rooted LL), the staged direct path otherwise — in place of both rings.
+int sum_fp32_algo(int level, const AlgoPolicy& p, int coll, int64_t eltSize, int64_t count);
 int proto_of_algo(int algo);
 
 struct GroupTask {
@@ -124,6 +132,10 @@ struct GroupTask {
 // kernel_type_of (K_U8 for a byte copy), passed in so no kernel header is
 // needed here.
 GroupTask group_task_of(int coll, size_t count, ncclDataType_t datatype, int devOp, int kernelType);
+// A group holding ONE collective is a call on its own: where sum_fp32_algo
+// sends its wide call to LL, the `wide` flag is dropped and select_algo, asked
+// for that one call, answers LL.  Groups of several collectives keep the flag.
+void sum_fp32_group_rule(std::vector<GroupTask>& g, int level, const AlgoPolicy& pol);
 
 struct PlanGeometry {
   int64_t stepBytes, nThreads;            // SIMPLE: FIFO step, NCCL_NTHREADS

@@ -394,13 +394,15 @@ ncclResult_t setup_local(int n, int minCTAs, int maxCTAs, CommSetup* s, SetupSiz
   s->p2pLLMaxBytes = p2p_ll_max_of(*s, param_int("P2P_LL_THRESHOLD", 0), n, false, n > 1 && s->p2pOff == kP2pOn);
   if (s->p2pLLMaxBytes > 0) z->p2pLLBytes = p2p_ll_fifo_bytes(n, s->p2pLLStepBytes) + (size_t)n * kFlagStride;
   // fp32-accumulated sums for f16 / bf16 / fp8 (the staged direct all-reduce
-  // and reduce-scatter at every size): opt-in, it changes the result's bits
-  s->sumFp32 = sum_fp32_of(*s, param_int("SUM_FP32", 0) != 0, n, false, s->dRegionBytes > 0);
+  // and reduce-scatter at every size; 2: the LL, zero-copy and reduce folds
+  // too): opt-in, it changes the result's bits
+  s->sumFp32 = sum_fp32_of(*s, (int)param_int("SUM_FP32", 0), n, false, s->dRegionBytes > 0);
   return ncclSuccess;
 }
 
-int sum_fp32_of(const CommSetup& s, bool on, int nRanks, bool anyNet, bool inbox) {
-  return sum_fp32_effective(on, inbox, (s.algoAllowed & kAllowDirect) != 0, anyNet, nRanks) ? 1 : 0;
+int sum_fp32_of(const CommSetup& s, int level, int nRanks, bool anyNet, bool inbox) {
+  if (!sum_fp32_effective(level != 0, inbox, (s.algoAllowed & kAllowDirect) != 0, anyNet, nRanks)) return 0;
+  return level == 2 ? 2 : 1;  // any other non-zero value is level 1, as before level 2 existed
 }
 
 size_t p2p_ll_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool hasP2p) {

@@ -83,7 +83,8 @@ struct CommSetup {
   // fp32-accumulated f16 / bf16 / fp8 sums on the staged direct all-reduce and
   // reduce-scatter (VCCL_SUM_FP32, plan.h sum_fp32_effective; default 0 = off;
   // not part of what vcclCommSetup reports either).  Calls also need the
-  // peers' inboxes mapped (launch.h sum_fp32_on).
+  // peers' inboxes mapped (launch.h sum_fp32_on).  The level: 1, or 2 — also
+  // the LL and zero-copy folds and ncclReduce (plan.h sum_fp32_op).
   int sumFp32 = 0;
 };
 enum { kP2pOn = 0, kP2pOffEnv = 1, kP2pOffRanks = 2, kP2pOffNet = 3 };
@@ -117,9 +118,9 @@ size_t direct_a2a_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool
 // (setup_local; vcclCommSetP2pLLThreshold).
 size_t p2p_ll_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool hasP2p);
 
-// CommSetup::sumFp32 for a VCCL_SUM_FP32 of `on`, likewise (setup_local;
-// vcclCommSetSumFp32).
-int sum_fp32_of(const CommSetup& s, bool on, int nRanks, bool anyNet, bool inbox);
+// CommSetup::sumFp32 for a VCCL_SUM_FP32 of `level`, likewise (setup_local;
+// vcclCommSetSumFp32): the level in force, 0, 1 or 2.
+int sum_fp32_of(const CommSetup& s, int level, int nRanks, bool anyNet, bool inbox);
 
 // A comm's VCCL_REG_THRESHOLD of `threshold` as it takes effect (plan.h
 // reg_max; inbox: every peer's inbox and direct flags are mapped).

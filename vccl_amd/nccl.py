@@ -1083,12 +1083,13 @@ class Comm:
               "vcclCommSetRingWave")
         return int(n.value)
 
-    def set_sum_fp32(self, on: bool) -> bool:
-        """vcclCommSetSumFp32: fp32-accumulated f16 / bf16 / fp8 sums on the staged direct all-reduce and
-        reduce-scatter for later calls (VCCL_SUM_FP32); returns whether it took effect."""
+    def set_sum_fp32(self, level: int) -> int:
+        """vcclCommSetSumFp32: fp32-accumulated f16 / bf16 / fp8 sums for later calls (VCCL_SUM_FP32).  Level 1
+        (or True): the staged direct all-reduce and reduce-scatter; 2: also their LL and zero-copy kernels and
+        ncclReduce; 0: off.  Returns the level in force (0 where it cannot take effect)."""
         eff = ctypes.c_int(0)
-        check(lib().vcclCommSetSumFp32(self.handle, int(bool(on)), ctypes.byref(eff)), "vcclCommSetSumFp32")
-        return bool(eff.value)
+        check(lib().vcclCommSetSumFp32(self.handle, int(level), ctypes.byref(eff)), "vcclCommSetSumFp32")
+        return eff.value
 
     def debug_set_epochs(self, ll_epoch: int, direct_epoch: int):
         """vcclCommDebugSetEpochs: overwrite the LL / direct call epochs (wrap tests)."""
