@@ -172,7 +172,9 @@ ncclResult_t pncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm);
 /* ---- collectives on the hot path ---- */
 /* nccl.h.in:353-356; collectives.cc:93-106.  VCCL_SUM_FP32=1 (default off): f16 / bf16 / fp8 sums and averages of
  * ncclAllReduce / ncclReduceScatter accumulate in binary32 on the staged direct path (vccl_ext.h vcclCommSetSumFp32);
- * VCCL_SUM_FP32=2: also on the one-hop LL and zero-copy paths, and in ncclReduce. */
+ * VCCL_SUM_FP32=2: also on the one-hop LL and zero-copy paths, and in ncclReduce.  VCCL_SUM_FP32_RING_THRESHOLD=<bytes>
+ * (default 0 = off): such calls of at least that size run on a SIMPLE ring with binary32 partial sums instead
+ * (vccl_ext.h vcclCommSetSumFp32RingThreshold). */
 ncclResult_t  ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count,
     ncclDataType_t datatype, ncclRedOp_t op, ncclComm_t comm, hipStream_t stream);
 ncclResult_t pncclAllReduce(const void* sendbuff, void* recvbuff, size_t count,

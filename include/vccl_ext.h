@@ -349,6 +349,21 @@ ncclResult_t vcclCommSetDirectA2aThreshold(ncclComm_t comm, int64_t bytes, int64
  *                    2..8 ranks, with a peer behind the net proxy or Direct
  *                    excluded by NCCL_ALGO. */
 ncclResult_t vcclCommSetSumFp32(ncclComm_t comm, int on, int* effective);
+/* The wide sums' own SIMPLE ring (opt-in: VCCL_SUM_FP32_RING_THRESHOLD=<bytes>
+ * at init, default 0 = off): a wide ncclAllReduce /
+ * ncclReduceScatter on its own (or its comm's only collective of a group) of
+ * at least that many bytes — count * size, the reduce-scatter's nranks *
+ * recvcount * size — takes a ring whose partial sums travel in binary32,
+ * after the zero-copy negotiation and the LL path of level 2 and instead of
+ * the staged direct wide kernel; vcclCommCollAlgo then says vcclAlgoRing.
+ * Same arithmetic and source order, so the same bits.  Untimed over xGMI.
+ *   vcclCommSetSumFp32RingThreshold  the same for later calls; every rank
+ *                    calls it alike, outside a group.  bytes 0: off; negative:
+ *                    ncclInvalidArgument.  *effective = what is in force now:
+ *                    0 while the wide sums are off (the request is kept and
+ *                    takes effect with vcclCommSetSumFp32) or where NCCL_ALGO /
+ *                    NCCL_PROTO exclude the SIMPLE ring. */
+ncclResult_t vcclCommSetSumFp32RingThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
 /* Zero-copy direct all-reduce / reduce-scatter / all-gather over
  * ncclCommRegister'ed buffers (opt-in: VCCL_REG_THRESHOLD=<bytes> at init,
  * default 0 = off).

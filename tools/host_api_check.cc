@@ -520,6 +520,11 @@ int main() {
       EXPECT(vcclCommSetSumFp32(nullptr, level, &eff) == ncclInvalidArgument && eff == 7);
       EXPECT(vcclCommSetSumFp32(nullptr, level, nullptr) == ncclInvalidArgument);
     }
+    // the wide ring's threshold likewise
+    int64_t eff64 = 7;
+    for (int64_t bytes : {(int64_t)0, (int64_t)1, (int64_t)-1, INT64_MAX})
+      EXPECT(vcclCommSetSumFp32RingThreshold(nullptr, bytes, &eff64) == ncclInvalidArgument && eff64 == 7);
+    EXPECT(vcclCommSetSumFp32RingThreshold(nullptr, 4096, nullptr) == ncclInvalidArgument);
     char buf[64] = {};
     const void* src[1] = {buf};
     void* dst[1] = {buf};

@@ -1,6 +1,6 @@
 // Collective kernels for ONE kernel element type (VCCL_KT) and ONE family
 // (VCCL_PART: 0 ring, 1 LL, 2 direct, 3 LL128 ring, 4 ring with the per-wave
-// hand-off — separate objects, built in parallel):
+// hand-off, 5 the wide sums' ring — separate objects, built in parallel):
 // per reduction functor the ring all-reduce / reduce-scatter / reduce (one workgroup
 // per channel, enqueue.cc:1576-1666), the one-shot LL and the direct
 // (two-shot all-reduce, one-hop reduce-scatter, two-hop reduce) kernels; in
@@ -12,6 +12,8 @@
 #include "ring_launch.hpp"
 #if VCCL_PART == 0 || VCCL_PART == 3 || VCCL_PART == 4
 #include "ring.hpp"
+#elif VCCL_PART == 5
+#include "ring_wide.hpp"
 #elif VCCL_PART == 1
 #include "ll.hpp"
 #else
@@ -22,21 +24,26 @@
 #error "compile with -DVCCL_KT=<kernel element type>"
 #endif
 #ifndef VCCL_PART
-#error "compile with -DVCCL_PART=<0 ring | 1 LL | 2 direct | 3 LL128 ring | 4 per-wave ring>"
+#error "compile with -DVCCL_PART=<0 ring | 1 LL | 2 direct | 3 LL128 ring | 4 per-wave ring | 5 wide ring>"
 #endif
 
 namespace vccl {
 
-#if VCCL_PART == 0 || VCCL_PART == 3 || VCCL_PART == 4
+#if VCCL_PART == 0 || VCCL_PART == 3 || VCCL_PART == 4 || VCCL_PART == 5
 // PART 0: the SIMPLE ring; PART 3: the same schedules over LL128 FIFOs;
 // PART 4: the SIMPLE ring with the per-wave hand-off, for the bandwidth
 // kernels only (sum over f32 / f16 / bf16, the byte-copy all-gather and
-// broadcast; Makefile WAVE_KTS), chosen per comm (VCCL_RING_WAVE).
+// broadcast; Makefile WAVE_KTS), chosen per comm (VCCL_RING_WAVE);
+// PART 5: the SIMPLE ring of the wide sums (ring_wide.hpp: all-reduce and
+// reduce-scatter of FnSumWide / FnPreMulSumWide; Makefile WIDE_KTS), chosen
+// per call (VCCL_SUM_FP32_RING_THRESHOLD).
 constexpr int kPartProto = VCCL_PART == 3 ? kProtoLL128 : VCCL_PART == 4 ? kProtoSimpleWave : kProtoSimple;
 #if VCCL_PART == 3
 #define VCCL_RING_LAUNCH ring_launch_ll128
 #elif VCCL_PART == 4
 #define VCCL_RING_LAUNCH ring_launch_wave
+#elif VCCL_PART == 5
+#define VCCL_RING_LAUNCH ring_launch_wide
 #else
 #define VCCL_RING_LAUNCH ring_launch
 #endif
@@ -56,12 +63,17 @@ constexpr int ring_unroll() { return IsF8<typename Fn::EltType>::value ? 2 : kRi
 // LL128 objects never define the same symbol differently.
 template <int COLL, class Fn, int UNROLL, int PROTO>
 __device__ __forceinline__ void ring_run(RingCtx& r, const Fn& fn, const RingWork& w) {
+#if VCCL_PART == 5
+  if constexpr (COLL == kCollAllReduce) ring_allreduce_wide<Fn, UNROLL>(r, fn, w, blockIdx.x);
+  else ring_reducescatter_wide<Fn, UNROLL>(r, fn, w, blockIdx.x);
+#else
   if constexpr (COLL == kCollAllReduce) ring_allreduce<Fn, UNROLL, PROTO>(r, fn, w, blockIdx.x);
   else if constexpr (COLL == kCollReduceScatter)
     ring_reducescatter<Fn, UNROLL, PROTO>(r, fn, w, blockIdx.x);
   else if constexpr (COLL == kCollReduce) ring_reduce<Fn, UNROLL, PROTO>(r, fn, w, blockIdx.x);
   else if constexpr (COLL == kCollAllGather) ring_allgather<UNROLL, PROTO>(r, w, blockIdx.x);
   else ring_broadcast<UNROLL, PROTO>(r, w, blockIdx.x);
+#endif
 }
 
 // One launch = 1 .. kRingMaxWorks calls (RingBatch, group aggregation): the
@@ -116,6 +128,19 @@ hipError_t VCCL_RING_LAUNCH<VCCL_KT>(int coll, int devOp, const RingBatch& w, in
   using T = typename KTypeOf<VCCL_KT>::T;
   hipError_t err = hipErrorInvalidValue;
   dim3 grid(w.w.nChannels), block(nthreads);
+#if VCCL_PART == 5
+  // the wide sums: the all-reduce and the reduce-scatter, nothing else
+  if constexpr (wide_kernel_type(VCCL_KT)) {
+    dispatch_wide_op<T>(devOp, [&]<class Fn>() {
+      if (coll == kCollAllReduce)
+        err = launch_k(k_ring<kCollAllReduce, Fn, ring_wide_unroll<Fn>(), kPartProto>, grid, block, stream, stop, w);
+      else if (coll == kCollReduceScatter)
+        err = launch_k(k_ring<kCollReduceScatter, Fn, ring_wide_unroll<Fn>(), kPartProto>, grid, block, stream, stop,
+                       w);
+    });
+  }
+  return err;
+#else
   if (coll == kCollAllGather || coll == kCollBroadcast) {  // byte copies: the K_U8 unit only
     if constexpr (VCCL_KT == K_U8) {
       if (coll == kCollBroadcast)
@@ -146,6 +171,7 @@ hipError_t VCCL_RING_LAUNCH<VCCL_KT>(int coll, int devOp, const RingBatch& w, in
     }
   });
   return err;
+#endif
 }
 
 #elif VCCL_PART == 1

@@ -41,10 +41,21 @@ hipError_t ring_launch_ll128(int coll, int devOp, const RingBatch& w, int nthrea
 template <int K>
 hipError_t ring_launch_wave(int coll, int devOp, const RingBatch& w, int nthreads, hipStream_t stream,
                             hipEvent_t stop);
-enum : int { kRingVariantSimple = 0, kRingVariantLL128 = 1, kRingVariantWave = 2 };
+// The SIMPLE ring of the wide sums (ring_wide.hpp: partial sums travel in
+// binary32): the all-reduce and reduce-scatter of a wide op code over the
+// four wide kernel types; the workgroup hand-off whatever the comm's wave
+// setting.
+template <int K>
+hipError_t ring_launch_wide(int coll, int devOp, const RingBatch& w, int nthreads, hipStream_t stream,
+                            hipEvent_t stop);
+enum : int { kRingVariantSimple = 0, kRingVariantLL128 = 1, kRingVariantWave = 2, kRingVariantWide = 3 };
 template <int K>
 inline hipError_t ring_launch_any(int variant, int coll, int devOp, const RingBatch& w, int nthreads,
                                   hipStream_t stream, hipEvent_t stop) {
+  if (variant == kRingVariantWide) {
+    if constexpr (wide_kernel_type(K)) return ring_launch_wide<K>(coll, devOp, w, nthreads, stream, stop);
+    return hipErrorInvalidValue;
+  }
   if (variant == kRingVariantLL128) return ring_launch_ll128<K>(coll, devOp, w, nthreads, stream, stop);
   if constexpr (K == K_U8 || K == K_F32 || K == K_F16 || K == K_BF16)
     if (variant == kRingVariantWave) return ring_launch_wave<K>(coll, devOp, w, nthreads, stream, stop);

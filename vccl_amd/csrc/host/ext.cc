@@ -509,6 +509,18 @@ VCCL_EXPORT ncclResult_t vcclCommSetSumFp32(ncclComm_t comm, int on, int* effect
   return ncclSuccess;
 }
 
+// The wide sums' SIMPLE ring for later wide all-reduces / reduce-scatters of at
+// least `bytes` bytes (as VCCL_SUM_FP32_RING_THRESHOLD at init; 0: off): every
+// rank must call it alike, outside a group.  `effective`: what is in force at
+// the comm's present level; the request is kept across vcclCommSetSumFp32.
+VCCL_EXPORT ncclResult_t vcclCommSetSumFp32RingThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective) {
+  NCCLCHECK(comm_check(comm, "vcclCommSetSumFp32RingThreshold"));
+  if (bytes < 0) return ncclInvalidArgument;
+  comm->sumFp32RingBytes = bytes;
+  if (effective) *effective = (int64_t)sum_fp32_ring_of(*comm, sum_fp32_level(comm));
+  return ncclSuccess;
+}
+
 // -------------------------------------------------------- registered buffers
 // A comm's VCCL_REG_THRESHOLD as it takes effect (the registry bit of the init
 // all-gather aside: this is the arithmetic).

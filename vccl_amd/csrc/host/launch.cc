@@ -185,7 +185,8 @@ AlgoPolicy policy_of(const ncclComm* c) {
                     .ll128 = c->ll128Buf != nullptr, .ll128Min = c->ll128MinBytes, .ll128Max = c->ll128MaxBytes,
                     .direct = c->dPeers != nullptr, .directMax = c->directMaxBytes,
                     .directRsAgMax = c->directRsAgMaxBytes, .llRootedMax = c->llRootedMaxBytes,
-                    .directRootedMax = c->directRootedMaxBytes};
+                    .directRootedMax = c->directRootedMaxBytes,
+                    .sumFp32RingMin = sum_fp32_ring_of(*c, sum_fp32_level(c))};
 }
 
 int kernel_type_of_call(int coll, int devOp, ncclDataType_t datatype) {
@@ -286,7 +287,10 @@ static ncclResult_t launch_ring(const Task* ts, int nTasks, bool ll128, hipEvent
     b.w.nChannels = std::max(b.w.nChannels, wi.nChannels);
   }
   b.nParts = nTasks;
-  const int v = ll128 ? kRingVariantLL128
+  // a wide op code: the wide ring's kernels, SIMPLE with the workgroup hand-off whatever the comm's wave setting
+  if (is_wide_op(devOp) && (ll128 || (t.coll != kAllReduce && t.coll != kReduceScatter))) return ncclInternalError;
+  const int v = is_wide_op(devOp) ? kRingVariantWide
+                : ll128 ? kRingVariantLL128
                 : comm->ringWave && ring_wave_kernel(kt, devOp, t.coll) ? kRingVariantWave : kRingVariantSimple;
   const hipError_t e = by_kernel_type(
       kt, [&]<int K>() { return ring_launch_any<K>(v, t.coll, devOp, b, comm->nThreads, t.stream, stop); });
@@ -597,7 +601,8 @@ static ncclResult_t launch_direct_reg_rooted(const Task& t, hipEvent_t stop) {
 
 // A call's path: select_algo on the comm's thresholds.
 static int choose_algo(const Task& t) {
-  // the wide sums: the staged direct path, at level 2 the one-hop LL kernel where select_algo answers LL
+  // the wide sums: the staged direct path, at level 2 the one-hop LL kernel where select_algo answers LL, the
+  // wide ring from the comm's VCCL_SUM_FP32_RING_THRESHOLD up
   if (is_wide_op(t.devOp))
     return sum_fp32_algo(sum_fp32_level(t.comm), policy_of(t.comm), t.coll, type_size(t.datatype), (int64_t)t.count);
   return select_algo(policy_of(t.comm), t.coll, type_size(t.datatype), (int64_t)t.count);

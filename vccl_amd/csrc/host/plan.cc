@@ -308,7 +308,13 @@ int sum_fp32_op(int level, int coll, int devOp, ncclDataType_t datatype) {
 int sum_fp32_algo(int level, const AlgoPolicy& p, int coll, int64_t eltSize, int64_t count) {
   if (level >= 2 && (coll == kAllReduce || coll == kReduceScatter) && select_algo(p, coll, eltSize, count) == kAlgoLL)
     return kAlgoLL;
+  if (p.sumFp32RingMin > 0 && level >= 1 && (coll == kAllReduce || coll == kReduceScatter) && p.algoForce <= 1 &&
+      (uint64_t)(count * eltSize) * (uint64_t)(coll == kAllReduce ? 1 : p.nRanks) >= p.sumFp32RingMin)
+    return kAlgoRing;
   return kAlgoDirect;
+}
+uint64_t sum_fp32_ring_min(int64_t threshold, int level, bool simpleAllowed) {
+  return threshold > 0 && level > 0 && simpleAllowed ? (uint64_t)threshold : 0;
 }
 uint64_t ll_rooted_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks) {
   if (threshold <= 0 || llSlotBytes <= 0 || !llAllowed || anyNet || nRanks > kOrderMaxRanks) return 0;
@@ -356,8 +362,10 @@ GroupTask group_task_of(int coll, size_t count, ncclDataType_t datatype, int dev
                    !ag && is_wide_sum_op(devOp)};
 }
 void sum_fp32_group_rule(std::vector<GroupTask>& g, int level, const AlgoPolicy& pol) {
-  if (g.size() == 1 && g[0].wide && sum_fp32_algo(level, pol, g[0].coll, g[0].eltSize, g[0].count) == kAlgoLL)
-    g[0].wide = false;
+  if (g.size() != 1 || !g[0].wide) return;
+  const int algo = sum_fp32_algo(level, pol, g[0].coll, g[0].eltSize, g[0].count);
+  if (algo == kAlgoLL) g[0].wide = false;
+  g[0].wideRing = algo == kAlgoRing;
 }
 uint32_t u32fp_encode(uint32_t x, int bitsPerPow2) {  // bitops.h:252-262
   const int log2x = 31 - __builtin_clz(x | 1);
@@ -402,7 +410,9 @@ void group_plan(const std::vector<GroupTask>& ts, int nRanks, int commChannels, 
       int64_t aggCount = ts[lst[a]].count;
       while (e < lst.size() && traffic[lst[e]] < 4 * traffic[lst[a]]) aggCount += ts[lst[e++]].count;
       const GroupTask& h = ts[lst[a]];
-      const int algo = !pol ? kAlgoRing : h.wide ? kAlgoDirect : select_algo(*pol, h.coll, h.eltSize, aggCount);
+      const int algo = !pol || h.wideRing ? kAlgoRing
+                       : h.wide          ? kAlgoDirect
+                                         : select_algo(*pol, h.coll, h.eltSize, aggCount);
       const int pr = proto_of_algo(algo);
       const int nc = ring_nmax_channels(h.coll, aggCount, h.eltSize, nRanks, commChannels, pr,
                                         pr == kProtoLL128 ? geo.ll128Threads : geo.nThreads);

@@ -87,6 +87,7 @@ struct AlgoPolicy {
   uint64_t directMax = 0, directRsAgMax = 0;
   uint64_t llRootedMax = 0;                // largest broadcast / reduce on the one-hop LL path (0 = off)
   uint64_t directRootedMax = 0;            // largest broadcast / reduce on the two-hop direct path (0 = off)
+  uint64_t sumFp32RingMin = 0;             // smallest wide all-reduce / reduce-scatter on the wide ring (0 = off)
 };
 // A comm's VCCL_LL_ROOTED_THRESHOLD as it takes effect: clamped to what one
 // LL slot holds; 0 without LL buffers, with LL excluded by NCCL_PROTO, with a
@@ -117,8 +118,16 @@ inline bool is_wide_sum_op(int devOp) { return devOp == kSumWideOp || devOp == k
 int sum_fp32_op(int level, int coll, int devOp, ncclDataType_t datatype);
 // The path of a call with a wide op on its own: LL where level 2 is in force
 // and select_algo answers LL for an all-reduce or reduce-scatter (never the
-// rooted LL), the staged direct path otherwise — in place of both rings.
+// rooted LL); else the wide SIMPLE ring (device/ring_wide.hpp) for an
+// all-reduce or reduce-scatter of at least p.sumFp32RingMin bytes (0: never)
+// — the all-reduce's count * eltSize, the reduce-scatter's whole nRanks-block
+// buffer — unless a path other than the SIMPLE ring is forced; the staged
+// direct path otherwise, in place of both native rings.
 int sum_fp32_algo(int level, const AlgoPolicy& p, int coll, int64_t eltSize, int64_t count);
+// A comm's VCCL_SUM_FP32_RING_THRESHOLD (bytes) as it takes effect: 0 where
+// the wide sums are off (`level` 0: sum_fp32_effective said no, or nobody
+// asked) or where NCCL_ALGO / NCCL_PROTO exclude the SIMPLE ring.
+uint64_t sum_fp32_ring_min(int64_t threshold, int level, bool simpleAllowed);
 int proto_of_algo(int algo);
 
 struct GroupTask {
@@ -127,6 +136,7 @@ struct GroupTask {
   int binKey;              // (func, devOp, type): ncclPrepareTasks' bins
   int funcKey;             // the device function (batches merge per function)
   bool wide = false;       // a wide op code: the staged direct path whatever the aggregate's size
+  bool wideRing = false;   // ... a group's only collective that sum_fp32_algo sends to the wide ring
 };
 // A call as the group planner takes it.  kernelType: dispatch.hpp
 // kernel_type_of (K_U8 for a byte copy), passed in so no kernel header is
@@ -134,7 +144,9 @@ struct GroupTask {
 GroupTask group_task_of(int coll, size_t count, ncclDataType_t datatype, int devOp, int kernelType);
 // A group holding ONE collective is a call on its own: where sum_fp32_algo
 // sends its wide call to LL, the `wide` flag is dropped and select_algo, asked
-// for that one call, answers LL.  Groups of several collectives keep the flag.
+// for that one call, answers LL; where it sends it to the wide ring, wideRing
+// is set and the planner answers the ring.  Groups of several collectives keep
+// the flag: staged direct.
 void sum_fp32_group_rule(std::vector<GroupTask>& g, int level, const AlgoPolicy& pol);
 
 struct PlanGeometry {

@@ -397,7 +397,14 @@ ncclResult_t setup_local(int n, int minCTAs, int maxCTAs, CommSetup* s, SetupSiz
   // and reduce-scatter at every size; 2: the LL, zero-copy and reduce folds
   // too): opt-in, it changes the result's bits
   s->sumFp32 = sum_fp32_of(*s, (int)param_int("SUM_FP32", 0), n, false, s->dRegionBytes > 0);
+  // ... and their SIMPLE ring with binary32 partial sums from this many bytes
+  // up: opt-in, untimed against the staged direct wide kernel
+  s->sumFp32RingBytes = std::max<int64_t>(0, param_int("SUM_FP32_RING_THRESHOLD", 0));
   return ncclSuccess;
+}
+
+size_t sum_fp32_ring_of(const CommSetup& s, int level) {
+  return (size_t)sum_fp32_ring_min(s.sumFp32RingBytes, level, (s.algoAllowed & kAllowSimple) != 0);
 }
 
 int sum_fp32_of(const CommSetup& s, int level, int nRanks, bool anyNet, bool inbox) {

@@ -86,6 +86,12 @@ struct CommSetup {
   // peers' inboxes mapped (launch.h sum_fp32_on).  The level: 1, or 2 — also
   // the LL and zero-copy folds and ncclReduce (plan.h sum_fp32_op).
   int sumFp32 = 0;
+  // Smallest wide all-reduce / reduce-scatter that takes the wide SIMPLE ring
+  // instead of the staged direct kernel, as asked for
+  // (VCCL_SUM_FP32_RING_THRESHOLD / vcclCommSetSumFp32RingThreshold, bytes;
+  // default 0 = off; not part of what vcclCommSetup reports either).  What
+  // takes effect follows the level in force (sum_fp32_ring_of).
+  int64_t sumFp32RingBytes = 0;
 };
 enum { kP2pOn = 0, kP2pOffEnv = 1, kP2pOffRanks = 2, kP2pOffNet = 3 };
 
@@ -121,6 +127,9 @@ size_t p2p_ll_max_of(const CommSetup& s, int64_t threshold, int nRanks, bool any
 // CommSetup::sumFp32 for a VCCL_SUM_FP32 of `level`, likewise (setup_local;
 // vcclCommSetSumFp32): the level in force, 0, 1 or 2.
 int sum_fp32_of(const CommSetup& s, int level, int nRanks, bool anyNet, bool inbox);
+// The comm's wide-ring threshold as it takes effect at `level` (the level in
+// force, sum_fp32_of's or launch.h sum_fp32_level's): plan.h sum_fp32_ring_min.
+size_t sum_fp32_ring_of(const CommSetup& s, int level);
 
 // A comm's VCCL_REG_THRESHOLD of `threshold` as it takes effect (plan.h
 // reg_max; inbox: every peer's inbox and direct flags are mapped).

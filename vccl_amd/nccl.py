@@ -71,7 +71,7 @@ EXPORTED = [
     "vcclRegRootedMax", "vcclRegRootedEligible", "vcclRegRootedPlan", "vcclCommRegRootedStats",
     "vcclCommSetRegRootedThreshold",
     # fp32-accumulated sums for f16 / bf16 / fp8: the engine's entry point and the comm's live knob
-    "vcclReduceCopyWide", "vcclCommSetSumFp32",
+    "vcclReduceCopyWide", "vcclCommSetSumFp32", "vcclCommSetSumFp32RingThreshold",
     # out of scope, exported so libnccl-linked binaries load: WARN + ncclInvalidUsage
     "ncclGroupSimulateEnd",
     # memory / registration / scalable init (what a libnccl caller such as
@@ -169,6 +169,7 @@ def lib() -> ctypes.CDLL:
         "vcclReduceCopyWide": [c_int, c_int, u64, c_int, c_int, ctypes.POINTER(vp), c_int, ctypes.POINTER(vp),
                                c_size, vp],
         "vcclCommSetSumFp32": [vp, c_int, ctypes.POINTER(c_int)],
+        "vcclCommSetSumFp32RingThreshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
         "vcclHostToDevRedOp": [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(u64)],
         "vcclKernelTypeOf": [c_int, c_int],
         "vcclBootstrapAllGather": [ctypes.POINTER(ncclUniqueId), c_int, c_int, vp, c_size],
@@ -1090,6 +1091,15 @@ class Comm:
         eff = ctypes.c_int(0)
         check(lib().vcclCommSetSumFp32(self.handle, int(level), ctypes.byref(eff)), "vcclCommSetSumFp32")
         return eff.value
+
+    def set_sum_fp32_ring_threshold(self, nbytes: int) -> int:
+        """vcclCommSetSumFp32RingThreshold: wide all-reduces / reduce-scatters of at least `nbytes` bytes take
+        the wide SIMPLE ring (binary32 partial sums) instead of the staged direct kernel
+        (VCCL_SUM_FP32_RING_THRESHOLD; 0: off).  Returns the threshold in force (0 while the wide sums are off)."""
+        eff = ctypes.c_int64(0)
+        check(lib().vcclCommSetSumFp32RingThreshold(self.handle, int(nbytes), ctypes.byref(eff)),
+              "vcclCommSetSumFp32RingThreshold")
+        return int(eff.value)
 
     def debug_set_epochs(self, ll_epoch: int, direct_epoch: int):
         """vcclCommDebugSetEpochs: overwrite the LL / direct call epochs (wrap tests)."""
