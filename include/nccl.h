@@ -179,6 +179,30 @@ ncclResult_t  ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count,
     ncclDataType_t datatype, ncclRedOp_t op, ncclComm_t comm, hipStream_t stream);
 ncclResult_t pncclAllReduce(const void* sendbuff, void* recvbuff, size_t count,
     ncclDataType_t datatype, ncclRedOp_t op, ncclComm_t comm, hipStream_t stream);
+/* RCCL's all-reduce with a bias (not VCCL API): the all-reduce of a row-parallel layer with its bias or residual
+ * folded inside the kernel instead of in a pass of its own.
+ *  - acc == NULL: exactly ncclAllReduce — same path, same kernels, same bits.
+ *  - Otherwise recv[i] = op(F[i], acc[i]), where F[i] is what ncclAllReduce would have stored for the same call on
+ *    the same path (same fold order, same per-step rounding to the element type): acc enters last, as one more
+ *    source of the native functor, with no preOp on it.  Path selection is that of the call without the bias.
+ *  - Every rank passes an acc of count elements with the same contents; each element takes the acc of the rank that
+ *    folds it (the shard's owner on the direct path, every rank on the LL path).  Differing contents are undefined.
+ *  - ncclSum, ncclProd, ncclMin and ncclMax over every datatype.  ncclAvg and PreMulSum operations are
+ *    ncclInvalidArgument: they scale by a preOp for the floating-point types and divide in a postOp for the integers,
+ *    so where the bias would sit relative to the scale differs by type.
+ *  - acc == recvbuff is ncclInvalidArgument; an acc that overlaps recvbuff in any other way is undefined.  In place
+ *    (sendbuff == recvbuff) and acc == sendbuff are allowed.  count == 0 is a successful no-op.  Every check
+ *    ncclAllReduce makes gives the same code here.
+ *  - With VCCL_SUM_FP32 on and ncclSum over f16 / bf16 / fp8: recv = narrow(F32 + widen(acc)), F32 the binary32 fold —
+ *    the bias is added in binary32 before the single narrowing (staged direct path; at level 2 also the LL path).
+ *    Such a call never takes the wide ring (VCCL_SUM_FP32_RING_THRESHOLD) and never negotiates zero-copy.
+ * The one-hop LL and two-shot direct kernels fold the bias themselves (no extra launch, no extra wire bytes); one
+ * rank is a single two-source reduce-copy; on every other path the plain collective is followed by one two-source
+ * reduce-copy recv = op(recv, acc) on the same stream, which for these ops gives the same bits. */
+ncclResult_t  ncclAllReduceWithBias(const void* sendbuff, void* recvbuff, size_t count,
+    ncclDataType_t datatype, ncclRedOp_t op, ncclComm_t comm, hipStream_t stream, const void* acc);
+ncclResult_t pncclAllReduceWithBias(const void* sendbuff, void* recvbuff, size_t count,
+    ncclDataType_t datatype, ncclRedOp_t op, ncclComm_t comm, hipStream_t stream, const void* acc);
 /* nccl.h.in:369-374; collectives.cc:145-158 */
 ncclResult_t  ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recvcount,
     ncclDataType_t datatype, ncclRedOp_t op, ncclComm_t comm, hipStream_t stream);

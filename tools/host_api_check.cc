@@ -223,6 +223,9 @@ int main() {
     EXPECT(vcclCommGroupAlgos(nullptr, 1, &c, &cnt, &d, &o, &a) == ncclInvalidArgument);
   }
   EXPECT(ncclAllReduce(nullptr, nullptr, 4, ncclFloat32, ncclSum, nullptr, nullptr) == ncclInvalidArgument);
+  // ... with a bias (RCCL's extension): the same check first, whatever acc is
+  EXPECT(ncclAllReduceWithBias(nullptr, nullptr, 4, ncclFloat32, ncclSum, nullptr, nullptr, nullptr) == ncclInvalidArgument);
+  EXPECT(pncclAllReduceWithBias(&v, &v, 4, ncclFloat32, ncclAvg, nullptr, nullptr, &v) == ncclInvalidArgument);
   EXPECT(ncclGroupStart() == ncclSuccess);
   EXPECT(ncclAllGather(nullptr, nullptr, 4, ncclFloat32, nullptr, nullptr) == ncclInvalidArgument);
   const ncclResult_t ge = ncclGroupEnd();

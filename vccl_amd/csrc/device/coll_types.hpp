@@ -313,4 +313,19 @@ __host__ __device__ inline DirectWork direct_work_with(DirectWork w, const Direc
   return w;
 }
 
+// ncclAllReduceWithBias: the argument of the bias kernels — the launch's work as every other
+// LL / direct all-reduce kernel takes it, and beside it the bias of each part (count elements / nbytes bytes, the
+// part's own).  Kept out of LLPart / DirectWork / DirectPart, so the kernels without a bias read the argument
+// layout they always read.
+struct LLBiasWork {
+  LLWork w;
+  const char* acc[kLLMaxParts];
+};
+static_assert(sizeof(LLBiasWork) <= 4096, "LLBiasWork must fit the kernel-argument budget");
+struct DirectBiasBatch {
+  DirectBatch b;
+  const char* acc[kDirectMaxWorks];  // acc[0]: b.w's, acc[i]: b.more[i - 1]'s
+};
+static_assert(sizeof(DirectBiasBatch) <= 4096, "DirectBiasBatch must fit the kernel-argument budget");
+
 }  // namespace vccl

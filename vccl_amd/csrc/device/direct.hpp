@@ -317,6 +317,108 @@ constexpr int direct_fold_unroll() {
   return is_wide_fn<Fn>() && sizeof(typename Fn::EltType) == 1 ? 1 : kDirectUnroll;
 }
 
+// ------------------------------------------------- the bias fold
+// ncclAllReduceWithBias: dst[i] = (src_0[i] (+) ... (+) src_{nS-1}[i]) (+) bias[i], the owner's phase-2 fold of the
+// all-reduce with the matching span of its own `acc` as one more source, entering last and without a preOp (the ops
+// that have a preOp or a postOp are refused at the API).  A variant of its own beside direct_rc — the ninth source
+// is a step after the source loop, not a wider loop — so the kernels without a bias keep their code.  For a wide
+// functor the bias is widened and added in binary32 before the single narrowing.
+//
+// Packs per thread and source: the bias adds one pack of loads per unrolled pack to the up to 8 x U of the sources,
+// so the variant unrolls by 2 only where the accumulator is the pack itself and an element is at least 2 bytes; the
+// byte types' per-element folds and every wide accumulator (8 or 16 registers per pack) take 1 (§4.18 table).
+template <class Fn>
+constexpr int direct_bias_unroll() {
+  return is_wide_fn<Fn>() || sizeof(typename Fn::EltType) == 1 ? 1 : kDirectUnroll;
+}
+// Pack p of a source k bytes past a 16-byte boundary, from aligned loads (the engine's shifted-source scheme,
+// reduce_copy.hpp: a pack past the end is clamped, lane 63 loads its successor pack itself, every other lane takes
+// the next lane's).  Every lane of the wave calls it.
+template <int P>
+__device__ __forceinline__ u32x4 direct_ld16_shifted(const char* p, int k, int64_t pk, int64_t nPacks) {
+  const u32x4 cur = ld16_body<P>(p, k, pk, nPacks);
+  if (k == 0) return cur;
+  u32x4 ext = cur;
+  if (__lane_id() == 63) ext = ld16<P>(p - k, (pk + 1 < nPacks ? pk + 1 : nPacks) * 16);
+  return realign(cur, ext, k);
+}
+// One wave (lane, 64 lanes, all active) folds nElts elements into the 16-byte-aligned `dst`.
+//  * every operand 16-byte aligned: U packs per lane, the loads of all nS sources and of the bias issued before the
+//    first reduce, as direct_rc batches them;
+//  * a source or the bias at another offset (a user buffer off alignment: the own input, `acc`, or both — the
+//    inbox regions and the destination are aligned by construction): one pack per lane and step, each shifted
+//    operand realigned in registers.  The engine itself is not used here: its operand table holds 8 sources and
+//    the 8-rank fold has 9;
+//  * operands off element alignment, or a destination off 16 bytes (neither is produced by the caller): elements.
+template <class Fn, int U, int LDP, int STP>
+__device__ __forceinline__ void direct_rc_bias(const Fn& fn, const char* const (&src)[kDirectMaxRanks], int nS,
+                                               const char* bias, char* dst, int64_t nElts, int lane) {
+  using T = typename Fn::EltType;
+  constexpr int64_t esz = (int64_t)sizeof(T);
+  if (nElts <= 0) return;
+  uintptr_t bits = (uintptr_t)bias;
+#pragma unroll
+  for (int s = 0; s < kDirectMaxRanks; s++)
+    if (s < nS) bits |= (uintptr_t)src[s];
+  const bool eltOnly = ((uintptr_t)dst & 15) != 0 || (bits & (uintptr_t)(esz - 1)) != 0;
+  const int64_t nPacks = eltOnly ? 0 : nElts * esz / 16;
+  if (bits & 15) {
+    const int kb = (int)((uintptr_t)bias & 15);
+    for (int64_t base = 0; base < nPacks; base += 64) {  // wave-uniform trip count: the lane shift needs every lane
+      const int64_t p = base + lane;
+      u32x4 v[kDirectMaxRanks];
+#pragma unroll
+      for (int s = 0; s < kDirectMaxRanks; s++)
+        if (s < nS) v[s] = direct_ld16_shifted<LDP>(src[s], (int)((uintptr_t)src[s] & 15), p, nPacks);
+      const u32x4 vb = direct_ld16_shifted<kPlain>(bias, kb, p, nPacks);
+      auto w = acc_first(fn, v[0], false);
+#pragma unroll
+      for (int s = 1; s < kDirectMaxRanks; s++)
+        if (s < nS) acc_add(fn, w, v[s], false);
+      acc_add(fn, w, vb, false);
+      if (p < nPacks) st16<STP>(dst, p * 16, acc_done(fn, w, false));
+    }
+  } else {
+    for (int64_t base = 0; base < nPacks; base += 64 * U) {
+      u32x4 v[kDirectMaxRanks][U], vb[U];
+#pragma unroll
+      for (int s = 0; s < kDirectMaxRanks; s++) {
+        if (s < nS) {
+#pragma unroll
+          for (int u = 0; u < U; u++) {
+            const int64_t p = base + u * 64 + lane;
+            if (p < nPacks) v[s][u] = ld16<LDP>(src[s], p * 16);
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int64_t p = base + u * 64 + lane;
+        if (p < nPacks) vb[u] = ld16<kPlain>(bias, p * 16);
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        auto w = acc_first(fn, v[0][u], false);
+#pragma unroll
+        for (int s = 1; s < kDirectMaxRanks; s++)
+          if (s < nS) acc_add(fn, w, v[s][u], false);
+        acc_add(fn, w, vb[u], false);  // the bias: last, one more source of the same functor
+        const int64_t p = base + u * 64 + lane;
+        if (p < nPacks) st16<STP>(dst, p * 16, acc_done(fn, w, false));
+      }
+    }
+  }
+  // Element path: the < 16-byte tail (or everything, see above).
+  for (int64_t i = nPacks * 16 / esz + lane; i < nElts; i += 64) {
+    auto w = elt_first(fn, ldT<LDP, T>(src[0], i), false);
+#pragma unroll
+    for (int s = 1; s < kDirectMaxRanks; s++)
+      if (s < nS) elt_add(fn, w, ldT<LDP, T>(src[s], i), false);
+    elt_add(fn, w, ldT<kPlain, T>(bias, i), false);
+    stT<STP, T>(dst, i, elt_done(fn, w, false));
+  }
+}
+
 // Copy nBytes from a 16-byte-aligned source to nD 16-byte-aligned
 // destinations (write-through): the direct all-reduce's broadcast of a
 // folded chunk (both ends are the output / inbox, aligned by construction),
@@ -425,8 +527,11 @@ __device__ __forceinline__ void direct_post(const DirectWork& w, const DirectPee
 // the reader's scatter of chunk c+2, which the reader issues after its gather
 // of chunk c.  Per-parity flags: a flag of parity p is raised again (chunk
 // c+2) only after its reader awaited chunk c's value (same chains).
-template <class Fn>
-__device__ void direct_allreduce_part(const DirectWork& w, uint32_t& e, int& shFail) {
+// BIAS (ncclAllReduceWithBias, the bias kernels only): the fold (a) takes the span of `acc` (the part's bias, count
+// elements) that matches the owner's block as one more source (direct_rc_bias); scatter, broadcast, gather, flags
+// and epochs are the same.
+template <class Fn, bool BIAS = false>
+__device__ void direct_allreduce_part(const DirectWork& w, uint32_t& e, int& shFail, const char* acc = nullptr) {
   using T = typename Fn::EltType;
   const Fn fn(load_op_arg(w.redArgPtr, w.redArgBytes, w.redArg));
   const auto cfn = direct_copy_fn(fn);  // scatter / gather copies
@@ -530,8 +635,12 @@ __device__ void direct_allreduce_part(const DirectWork& w, uint32_t& e, int& shF
             s[j] = q == me ? in + (off + cur) * esz
                            : myBuf + direct_region_off(0, par, q, n, w.regionBytes) + inOff + cur * esz;
           }
-          direct_rc<Fn, direct_fold_unroll<Fn>(), kSys, kPlain, kPlain>(fn, s, n, w.preOp ? n : 0, true, d, 1,
-                                                             end - cur, lane, 64);
+          if constexpr (BIAS)
+            direct_rc_bias<Fn, direct_bias_unroll<Fn>(), kSys, kPlain>(
+                fn, s, n, acc + (c0 + off + cur) * esz, res, end - cur, lane);
+          else
+            direct_rc<Fn, direct_fold_unroll<Fn>(), kSys, kPlain, kPlain>(fn, s, n, w.preOp ? n : 0, true, d, 1,
+                                                                          end - cur, lane, 64);
         }
         // (b) broadcast: this wave reads back what it just stored (same
         // wave, drained) and writes it into every peer's region (1, me).
@@ -1032,6 +1141,19 @@ __device__ __forceinline__ void direct_batch(const DirectBatch& bt, Body body) {
   __syncthreads();
   body(w, e, shFail);
   for (int i = 1; i < bt.nParts; i++) body(direct_work_with(w, bt.more[i - 1]), e, shFail);
+  epoch_retire(&w.comm->dEpoch, &w.comm->dDone, e);
+}
+// ... of ncclAllReduceWithBias calls (DirectBiasBatch): the same, every part with its bias.
+template <class Fn>
+__device__ __forceinline__ void direct_batch_bias(const DirectBiasBatch& bb) {
+  __shared__ int shFail;
+  const DirectWork& w = bb.b.w;
+  uint32_t e = __hip_atomic_load(&w.comm->dEpoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (threadIdx.x == 0) shFail = 0;
+  __syncthreads();
+  // one call site: the part function is inlined once (two sites left it a real call with spilled callee-saved VGPRs)
+  for (int i = 0; i < bb.b.nParts; i++)
+    direct_allreduce_part<Fn, true>(i ? direct_work_with(w, bb.b.more[i - 1]) : w, e, shFail, bb.acc[i]);
   epoch_retire(&w.comm->dEpoch, &w.comm->dDone, e);
 }
 

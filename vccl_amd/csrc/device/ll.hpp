@@ -192,10 +192,21 @@ __device__ __forceinline__ int ll_advance(const LLParts& sh, int nParts, int cur
   return cur;
 }
 
-template <class Fn>
-__device__ void ll_allreduce(const LLWork& w) {
+// BIAS (ncclAllReduceWithBias, the bias kernels only): every rank folds, so every rank applies the 8
+// bytes of its part's bias (`accs`: LLBiasWork::acc, one per part, the part's nbytes long) that match the line, after
+// the chain fold and before the postOp and the store — for a native functor one more reduce (fold (+) bias), for a
+// wide one one more binary32 add before the single narrowing.  The load is issued ahead of the line's slot loads, so
+// its latency overlaps theirs.  The per-part pointers sit in LDS beside the part table, filled the same way.
+template <class Fn, bool BIAS = false>
+__device__ void ll_allreduce(const LLWork& w, const char* const* accs = nullptr) {
   const Fn fn(load_op_arg(w.redArgPtr, w.redArgBytes, w.redArg));
   __shared__ LLParts sh;
+  __shared__ const char* shAcc[BIAS ? kLLMaxParts : 1];
+  if constexpr (BIAS) {
+#pragma unroll
+    for (int i = 0; i < kLLMaxParts; i++)
+      if ((int)threadIdx.x == 64 + i && i < w.nParts) shAcc[i] = accs[i];
+  }
   ll_load_parts(w, &sh);
   const uint32_t epoch = ll_epoch_of(w.comm);
   const int64_t nLines = w.nLines;
@@ -236,6 +247,8 @@ __device__ void ll_allreduce(const LLWork& w) {
     const LLPart& part = sh.p[pc];
     const int64_t pl = l - part.line0;
     typename LLAccOf<Fn>::Line acc{};  // the line itself, or its elements in binary32
+    uint64_t bias = 0;
+    if constexpr (BIAS) bias = ll_load8(shAcc[pc], pl, part.nbytes);  // same tail handling as part.send
     for (int hi = w.nRanks - 1; hi >= 0 && ok; hi -= kLLBatch) {
       const int lo = hi - kLLBatch + 1 > 0 ? hi - kLLBatch + 1 : 0;
       u32x4 v[kLLBatch];
@@ -273,8 +286,10 @@ __device__ void ll_allreduce(const LLWork& w) {
     }
     if (!ok) break;
     if constexpr (is_wide_fn<Fn>()) {
+      if constexpr (BIAS) ll_fold(fn, acc, bias, false, false);
       ll_store8(part.recv, pl, part.nbytes, ll_done(fn, acc));
     } else {
+      if constexpr (BIAS) acc = ll_apply(fn, acc, bias, 0);
       if (Fn::kPostOp) acc = ll_apply(fn, acc, 0, 2);
       ll_store8(part.recv, pl, part.nbytes, acc);
     }

@@ -1,6 +1,7 @@
 // Collective kernels for ONE kernel element type (VCCL_KT) and ONE family
 // (VCCL_PART: 0 ring, 1 LL, 2 direct, 3 LL128 ring, 4 ring with the per-wave
-// hand-off, 5 the wide sums' ring — separate objects, built in parallel):
+// hand-off, 5 the wide sums' ring, 6 / 7 the LL / direct all-reduce with a bias
+// — separate objects, built in parallel):
 // per reduction functor the ring all-reduce / reduce-scatter / reduce (one workgroup
 // per channel, enqueue.cc:1576-1666), the one-shot LL and the direct
 // (two-shot all-reduce, one-hop reduce-scatter, two-hop reduce) kernels; in
@@ -14,7 +15,7 @@
 #include "ring.hpp"
 #elif VCCL_PART == 5
 #include "ring_wide.hpp"
-#elif VCCL_PART == 1
+#elif VCCL_PART == 1 || VCCL_PART == 6
 #include "ll.hpp"
 #else
 #include "direct.hpp"
@@ -24,7 +25,7 @@
 #error "compile with -DVCCL_KT=<kernel element type>"
 #endif
 #ifndef VCCL_PART
-#error "compile with -DVCCL_PART=<0 ring | 1 LL | 2 direct | 3 LL128 ring | 4 per-wave ring | 5 wide ring>"
+#error "compile with -DVCCL_PART=<0 ring | 1 LL | 2 direct | 3 LL128 ring | 4 per-wave ring | 5 wide ring | 6 LL bias | 7 direct bias>"
 #endif
 
 namespace vccl {
@@ -295,6 +296,43 @@ hipError_t direct_launch<VCCL_KT>(int coll, int devOp, const DirectBatch& b, hip
   });
   return err;
 }
+
+#elif VCCL_PART == 6 || VCCL_PART == 7
+// PARTS 6 / 7: ncclAllReduceWithBias on the one-hop LL and the two-shot direct path (ll.hpp ll_allreduce<Fn, true>,
+// direct.hpp direct_allreduce_part<Fn, true>): the all-reduce only, Sum / Prod / MinMax over every kernel type and
+// the wide Sum over the four wide types — ncclAvg and PreMulSum are refused at the API, so no functor with a preOp
+// or a postOp is instantiated.  Objects of their own: the kernels without a bias are compiled as they always were.
+#if VCCL_PART == 6
+template <class Fn>
+__global__ __launch_bounds__(256) void k_ll_allreduce_bias(LLBiasWork w) {
+  ll_allreduce<Fn, true>(w.w, w.acc);
+}
+#define VCCL_BIAS_LAUNCH(Fn) launch_k(k_ll_allreduce_bias<Fn>, dim3(grid), dim3(256), stream, stop, w)
+template <>
+hipError_t ll_launch_bias<VCCL_KT>(int devOp, const LLBiasWork& w, int grid, hipStream_t stream, hipEvent_t stop) {
+#else
+template <class Fn>
+__global__ __launch_bounds__(kDirectThreads) void k_direct_allreduce_bias(DirectBiasBatch bb) {
+  direct_batch_bias<Fn>(bb);
+}
+#define VCCL_BIAS_LAUNCH(Fn) \
+  launch_k(k_direct_allreduce_bias<Fn>, dim3(w.b.w.nBlocks), dim3(kDirectThreads), stream, stop, w)
+template <>
+hipError_t direct_launch_bias<VCCL_KT>(int devOp, const DirectBiasBatch& w, hipStream_t stream, hipEvent_t stop) {
+#endif
+  using T = typename KTypeOf<VCCL_KT>::T;
+  if (devOp == OP_SUM_WIDE) {
+    if constexpr (wide_kernel_type(VCCL_KT)) return VCCL_BIAS_LAUNCH(FnSumWide<T>);
+    return hipErrorInvalidValue;
+  }
+  switch (devOp) {
+    case OP_SUM: return VCCL_BIAS_LAUNCH(FnSum<T>);
+    case OP_PROD: return VCCL_BIAS_LAUNCH(FnProd<T>);
+    case OP_MINMAX: return VCCL_BIAS_LAUNCH(FnMinMax<T>);
+  }
+  return hipErrorInvalidValue;
+}
+#undef VCCL_BIAS_LAUNCH
 
 #endif
 

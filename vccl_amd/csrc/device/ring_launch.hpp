@@ -67,6 +67,11 @@ inline hipError_t ring_launch_any(int variant, int coll, int devOp, const RingBa
 template <int K>
 hipError_t ll_launch(int coll, int devOp, const LLWork& w, int grid, hipStream_t stream, hipEvent_t stop);
 
+// ncclAllReduceWithBias on the LL path (ll.hpp ll_allreduce<Fn, true>; w.acc[i]: part i's bias): devOp Sum, Prod,
+// MinMax, or the wide Sum over a wide kernel type.  An object of its own per kernel type.
+template <int K>
+hipError_t ll_launch_bias(int devOp, const LLBiasWork& w, int grid, hipStream_t stream, hipEvent_t stop);
+
 // One-hop LL all-to-all(v) (ll.hpp ll_alltoall): a byte copy, built once in
 // the K_U8 unit; 256-thread workgroups, `grid` of them.
 hipError_t ll_a2a_launch(const LLA2aWork& w, int grid, hipStream_t stream, hipEvent_t stop);
@@ -77,6 +82,11 @@ hipError_t ll_a2a_launch(const LLA2aWork& w, int grid, hipStream_t stream, hipEv
 // All-gather only in the K_U8 unit.
 template <int K>
 hipError_t direct_launch(int coll, int devOp, const DirectBatch& b, hipStream_t stream, hipEvent_t stop);
+
+// ncclAllReduceWithBias on the direct path (direct.hpp direct_batch_bias; b.acc[i]: part i's bias): the ops of
+// ll_launch_bias, the grid of direct_launch.  An object of its own per kernel type.
+template <int K>
+hipError_t direct_launch_bias(int devOp, const DirectBiasBatch& b, hipStream_t stream, hipEvent_t stop);
 
 // Zero-copy direct all-reduce / reduce-scatter / all-gather over registered
 // buffers, with the staged kernel of the same collective as its in-kernel

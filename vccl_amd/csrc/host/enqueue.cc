@@ -79,13 +79,20 @@ static ncclResult_t args_check(ncclComm* comm, const char* name, ncclDataType_t 
 
 static ncclResult_t enqueue_check_impl(int coll, const char* name, const void* sendbuff,
                                        void* recvbuff, size_t count, ncclDataType_t dt,
-                                       ncclRedOp_t op, ncclComm* comm, hipStream_t stream, int root) {
+                                       ncclRedOp_t op, ncclComm* comm, hipStream_t stream, int root,
+                                       const void* acc = nullptr) {
   NCCLCHECK(comm_check(comm, name));
   if ((coll == kBroadcast || coll == kReduce) && (root < 0 || root >= comm->nRanks)) {  // argcheck.cc:66-69
     VWARN("%s : invalid root %d (root should be in the 0..%d range)", name, root, comm->nRanks);
     return ncclInvalidArgument;
   }
   NCCLCHECK(args_check(comm, name, dt, op, !is_copy_coll(coll)));
+  // a bias enters as one more source of the native functor: where it would sit relative to ncclAvg's divide or a
+  // PreMulSum scalar differs by type (a preOp for the floats, a postOp for the integers), so those ops are refused
+  if (acc && (op == ncclAvg || (int)op >= (int)ncclNumOps)) {
+    VWARN("%s : ncclAvg and PreMulSum operations take no bias (op %d)", name, (int)op);
+    return ncclInvalidArgument;
+  }
   VINFO("%s: opCount %lx sendbuff %p recvbuff %p count %zu datatype %d op %d comm %p [nranks=%d] stream %p",
         name, (unsigned long)comm->opCount, sendbuff, recvbuff, count, (int)dt, (int)op,
         (void*)comm, comm->nRanks, (void*)stream);
@@ -97,8 +104,12 @@ static ncclResult_t enqueue_check_impl(int coll, const char* name, const void* s
     VWARN("%s : NULL buffer", name);
     return ncclInvalidArgument;
   }
+  if (acc && acc == recvbuff) {
+    VWARN("%s : the bias must not be the receive buffer (acc == recvbuff)", name);
+    return ncclInvalidArgument;
+  }
   Task t{.coll = coll, .sendbuff = sendbuff, .recvbuff = recvbuff, .count = count, .datatype = dt,
-         .devOp = OP_COPY, .root = root, .comm = comm, .stream = stream};
+         .devOp = OP_COPY, .root = root, .comm = comm, .stream = stream, .acc = acc};
   if (!is_copy_coll(coll)) {
     NCCLCHECK(resolve_op(comm, op, dt, &t.devOp, &t.arg, &t.argPtr));
     t.devOp = sum_fp32_op(sum_fp32_level(comm), coll, t.devOp, dt);  // VCCL_SUM_FP32: the wide op code, or unchanged
@@ -117,8 +128,8 @@ static ncclResult_t enqueue_check_impl(int coll, const char* name, const void* s
 
 static ncclResult_t enqueue_check(int coll, const char* name, const void* sendbuff, void* recvbuff,
                                   size_t count, ncclDataType_t dt, ncclRedOp_t op, ncclComm* comm,
-                                  hipStream_t stream, int root = 0) {
-  return group_result(enqueue_check_impl(coll, name, sendbuff, recvbuff, count, dt, op, comm, stream, root));
+                                  hipStream_t stream, int root = 0, const void* acc = nullptr) {
+  return group_result(enqueue_check_impl(coll, name, sendbuff, recvbuff, count, dt, op, comm, stream, root, acc));
 }
 
 }  // namespace vccl
@@ -292,6 +303,13 @@ VCCL_EXPORT ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, siz
                                        ncclRedOp_t op, ncclComm_t comm, hipStream_t stream) {
   return enqueue_check(kAllReduce, "AllReduce", sendbuff, recvbuff, count, datatype, op, comm, stream);
 }
+// RCCL's all-reduce with a bias (include/nccl.h): recv = op(all-reduce, acc); a NULL acc is ncclAllReduce itself.
+VCCL_EXPORT ncclResult_t ncclAllReduceWithBias(const void* sendbuff, void* recvbuff, size_t count,
+                                               ncclDataType_t datatype, ncclRedOp_t op, ncclComm_t comm,
+                                               hipStream_t stream, const void* acc) {
+  if (!acc) return ncclAllReduce(sendbuff, recvbuff, count, datatype, op, comm, stream);
+  return enqueue_check(kAllReduce, "AllReduceWithBias", sendbuff, recvbuff, count, datatype, op, comm, stream, 0, acc);
+}
 VCCL_EXPORT ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recvcount,
                                            ncclDataType_t datatype, ncclRedOp_t op, ncclComm_t comm,
                                            hipStream_t stream) {
@@ -420,3 +438,4 @@ VCCL_PALIAS(ncclAllReduce) VCCL_PALIAS(ncclReduceScatter) VCCL_PALIAS(ncclAllGat
 VCCL_PALIAS(ncclReduce) VCCL_PALIAS(ncclBcast) VCCL_PALIAS(ncclGroupStart) VCCL_PALIAS(ncclGroupEnd)
 VCCL_PALIAS(ncclGroupSimulateEnd) VCCL_PALIAS(ncclRedOpCreatePreMulSum) VCCL_PALIAS(ncclRedOpDestroy)
 VCCL_PALIAS(ncclSend) VCCL_PALIAS(ncclRecv) VCCL_PALIAS(ncclAllToAll) VCCL_PALIAS(ncclAllToAllv)
+VCCL_PALIAS(ncclAllReduceWithBias)

@@ -152,7 +152,28 @@ static hipEvent_t stream_last_event(ncclComm* comm, const CaptureState& cs) {
 
 // ncclLaunchOneRank (onerank.cu:47-83): a copy, or the PreMulSum kernel.  An
 // in-place call without a preOp enqueues nothing.
+// ncclAllReduceWithBias: recv = op(first, acc), one launch of the engine's two-source reduce-copy with the call's
+// native functor on its stream.  One rank: first = sendbuff, the whole call.  More ranks, on a path without a bias
+// kernel (the rings, the zero-copy kernels): first = recvbuff, right behind the launch that carried the plain
+// collective — for a native functor op(F, acc) rounds as the fused fold's last step does.
+static ncclResult_t launch_bias_rc(const Task& t, const void* first) {
+  RCArgs a = {};
+  a.srcs[0] = (const char*)first;
+  a.srcs[1] = (const char*)t.acc;
+  a.dsts[0] = (char*)t.recvbuff;
+  a.nSrcs = 2;
+  a.nDsts = 1;
+  const hipError_t e = reduce_copy_launch(native_op_of(t.devOp), (int)t.datatype, t.arg, a, (int64_t)t.count, nullptr,
+                                          t.stream);
+  if (e != hipSuccess) {
+    VWARN("bias reduce-copy launch failed: %s", hipGetErrorString(e));
+    return ncclUnhandledCudaError;
+  }
+  return ncclSuccess;
+}
+
 static ncclResult_t launch_one_rank(const Task& t) {
+  if (t.acc) return launch_bias_rc(t, t.sendbuff);
   const size_t bytes = t.count * (size_t)type_size(t.datatype);
   RCArgs a = {};
   a.srcs[0] = (const char*)t.sendbuff;
@@ -336,7 +357,8 @@ static int ll_grid(const ncclComm* comm, int64_t lines) {
 static ncclResult_t launch_ll(const Task* ts, int nTasks, hipEvent_t stop) {
   const Task& t = ts[0];
   ncclComm* comm = t.comm;
-  LLWork w{};
+  LLBiasWork bw{};  // bw.acc: a bias launch's per-part pointers (ncclAllReduceWithBias)
+  LLWork& w = bw.w;
   fill_op_fields(w, t);
   w.rank = comm->rank;
   w.linesPerSlot = comm->llLines;
@@ -349,6 +371,8 @@ static ncclResult_t launch_ll(const Task* ts, int nTasks, hipEvent_t stop) {
     if (ts[i].coll != t.coll) return ncclInternalError;
     w.parts[i].send = (const char*)ts[i].sendbuff;
     w.parts[i].recv = (char*)ts[i].recvbuff;
+    bw.acc[i] = (const char*)ts[i].acc;
+    if ((ts[i].acc != nullptr) != (t.acc != nullptr)) return ncclInternalError;  // bias calls fuse among themselves
     w.parts[i].nbytes = (int64_t)ts[i].count * type_size(ts[i].datatype);
     w.parts[i].line0 = lines;
     // reduce: the call's own partition, as the reduce-scatter takes its block's
@@ -380,7 +404,10 @@ static ncclResult_t launch_ll(const Task* ts, int nTasks, hipEvent_t stop) {
   if (is_wide_op(t.devOp) && rooted) return ncclInternalError;  // the wide reduce never takes the rooted LL
   const int grid = ll_grid(comm, lines);
   const int devOp = copy ? OP_COPY : t.devOp;
-  const hipError_t e = by_kernel_type(kt, [&]<int K>() { return ll_launch<K>(t.coll, devOp, w, grid, t.stream, stop); });
+  if (t.acc && t.coll != kAllReduce) return ncclInternalError;
+  const hipError_t e = by_kernel_type(kt, [&]<int K>() {
+    return t.acc ? ll_launch_bias<K>(devOp, bw, grid, t.stream, stop) : ll_launch<K>(t.coll, devOp, w, grid, t.stream, stop);
+  });
   if (e != hipSuccess) {
     VWARN("LL kernel launch failed: %s", hipGetErrorString(e));
     return ncclUnhandledCudaError;
@@ -467,17 +494,19 @@ static ncclResult_t direct_work_of(const Task& t, DirectWork* out, int* ktOut, i
 static ncclResult_t launch_direct(const Task* ts, int nTasks, hipEvent_t stop) {
   const Task& t = ts[0];
   if (nTasks < 1 || nTasks > kDirectMaxWorks) return ncclInternalError;
-  DirectBatch b{};
+  DirectBiasBatch bb{};  // bb.acc: a bias launch's per-part pointers (ncclAllReduceWithBias)
+  DirectBatch& b = bb.b;
   int kt = -1, devOp = -1;
   int64_t blk = 0;
   for (int i = 0; i < nTasks; i++) {
     DirectWork wi;
     int kti, opi;
     NCCLCHECK(direct_work_of(ts[i], &wi, &kti, &opi));
-    if (i > 0 && (kti != kt || opi != devOp)) return ncclInternalError;
+    if (i > 0 && (kti != kt || opi != devOp || (ts[i].acc != nullptr) != (t.acc != nullptr))) return ncclInternalError;
     kt = kti;
     devOp = opi;
     blk = std::max(blk, wi.blkElts);
+    bb.acc[i] = (const char*)ts[i].acc;
   }
   NCCLCHECK(direct_work_of(t, &b.w, &kt, &devOp, nTasks > 1 ? blk : 0));
   for (int i = 1; i < nTasks; i++) {
@@ -488,7 +517,10 @@ static ncclResult_t launch_direct(const Task* ts, int nTasks, hipEvent_t stop) {
     b.w.nBlocks = std::max(b.w.nBlocks, wi.nBlocks);
   }
   b.nParts = nTasks;
-  const hipError_t e = by_kernel_type(kt, [&]<int K>() { return direct_launch<K>(t.coll, devOp, b, t.stream, stop); });
+  if (t.acc && t.coll != kAllReduce) return ncclInternalError;
+  const hipError_t e = by_kernel_type(kt, [&]<int K>() {
+    return t.acc ? direct_launch_bias<K>(devOp, bb, t.stream, stop) : direct_launch<K>(t.coll, devOp, b, t.stream, stop);
+  });
   if (e != hipSuccess) {
     VWARN("direct kernel launch failed: %s", hipGetErrorString(e));
     return ncclUnhandledCudaError;
@@ -603,8 +635,12 @@ static ncclResult_t launch_direct_reg_rooted(const Task& t, hipEvent_t stop) {
 static int choose_algo(const Task& t) {
   // the wide sums: the staged direct path, at level 2 the one-hop LL kernel where select_algo answers LL, the
   // wide ring from the comm's VCCL_SUM_FP32_RING_THRESHOLD up
-  if (is_wide_op(t.devOp))
-    return sum_fp32_algo(sum_fp32_level(t.comm), policy_of(t.comm), t.coll, type_size(t.datatype), (int64_t)t.count);
+  if (is_wide_op(t.devOp)) {
+    const int a =
+        sum_fp32_algo(sum_fp32_level(t.comm), policy_of(t.comm), t.coll, type_size(t.datatype), (int64_t)t.count);
+    // a bias call never takes the wide ring: a bias added behind it would not enter the binary32 fold
+    return t.acc && a == kAlgoRing ? (int)kAlgoDirect : a;
+  }
   return select_algo(policy_of(t.comm), t.coll, type_size(t.datatype), (int64_t)t.count);
 }
 
@@ -614,10 +650,27 @@ constexpr int kAlgoDirectRegRooted = 101;  // ... a broadcast / reduce
 // The zero-copy path of a call that is eligible for one, else `algo`.
 static int reg_algo_or(const Task& t, int algo) {
   // level 1 of the wide sums keeps to the staged path: such calls do not negotiate
-  if (is_wide_op(t.devOp) && sum_fp32_level(t.comm) < 2) return algo;
+  // ... and a wide call with a bias at any level, whose bias must enter the staged kernel's binary32 fold
+  if (is_wide_op(t.devOp) && (sum_fp32_level(t.comm) < 2 || t.acc)) return algo;
   return reg_task_eligible(t) ? kAlgoDirectReg : reg_rooted_task_eligible(t) ? kAlgoDirectRegRooted : algo;
 }
+// The paths whose kernels fold a bias themselves; behind every other one each bias call of the run gets its
+// reduce-copy (launch_bias_rc), and the ordering event is recorded behind those instead of bound to the collective.
+static bool bias_fused(int algo) { return algo == kAlgoLL || algo == kAlgoDirect; }
+static bool needs_bias_tail(int algo, const Task* ts, int n) {
+  return !bias_fused(algo) && std::any_of(ts, ts + n, [](const Task& t) { return t.acc != nullptr; });
+}
+static ncclResult_t launch_path_only(int algo, const Task* ts, int n, hipEvent_t stop);
 static ncclResult_t launch_path(int algo, const Task* ts, int n, hipEvent_t stop) {
+  if (!needs_bias_tail(algo, ts, n)) return launch_path_only(algo, ts, n, stop);
+  if (std::any_of(ts, ts + n, [](const Task& t) { return is_wide_op(t.devOp); })) return ncclInternalError;
+  NCCLCHECK(launch_path_only(algo, ts, n, nullptr));
+  for (int i = 0; i < n; i++)
+    if (ts[i].acc) NCCLCHECK(launch_bias_rc(ts[i], ts[i].recvbuff));  // on ts[i].stream = the run's stream
+  if (stop) HIPCHECK(hipEventRecord(stop, ts[0].stream));
+  return ncclSuccess;
+}
+static ncclResult_t launch_path_only(int algo, const Task* ts, int n, hipEvent_t stop) {
   if (algo == kAlgoDirectReg) return n == 1 ? launch_direct_reg(ts[0], stop) : ncclInternalError;
   if (algo == kAlgoDirectRegRooted) return n == 1 ? launch_direct_reg_rooted(ts[0], stop) : ncclInternalError;
   return algo == kAlgoLL ? launch_ll(ts, n, stop)
@@ -660,7 +713,7 @@ ncclResult_t launch_task(const Task& t) {
 // tasks' streams are joined before it and wait for it after.
 // Same comm, collective, kernel type and op (the caller compares the paths).
 static bool fusable(const Task& a, const Task& b) {
-  if (a.comm != b.comm || a.coll != b.coll) return false;
+  if (a.comm != b.comm || a.coll != b.coll || (a.acc != nullptr) != (b.acc != nullptr)) return false;
   if (is_copy_coll(a.coll)) return true;  // byte copies: any type
   return a.datatype == b.datatype && a.devOp == b.devOp && a.arg == b.arg && a.argPtr == b.argPtr;
 }
@@ -737,7 +790,8 @@ static ncclResult_t launch_planned(std::vector<Task>& tasks, const std::vector<i
   std::vector<GroupTask> g;
   for (int j : idx) {
     const Task& t = tasks[j];
-    g.push_back(group_task_of(t.coll, t.count, t.datatype, t.devOp, kernel_type_of_call(t.coll, t.devOp, t.datatype)));
+    g.push_back(group_task_of(t.coll, t.count, t.datatype, t.devOp, kernel_type_of_call(t.coll, t.devOp, t.datatype),
+                              t.acc != nullptr));
   }
   GroupPlanOut plan;
   const AlgoPolicy pol = policy_of(comm);

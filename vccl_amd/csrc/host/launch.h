@@ -54,6 +54,10 @@ struct Task {
   // kernel (launch_comm_p2p): 1 .. kRegA2aMaxCalls, the skip word its FIFO items
   // are predicated on (device/p2p_types.hpp P2pWork::skip); 0: never dropped.
   int skip;
+  // ncclAllReduceWithBias: the bias, count elements, folded in last (nullptr: none).  Such a call is a bin of its
+  // own in a group and fuses with bias calls only; the LL and direct launches carry it in their bias kernels, every
+  // other path is followed by one two-source reduce-copy recv = op(recv, acc) (launch.cc launch_bias_tail).
+  const void* acc;
 };
 
 // VCCL_SUM_FP32 / vcclCommSetSumFp32 as the comm's calls take it: the setup's

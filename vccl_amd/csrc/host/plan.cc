@@ -354,18 +354,18 @@ int proto_of_algo(int algo) {
 // No policy: every call RING / SIMPLE.  Restated for the tests in
 // oracle/vccl_sched.py (plan_schedule).
 // group_task_of: all-gather / broadcast are int8 copies (enqueue.cc:2400-2404), keyed as such.
-GroupTask group_task_of(int coll, size_t count, ncclDataType_t datatype, int devOp, int kernelType) {
+GroupTask group_task_of(int coll, size_t count, ncclDataType_t datatype, int devOp, int kernelType, bool bias) {
   const bool ag = is_copy_coll(coll);
   const CallSize sz = call_size(coll, count, datatype);
-  const int key = (coll * 16 + (ag ? (int)OP_SUM : devOp)) * 32;
+  const int key = (coll * 16 + (ag ? (int)OP_SUM : devOp)) * 32 + (bias ? kBiasKey : 0);
   return GroupTask{coll, sz.count, sz.eltSize, key + (ag ? (int)ncclInt8 : (int)datatype), key + kernelType,
-                   !ag && is_wide_sum_op(devOp)};
+                   !ag && is_wide_sum_op(devOp), false, bias};
 }
 void sum_fp32_group_rule(std::vector<GroupTask>& g, int level, const AlgoPolicy& pol) {
   if (g.size() != 1 || !g[0].wide) return;
   const int algo = sum_fp32_algo(level, pol, g[0].coll, g[0].eltSize, g[0].count);
   if (algo == kAlgoLL) g[0].wide = false;
-  g[0].wideRing = algo == kAlgoRing;
+  g[0].wideRing = algo == kAlgoRing && !g[0].bias;  // with a bias: the staged direct kernel
 }
 uint32_t u32fp_encode(uint32_t x, int bitsPerPow2) {  // bitops.h:252-262
   const int log2x = 31 - __builtin_clz(x | 1);

@@ -137,11 +137,16 @@ struct GroupTask {
   int funcKey;             // the device function (batches merge per function)
   bool wide = false;       // a wide op code: the staged direct path whatever the aggregate's size
   bool wideRing = false;   // ... a group's only collective that sum_fp32_algo sends to the wide ring
+  bool bias = false;       // ncclAllReduceWithBias: a bin (and a device function) of its own, never the wide ring
 };
 // A call as the group planner takes it.  kernelType: dispatch.hpp
 // kernel_type_of (K_U8 for a byte copy), passed in so no kernel header is
 // needed here.
-GroupTask group_task_of(int coll, size_t count, ncclDataType_t datatype, int devOp, int kernelType);
+// bias: an ncclAllReduceWithBias call — kBiasKey apart from the same call without one in both keys, so it
+// aggregates and fuses with bias calls of its (op, type) only, as a wide op code does through its devOp.
+constexpr int kBiasKey = 1 << 16;
+GroupTask group_task_of(int coll, size_t count, ncclDataType_t datatype, int devOp, int kernelType,
+                        bool bias = false);
 // A group holding ONE collective is a call on its own: where sum_fp32_algo
 // sends its wide call to LL, the `wide` flag is dropped and select_algo, asked
 // for that one call, answers LL; where it sends it to the wide ring, wideRing

@@ -48,6 +48,8 @@ EXPORTED = [
     "ncclReduce", "ncclBcast", "ncclBroadcast", "ncclCommSplit", "ncclResetDebugInit",
     # point-to-point over per-peer FIFOs (RCCL's all-to-alls grouped from them) and its planner
     "ncclSend", "ncclRecv", "ncclAllToAll", "ncclAllToAllv", "vcclP2pPlan",
+    # RCCL's all-reduce with a bias folded inside the LL and direct kernels
+    "ncclAllReduceWithBias",
     # LL send / recv on per-pair LL FIFOs: the threshold, the plan with LL messages, the counters, the live knob,
     # the wrap tests' step setter
     "vcclP2pLLMax", "vcclP2pPlanEx", "vcclCommP2pStats", "vcclCommSetP2pLLThreshold", "vcclCommDebugSetP2pLLSteps",
@@ -148,6 +150,7 @@ def lib() -> ctypes.CDLL:
         "ncclRedOpCreatePreMulSum": [ctypes.POINTER(c_int), vp, c_int, c_int, vp],
         "ncclRedOpDestroy": [c_int, vp],
         "ncclAllReduce": [vp, vp, c_size, c_int, c_int, vp, vp],
+        "ncclAllReduceWithBias": [vp, vp, c_size, c_int, c_int, vp, vp, vp],
         "ncclReduceScatter": [vp, vp, c_size, c_int, c_int, vp, vp],
         "ncclAllGather": [vp, vp, c_size, c_int, vp, vp],
         "ncclBroadcast": [vp, vp, c_size, c_int, c_int, vp, vp],
@@ -867,7 +870,12 @@ class Comm:
     def async_error(self) -> int:
         return self._q(lib().ncclCommGetAsyncError, "ncclCommGetAsyncError")
 
-    def all_reduce(self, send: int, recv: int, count: int, dtype: int, op: int, stream: int = 0):
+    def all_reduce(self, send: int, recv: int, count: int, dtype: int, op: int, stream: int = 0, acc: int = None):
+        """acc: the address of a bias of `count` elements, folded in last (ncclAllReduceWithBias)."""
+        if acc is not None:
+            check(lib().ncclAllReduceWithBias(send, recv, count, dtype, op, self.handle, stream, acc),
+                  "ncclAllReduceWithBias")
+            return
         check(lib().ncclAllReduce(send, recv, count, dtype, op, self.handle, stream), "ncclAllReduce")
 
     def reduce_scatter(self, send: int, recv: int, recvcount: int, dtype: int, op: int,
