@@ -81,6 +81,22 @@ ncclResult_t vcclReduceCopyWide(vcclDevRedOp_t devOp, ncclDataType_t datatype, u
                                 int preOpSrcs, int nSrcs, const void* const* srcs, int nDsts,
                                 void* const* dsts, size_t nElts, hipStream_t stream);
 
+/* The MXFP8 codec on its own: `count` elements of
+ * ncclFloat16, ncclBfloat16 or ncclFloat32 <-> wire tiles.  A tile is 512
+ * elements = 512 OCP E4M3 payload bytes followed by one 16-byte line of 16 E8M0
+ * scale bytes, one per 32-element block (528 bytes); `wire` holds
+ * ceil(count / 512) whole tiles and is 16-byte aligned; a short last block
+ * counts its missing elements as 0.  Per block: amax == 0 gives scale 127 and
+ * payload 0; else scale s = max(e + 127, 0), e the smallest integer with
+ * amax * 2^-e <= 448, payload = E4M3(v * 2^(127 - s)) RN-even; a NaN or an
+ * infinity anywhere in the block gives scale 255, payload 0, and every element
+ * of it unpacks to NaN.  Unpack: widen(byte) * 2^(s - 127), narrowed RN-even to
+ * the datatype.  Values below 2^-100 in magnitude may flush to zero.  src / dst
+ * at any element alignment (off 16 bytes: an element path).  Another datatype,
+ * a NULL pointer with count > 0 or a misaligned wire: ncclInvalidArgument. */
+ncclResult_t vcclMxfp8Pack(const void* src, ncclDataType_t datatype, size_t count, void* wire, hipStream_t stream);
+ncclResult_t vcclMxfp8Unpack(const void* wire, ncclDataType_t datatype, size_t count, void* dst, hipStream_t stream);
+
 /* hostToDevRedOp for built-in ops: devOp + 64-bit opArg (xormask for
  * min/max, 1/nRanks bits for float avg, nRanks<<1|signed for integer avg). */
 ncclResult_t vcclHostToDevRedOp(ncclRedOp_t op, ncclDataType_t datatype, int nRanks,

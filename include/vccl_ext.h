@@ -364,6 +364,30 @@ ncclResult_t vcclCommSetSumFp32(ncclComm_t comm, int on, int* effective);
  *                    takes effect with vcclCommSetSumFp32) or where NCCL_ALGO /
  *                    NCCL_PROTO exclude the SIMPLE ring. */
 ncclResult_t vcclCommSetSumFp32RingThreshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
+/* MXFP8 wire format for the direct f16 / bf16 all-reduce (opt-in:
+ * VCCL_AR_MXFP8_THRESHOLD=<bytes> at init, default 0 = off: nothing allocated,
+ * no plan and no result changed).  An ncclAllReduce
+ * with ncclSum over ncclFloat16 / ncclBfloat16 of at least that many bytes
+ * (count * 2) travels as 32-element blocks of E4M3 under one scale byte, 33/32
+ * bytes per element and hop instead of 2:
+ *   out = narrow(D(E(D(E(x_0)) + ... + D(E(x_{n-1}))))), every + a binary32 add
+ * in ascending rank order, E / D as vcclMxfp8Pack / vcclMxfp8Unpack (blocks by
+ * global element index).  LOSSY by design; every rank holds the same bits, in
+ * place or not, at any buffer alignment.  Such a call takes the staged direct
+ * launch at every size (vcclCommCollAlgo says vcclAlgoDirect), never
+ * negotiates zero-copy, is a bin of its own in a group and wins over
+ * VCCL_SUM_FP32.  ncclAvg, PreMulSum, other ops and types,
+ * ncclAllReduceWithBias and every other collective are unchanged.  Untimed
+ * over xGMI.
+ *   vcclCommSetArMxfp8Threshold  the same for later calls; every rank calls it
+ *                    alike, outside a group.  bytes 0: off; negative:
+ *                    ncclInvalidArgument.  *effective = what is in force: 0
+ *                    without mapped inboxes, outside 2..8 ranks, with a peer
+ *                    behind the net proxy or Direct excluded by NCCL_ALGO.
+ *   vcclCommArMxfp8Stats  *launches = the all-reduce calls this comm has
+ *                    launched on the MXFP8 kernel. */
+ncclResult_t vcclCommSetArMxfp8Threshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
+ncclResult_t vcclCommArMxfp8Stats(ncclComm_t comm, uint64_t* launches);
 /* Zero-copy direct all-reduce / reduce-scatter / all-gather over
  * ncclCommRegister'ed buffers (opt-in: VCCL_REG_THRESHOLD=<bytes> at init,
  * default 0 = off).

@@ -545,6 +545,30 @@ int main() {
     src[0] = nullptr;
     EXPECT(vcclReduceCopyWide(vcclDevSum, ncclBfloat16, 0, 0, 1, src, 1, dst, 8, nullptr) == ncclInvalidArgument);
   }
+  // the MXFP8 switch without a comm, and every refusal the codec's entry points make before a launch
+  {
+    int64_t eff64 = 7;
+    uint64_t launches = 7;
+    for (int64_t bytes : {(int64_t)0, (int64_t)1, (int64_t)-1, INT64_MAX})
+      EXPECT(vcclCommSetArMxfp8Threshold(nullptr, bytes, &eff64) == ncclInvalidArgument && eff64 == 7);
+    EXPECT(vcclCommSetArMxfp8Threshold(nullptr, 4096, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclCommArMxfp8Stats(nullptr, &launches) == ncclInvalidArgument && launches == 7);
+    alignas(16) char buf[1056] = {};
+    for (int dt = 0; dt < (int)ncclNumTypes; dt++) {
+      const bool has = dt == ncclFloat16 || dt == ncclBfloat16 || dt == ncclFloat32;
+      // zero elements: success for a type the codec has, before any pointer is read
+      const ncclResult_t want = has ? ncclSuccess : ncclInvalidArgument;
+      EXPECT(vcclMxfp8Pack(nullptr, (ncclDataType_t)dt, 0, nullptr, nullptr) == want);
+      EXPECT(vcclMxfp8Unpack(nullptr, (ncclDataType_t)dt, 0, nullptr, nullptr) == want);
+      if (!has) EXPECT(vcclMxfp8Pack(buf, (ncclDataType_t)dt, 8, buf + 512, nullptr) == ncclInvalidArgument);
+    }
+    // a NULL operand, and a wire off 16 bytes
+    EXPECT(vcclMxfp8Pack(nullptr, ncclBfloat16, 8, buf, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclMxfp8Pack(buf, ncclBfloat16, 8, nullptr, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclMxfp8Unpack(nullptr, ncclFloat32, 8, buf, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclMxfp8Pack(buf, ncclFloat16, 8, buf + 520, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclMxfp8Unpack(buf + 8, ncclFloat16, 8, buf + 528, nullptr) == ncclInvalidArgument);
+  }
   // the registration table (vcclRegTable*) against a reference model under
   // random inserts, lookups and removals, with invalid entries and handles;
   // the zero-copy threshold, eligibility and step lists on random arguments

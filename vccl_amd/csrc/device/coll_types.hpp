@@ -166,6 +166,13 @@ __host__ __device__ __forceinline__ size_t direct_flag_off(int phase, int parity
 constexpr size_t kDirectFlagBytes =
     (size_t)kDirectInboxRegions * kDirectMaxRanks * kDirectMaxBlocks * kDirectFlagStride;
 
+// The MXFP8 wire format (mxfp8.hpp): blocks of 32 elements under one scale byte, tiles of 512
+// elements = 512 payload bytes + one 16-byte line of 16 scale bytes.  The direct all-reduce in the format
+// (direct_mx.hpp) takes a DirectWork whose chunkElts and blkElts are whole tiles (host/plan.cc direct_mx_plan).
+constexpr int kMxBlockElts = 32;
+constexpr int kMxTileElts = 512;
+constexpr int kMxTileBytes = kMxTileElts + kMxTileElts / kMxBlockElts;  // 528
+
 // Group aggregation of direct calls (DirectBatch: part 0 in `w`, the others
 // as DirectPart — what differs per call), run in order by one launch.
 constexpr int kDirectMaxWorks = 16;

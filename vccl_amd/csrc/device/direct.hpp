@@ -96,6 +96,13 @@
 //                    non-roots included, although they wait for no data.
 // In the LL protocol the job of the closing round needed the arrival token of
 // the rooted LL kernels (ll.hpp); here the closing flag round does it.
+//    MXFP8          (direct_mx.hpp, a launch of its own: the all-reduce with the
+//    all-reduce      MXFP8 wire format) the all-reduce's line word for word — one
+//                    position per chunk, two parities: the fold and the broadcast
+//                    of wire tiles follow direct_wait(0) (R1), the gather's
+//                    direct_wait(1) closes the chunk (R2); its regions hold wire
+//                    tiles, workgroup b's at bytes [528 b blkTiles, 528 (b + 1)
+//                    blkTiles) of every region;
 //    zero-copy      (direct_reg.hpp, a launch of its own over registered
 //    AR / RS / AG    buffers) spends one position on a negotiation — flags
 //                    only, a descriptor riding in the flag's own line: post (0),

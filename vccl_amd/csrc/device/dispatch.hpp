@@ -45,8 +45,13 @@ __host__ __device__ inline int kernel_type_of(int devOp, int type) {
 // and, like any other op code, its own bin of the group plan.
 enum : int { OP_SUM_WIDE = 5, OP_PREMULSUM_WIDE = 6 };
 __host__ __device__ inline bool is_wide_op(int devOp) { return devOp == OP_SUM_WIDE || devOp == OP_PREMULSUM_WIDE; }
+// The MXFP8 all-reduce (direct_mx.hpp): one more op code of the library's own, given at enqueue
+// to an eligible ncclSum all-reduce over f16 / bf16 and refused by kernel_type_of like the wide ones.
+enum : int { OP_SUM_MXFP8 = 7 };
+__host__ __device__ inline bool is_mx_op(int devOp) { return devOp == OP_SUM_MXFP8; }
 __host__ __device__ inline int native_op_of(int devOp) {
-  return devOp == OP_SUM_WIDE ? (int)OP_SUM : devOp == OP_PREMULSUM_WIDE ? (int)OP_PREMULSUM : devOp;
+  if (devOp == OP_SUM_WIDE || devOp == OP_SUM_MXFP8) return OP_SUM;
+  return devOp == OP_PREMULSUM_WIDE ? (int)OP_PREMULSUM : devOp;
 }
 // The wide counterpart of (devOp, type), or -1: Sum / PreMulSum over f16, bf16, e4m3, e5m2.
 __host__ __device__ inline int wide_op_of(int devOp, int type) {

@@ -45,5 +45,9 @@ hipError_t rc_launch(int devOp, const RCArgs& a, int64_t nElts, uint64_t redArg,
 template <int K>
 hipError_t rc_launch_wide(int devOp, const RCArgs& a, int64_t nElts, uint64_t redArg, const LaunchGeom& lg,
                           hipStream_t stream);
+// The MXFP8 codec on its own (mxfp8.hpp; K one of K_F16, K_BF16, K_F32): pack `count` elements at src into wire
+// tiles at dst, or unpack wire tiles at src into `count` elements at dst.
+template <int K>
+hipError_t mxfp8_codec_launch(bool pack, const void* src, void* dst, int64_t count, hipStream_t stream);
 
 }  // namespace vccl

@@ -136,6 +136,26 @@ extern "C" ncclResult_t vcclReduceCopyWide(vcclDevRedOp_t devOp, ncclDataType_t 
   return err == hipSuccess ? ncclSuccess : ncclUnhandledCudaError;
 }
 
+// The MXFP8 codec on its own (mxfp8.hpp): f16 / bf16 / f32 <-> wire tiles.
+static ncclResult_t mxfp8_codec(bool pack, const void* src, ncclDataType_t datatype, size_t count, void* dst,
+                                const void* wire, hipStream_t stream) {
+  if (datatype != ncclFloat16 && datatype != ncclBfloat16 && datatype != ncclFloat32) return ncclInvalidArgument;
+  if (count == 0) return ncclSuccess;
+  if (!src || !dst || ((uintptr_t)wire & 15) != 0 || count > (size_t)1 << 56) return ncclInvalidArgument;
+  const hipError_t err = datatype == ncclFloat16    ? mxfp8_codec_launch<K_F16>(pack, src, dst, (int64_t)count, stream)
+                         : datatype == ncclBfloat16 ? mxfp8_codec_launch<K_BF16>(pack, src, dst, (int64_t)count, stream)
+                                                    : mxfp8_codec_launch<K_F32>(pack, src, dst, (int64_t)count, stream);
+  return err == hipSuccess ? ncclSuccess : ncclUnhandledCudaError;
+}
+extern "C" ncclResult_t vcclMxfp8Pack(const void* src, ncclDataType_t datatype, size_t count, void* wire,
+                                      hipStream_t stream) {
+  return mxfp8_codec(true, src, datatype, count, wire, wire, stream);
+}
+extern "C" ncclResult_t vcclMxfp8Unpack(const void* wire, ncclDataType_t datatype, size_t count, void* dst,
+                                        hipStream_t stream) {
+  return mxfp8_codec(false, wire, datatype, count, dst, wire, stream);
+}
+
 extern "C" int vcclKernelTypeOf(int devOp, ncclDataType_t datatype) {
   return kernel_type_of(devOp, (int)datatype);
 }

@@ -88,6 +88,12 @@ hipError_t direct_launch(int coll, int devOp, const DirectBatch& b, hipStream_t 
 template <int K>
 hipError_t direct_launch_bias(int devOp, const DirectBiasBatch& b, hipStream_t stream, hipEvent_t stop);
 
+// The two-shot direct all-reduce with the MXFP8 wire format (direct_mx.hpp; device op OP_SUM_MXFP8, K_F16 or
+// K_BF16): the batch and the grid of direct_launch, the geometry in wire tiles (host/plan.cc direct_mx_plan).  An
+// object of its own per kernel type (mx_kernels.hip).
+template <int K>
+hipError_t direct_launch_mx(const DirectBatch& b, hipStream_t stream, hipEvent_t stop);
+
 // Zero-copy direct all-reduce / reduce-scatter / all-gather over registered
 // buffers, with the staged kernel of the same collective as its in-kernel
 // fallback (direct_reg.hpp): one call per launch, rw.w.nBlocks workgroups.

@@ -112,7 +112,10 @@ static ncclResult_t enqueue_check_impl(int coll, const char* name, const void* s
          .devOp = OP_COPY, .root = root, .comm = comm, .stream = stream, .acc = acc};
   if (!is_copy_coll(coll)) {
     NCCLCHECK(resolve_op(comm, op, dt, &t.devOp, &t.arg, &t.argPtr));
-    t.devOp = sum_fp32_op(sum_fp32_level(comm), coll, t.devOp, dt);  // VCCL_SUM_FP32: the wide op code, or unchanged
+    // VCCL_AR_MXFP8_THRESHOLD: the MXFP8 op code for an eligible all-reduce (it wins over the wide sum: it
+    // accumulates in binary32 anyway); else VCCL_SUM_FP32: the wide op code, or unchanged
+    t.devOp = ar_mxfp8_op(ar_mxfp8_min_of(comm), coll, t.devOp, dt, count, acc != nullptr);
+    if (t.devOp != kSumMxOp) t.devOp = sum_fp32_op(sum_fp32_level(comm), coll, t.devOp, dt);
   }
   if (*(volatile int*)comm->errorFlag) {
     const ncclResult_t e = error_word_result(comm);

@@ -91,6 +91,11 @@ VCCL_EXPORT ncclResult_t vcclCommCollAlgo(ncclComm_t comm, int coll, size_t coun
   const int level = sum_fp32_level(comm);
   const bool wide = is_wide_op(sum_fp32_op(level, coll, OP_SUM, datatype));
   const AlgoPolicy pol = policy_of(comm);
+  // VCCL_AR_MXFP8_THRESHOLD: an eligible sum all-reduce takes the staged direct launch at every size
+  if (ar_mxfp8_op(ar_mxfp8_min_of(comm), coll, OP_SUM, datatype, count, false) == kSumMxOp) {
+    *algo = public_algo(kAlgoDirect);
+    return ncclSuccess;
+  }
   *algo = public_algo(wide ? sum_fp32_algo(level, pol, coll, type_size(datatype), (int64_t)count)
                            : select_algo(pol, coll, type_size(datatype), (int64_t)count));
   return ncclSuccess;
@@ -129,7 +134,7 @@ VCCL_EXPORT ncclResult_t vcclRingChunkOf(size_t count, ncclDataType_t datatype, 
 static ncclResult_t group_plan_export(int nCalls, const int* colls, const size_t* counts, const int* datatypes,
                                       const int* ops, int nRanks, int nChannels, const PlanGeometry& geo,
                                       const AlgoPolicy* pol, int* algos, int* order, int* planOf, int64_t* cbd,
-                                      int sumFp32 = 0) {
+                                      int sumFp32 = 0, uint64_t arMxfp8Min = 0) {
   if (nCalls < 1 || !colls || !counts || !datatypes || !ops || !order || !planOf || !cbd || nRanks < 1 ||
       nChannels < 1 || nChannels > kMaxChannels || geo.stepBytes < 4096 || geo.nThreads < 64 ||
       geo.ll128StepBytes < 1920 * 16 || geo.ll128Threads < 64)
@@ -144,7 +149,9 @@ static ncclResult_t group_plan_export(int nCalls, const int* colls, const size_t
     if (!is_copy_coll(c)) NCCLCHECK(host_to_dev_redop((ncclRedOp_t)ops[i], dt, nRanks, &devOp, &arg));
     const int kt = kernel_type_of_call(c, devOp, dt);
     if (kt < 0) return ncclInvalidArgument;
-    g.push_back(group_task_of(c, counts[i], dt, sum_fp32_op(sumFp32, c, devOp, dt), kt));
+    int op = ar_mxfp8_op(arMxfp8Min, c, devOp, dt, counts[i], false);  // as enqueue gives the op codes
+    if (op != kSumMxOp) op = sum_fp32_op(sumFp32, c, devOp, dt);
+    g.push_back(group_task_of(c, counts[i], dt, op, kt));
   }
   GroupPlanOut p;
   if (pol) sum_fp32_group_rule(g, sumFp32, *pol);
@@ -196,7 +203,7 @@ VCCL_EXPORT ncclResult_t vcclCommGroupAlgos(ncclComm_t comm, int nCalls, const i
   const PlanGeometry geo{comm->stepBytes, comm->nThreads, ll128 ? comm->ll128StepBytes : kDefaultLL128.stepBytes,
                          ll128 ? comm->ll128Threads : kDefaultLL128.nThreads};
   return group_plan_export(nCalls, colls, counts, datatypes, ops, comm->nRanks, comm->nChannels, geo, &pol, algos,
-                           order.data(), planOf.data(), cbd.data(), sum_fp32_level(comm));
+                           order.data(), planOf.data(), cbd.data(), sum_fp32_level(comm), ar_mxfp8_min_of(comm));
 }
 
 // A comm's VCCL_P2P_LL_THRESHOLD as it takes effect.
@@ -518,6 +525,25 @@ VCCL_EXPORT ncclResult_t vcclCommSetSumFp32RingThreshold(ncclComm_t comm, int64_
   if (bytes < 0) return ncclInvalidArgument;
   comm->sumFp32RingBytes = bytes;
   if (effective) *effective = (int64_t)sum_fp32_ring_of(*comm, sum_fp32_level(comm));
+  return ncclSuccess;
+}
+
+// The MXFP8 wire format for later ncclSum all-reduces over f16 / bf16 of at least `bytes` bytes (as
+// VCCL_AR_MXFP8_THRESHOLD at init; 0: off): every rank must call it alike, outside a group.
+VCCL_EXPORT ncclResult_t vcclCommSetArMxfp8Threshold(ncclComm_t comm, int64_t bytes, int64_t* effective) {
+  NCCLCHECK(comm_check(comm, "vcclCommSetArMxfp8Threshold"));
+  if (bytes < 0) return ncclInvalidArgument;
+  // a comm with a net peer maps no inbox: dPeers says both
+  comm->arMxfp8MinBytes = ar_mxfp8_of(*comm, bytes, comm->nRanks, comm->dPeers == nullptr, comm->dPeers != nullptr);
+  if (effective) *effective = (int64_t)comm->arMxfp8MinBytes;
+  return ncclSuccess;
+}
+
+// All-reduce calls this comm launched on the MXFP8 direct kernel.
+VCCL_EXPORT ncclResult_t vcclCommArMxfp8Stats(ncclComm_t comm, uint64_t* launches) {
+  NCCLCHECK(comm_check(comm, "vcclCommArMxfp8Stats"));
+  if (!launches) return ncclInvalidArgument;
+  *launches = comm->arMxfp8Launches;
   return ncclSuccess;
 }
 

@@ -33,6 +33,7 @@ static_assert((int)OP_SUM == (int)vcclDevSum && (int)OP_PROD == (int)vcclDevProd
                   (int)OP_MINMAX == (int)vcclDevMinMax && (int)OP_PREMULSUM == (int)vcclDevPreMulSum &&
                   (int)OP_SUMPOSTDIV == (int)vcclDevSumPostDiv,
               "OP_* and vcclDevRedOp_t are one enumeration");
+static_assert((int)OP_SUM_MXFP8 == kSumMxOp, "plan.h names the MXFP8 op code without the kernel headers");
 static_assert((int)OP_SUM_WIDE == kSumWideOp && (int)OP_PREMULSUM_WIDE == kPreMulSumWideOp,
               "the wide op codes of plan.h are dispatch.hpp's");
 
@@ -446,6 +447,22 @@ static ncclResult_t direct_work_of(const Task& t, DirectWork* out, int* ktOut, i
     shard0 = direct_shard_elts(w.chunkElts, (int)rp.owner.size(), eltAlign);
     // reduce: the call's own partition under SIMPLE, as the ring reduce folds it
     if (t.coll == kReduce) w.cbd = rs_cbd(t, kProtoSimple);
+  } else if (is_mx_op(t.devOp)) {
+    // the MXFP8 all-reduce: whole wire tiles (plan.cc direct_mx_plan); it folds in rank order, no partition
+    if (t.coll != kAllReduce || (t.datatype != ncclFloat16 && t.datatype != ncclBfloat16)) return ncclInternalError;
+    DirectMxPlanOut mp;
+    if (direct_mx_plan(n, count, comm->dRegionBytes, comm->minCTAs, comm->maxCTAs, comm->directMaxBlocks, blkForce,
+                       &mp) != ncclSuccess)
+      return ncclInternalError;
+    w.chunkElts = mp.chunkElts;
+    w.nChunks = mp.nChunks;
+    w.blkElts = mp.blkElts;
+    w.nBlocks = mp.nBlocks;
+    w.regionBytes = comm->dRegionBytes;
+    *out = w;
+    *ktOut = t.datatype == ncclFloat16 ? K_F16 : K_BF16;
+    *devOpOut = t.devOp;
+    return ncclSuccess;
   } else if (t.coll == kAllReduce) {
     // Chunk: as many elements as fit one shard per inbox region, a multiple
     // of n x 16 bytes; the shard of the largest chunk is cut into blocks.
@@ -518,9 +535,17 @@ static ncclResult_t launch_direct(const Task* ts, int nTasks, hipEvent_t stop) {
   }
   b.nParts = nTasks;
   if (t.acc && t.coll != kAllReduce) return ncclInternalError;
-  const hipError_t e = by_kernel_type(kt, [&]<int K>() {
-    return t.acc ? direct_launch_bias<K>(devOp, bb, t.stream, stop) : direct_launch<K>(t.coll, devOp, b, t.stream, stop);
-  });
+  hipError_t e;
+  if (is_mx_op(devOp)) {  // the MXFP8 all-reduce: its own kernel, over the two 16-bit float types
+    if (t.acc) return ncclInternalError;
+    e = kt == K_F16 ? direct_launch_mx<K_F16>(b, t.stream, stop) : direct_launch_mx<K_BF16>(b, t.stream, stop);
+    if (e == hipSuccess) t.comm->arMxfp8Launches += (uint64_t)nTasks;
+  } else {
+    e = by_kernel_type(kt, [&]<int K>() {
+      return t.acc ? direct_launch_bias<K>(devOp, bb, t.stream, stop)
+                   : direct_launch<K>(t.coll, devOp, b, t.stream, stop);
+    });
+  }
   if (e != hipSuccess) {
     VWARN("direct kernel launch failed: %s", hipGetErrorString(e));
     return ncclUnhandledCudaError;
@@ -635,6 +660,7 @@ static ncclResult_t launch_direct_reg_rooted(const Task& t, hipEvent_t stop) {
 static int choose_algo(const Task& t) {
   // the wide sums: the staged direct path, at level 2 the one-hop LL kernel where select_algo answers LL, the
   // wide ring from the comm's VCCL_SUM_FP32_RING_THRESHOLD up
+  if (is_mx_op(t.devOp)) return kAlgoDirect;  // the MXFP8 all-reduce: the staged direct launch at every size
   if (is_wide_op(t.devOp)) {
     const int a =
         sum_fp32_algo(sum_fp32_level(t.comm), policy_of(t.comm), t.coll, type_size(t.datatype), (int64_t)t.count);
@@ -652,6 +678,7 @@ static int reg_algo_or(const Task& t, int algo) {
   // level 1 of the wide sums keeps to the staged path: such calls do not negotiate
   // ... and a wide call with a bias at any level, whose bias must enter the staged kernel's binary32 fold
   if (is_wide_op(t.devOp) && (sum_fp32_level(t.comm) < 2 || t.acc)) return algo;
+  if (is_mx_op(t.devOp)) return algo;  // the MXFP8 all-reduce never negotiates
   return reg_task_eligible(t) ? kAlgoDirectReg : reg_rooted_task_eligible(t) ? kAlgoDirectRegRooted : algo;
 }
 // The paths whose kernels fold a bias themselves; behind every other one each bias call of the run gets its

@@ -316,6 +316,35 @@ int sum_fp32_algo(int level, const AlgoPolicy& p, int coll, int64_t eltSize, int
 uint64_t sum_fp32_ring_min(int64_t threshold, int level, bool simpleAllowed) {
   return threshold > 0 && level > 0 && simpleAllowed ? (uint64_t)threshold : 0;
 }
+uint64_t ar_mxfp8_min(int64_t threshold, bool inbox, bool directAllowed, bool anyNet, int nRanks) {
+  return threshold > 0 && sum_fp32_effective(true, inbox, directAllowed, anyNet, nRanks) ? (uint64_t)threshold : 0;
+}
+int ar_mxfp8_op(uint64_t effective, int coll, int devOp, ncclDataType_t datatype, size_t count, bool bias) {
+  if (effective == 0 || coll != kAllReduce || devOp != OP_SUM || bias) return devOp;
+  if (datatype != ncclFloat16 && datatype != ncclBfloat16) return devOp;
+  return (uint64_t)count * 2 >= effective ? kSumMxOp : devOp;
+}
+ncclResult_t direct_mx_plan(int nRanks, int64_t count, int64_t regionBytes, int minCTAs, int maxCTAs,
+                            int directMaxBlocks, int64_t blkForce, DirectMxPlanOut* out) {
+  const int64_t n = nRanks, regionTiles = regionBytes / kMxTileBytes;
+  if (n < 2 || n > kDirectMaxRanks || count < 1 || regionTiles < 1) return ncclInvalidArgument;
+  out->chunkElts = std::min<int64_t>(count, regionTiles * n * kMxTileElts);
+  const int64_t nChunks = (count + out->chunkElts - 1) / out->chunkElts;
+  if (nChunks > INT32_MAX) return ncclInvalidArgument;
+  out->nChunks = (int)nChunks;
+  out->shardTiles = ((out->chunkElts + kMxTileElts - 1) / kMxTileElts + n - 1) / n;
+  // blocks of >= 16 KiB of wire bytes (one byte per element, the scale lines aside), in whole tiles
+  const int64_t blk = direct_blk_elts(out->shardTiles * kMxTileElts, 1, minCTAs, maxCTAs, directMaxBlocks);
+  out->blkElts = (blk + kMxTileElts - 1) / kMxTileElts * kMxTileElts;
+  if (blkForce > 0) {
+    if (blkForce < out->blkElts || blkForce % kMxTileElts) return ncclInternalError;
+    out->blkElts = blkForce;
+  }
+  const int64_t blkTiles = out->blkElts / kMxTileElts;
+  out->nBlocks = (int)((out->shardTiles + blkTiles - 1) / blkTiles);
+  if (out->shardTiles > regionTiles || out->nBlocks < 1 || out->nBlocks > kDirectMaxBlocks) return ncclInternalError;
+  return ncclSuccess;
+}
 uint64_t ll_rooted_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks) {
   if (threshold <= 0 || llSlotBytes <= 0 || !llAllowed || anyNet || nRanks > kOrderMaxRanks) return 0;
   return (uint64_t)std::min(threshold, llSlotBytes);
@@ -359,10 +388,10 @@ GroupTask group_task_of(int coll, size_t count, ncclDataType_t datatype, int dev
   const CallSize sz = call_size(coll, count, datatype);
   const int key = (coll * 16 + (ag ? (int)OP_SUM : devOp)) * 32 + (bias ? kBiasKey : 0);
   return GroupTask{coll, sz.count, sz.eltSize, key + (ag ? (int)ncclInt8 : (int)datatype), key + kernelType,
-                   !ag && is_wide_sum_op(devOp), false, bias};
+                   !ag && (is_wide_sum_op(devOp) || devOp == kSumMxOp), false, bias, !ag && devOp == kSumMxOp};
 }
 void sum_fp32_group_rule(std::vector<GroupTask>& g, int level, const AlgoPolicy& pol) {
-  if (g.size() != 1 || !g[0].wide) return;
+  if (g.size() != 1 || !g[0].wide || g[0].mx) return;
   const int algo = sum_fp32_algo(level, pol, g[0].coll, g[0].eltSize, g[0].count);
   if (algo == kAlgoLL) g[0].wide = false;
   g[0].wideRing = algo == kAlgoRing && !g[0].bias;  // with a bias: the staged direct kernel

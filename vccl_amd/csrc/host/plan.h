@@ -128,6 +128,30 @@ int sum_fp32_algo(int level, const AlgoPolicy& p, int coll, int64_t eltSize, int
 // the wide sums are off (`level` 0: sum_fp32_effective said no, or nobody
 // asked) or where NCCL_ALGO / NCCL_PROTO exclude the SIMPLE ring.
 uint64_t sum_fp32_ring_min(int64_t threshold, int level, bool simpleAllowed);
+// The MXFP8 wire format for the direct f16 / bf16 all-reduce (VCCL_AR_MXFP8_THRESHOLD /
+// vcclCommSetArMxfp8Threshold).  The threshold as it takes effect: 0 (off) for a request <= 0 and
+// under sum_fp32_effective's conditions — no mapped inboxes, outside 2 .. kDirectMaxRanks ranks, a peer behind the
+// net proxy, Direct excluded by NCCL_ALGO.
+uint64_t ar_mxfp8_min(int64_t threshold, bool inbox, bool directAllowed, bool anyNet, int nRanks);
+// The device op a call runs with: kSumMxOp (device/dispatch.hpp OP_SUM_MXFP8) for an ncclAllReduce without a bias
+// whose devOp is OP_SUM (ncclSum alone: ncclAvg and PreMulSum resolve to other codes) over f16 / bf16 and whose
+// count * size reaches `effective` (> 0); devOp unchanged for every other call.  Asked BEFORE sum_fp32_op, so it
+// wins where both apply.  A call with this op takes the staged direct launch at every size (group_plan, launch.cc
+// choose_algo), never negotiates zero-copy, and is a bin of its own in a group through its devOp.
+constexpr int kSumMxOp = 7;  // tied to dispatch.hpp in launch.cc
+int ar_mxfp8_op(uint64_t effective, int coll, int devOp, ncclDataType_t datatype, size_t count, bool bias);
+// Launch geometry of one such call, in wire tiles of kMxTileElts elements (device/direct_mx.hpp reads it from
+// DirectWork): a region holds floor(regionBytes / kMxTileBytes) tiles; a chunk is at most that many tiles per
+// shard, n shards, so chunkElts is a multiple of kMxTileElts * n unless the call is one chunk; the shard of the
+// largest chunk (shardTiles tiles) is cut into nBlocks blocks of blkElts elements (whole tiles) by direct_blk_elts
+// on the shard's wire bytes.  blkForce > 0 imposes the block length (a fused batch's common one).
+// ncclInvalidArgument when a region holds no tile.
+struct DirectMxPlanOut {
+  int64_t chunkElts = 0, blkElts = 0, shardTiles = 0;
+  int nChunks = 0, nBlocks = 0;
+};
+ncclResult_t direct_mx_plan(int nRanks, int64_t count, int64_t regionBytes, int minCTAs, int maxCTAs,
+                            int directMaxBlocks, int64_t blkForce, DirectMxPlanOut* out);
 int proto_of_algo(int algo);
 
 struct GroupTask {
@@ -138,6 +162,7 @@ struct GroupTask {
   bool wide = false;       // a wide op code: the staged direct path whatever the aggregate's size
   bool wideRing = false;   // ... a group's only collective that sum_fp32_algo sends to the wide ring
   bool bias = false;       // ncclAllReduceWithBias: a bin (and a device function) of its own, never the wide ring
+  bool mx = false;         // the MXFP8 all-reduce (kSumMxOp): `wide` too, and sum_fp32_group_rule leaves it alone
 };
 // A call as the group planner takes it.  kernelType: dispatch.hpp
 // kernel_type_of (K_U8 for a byte copy), passed in so no kernel header is

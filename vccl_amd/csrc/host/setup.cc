@@ -400,7 +400,14 @@ ncclResult_t setup_local(int n, int minCTAs, int maxCTAs, CommSetup* s, SetupSiz
   // ... and their SIMPLE ring with binary32 partial sums from this many bytes
   // up: opt-in, untimed against the staged direct wide kernel
   s->sumFp32RingBytes = std::max<int64_t>(0, param_int("SUM_FP32_RING_THRESHOLD", 0));
+  // the MXFP8 wire format for ncclSum all-reduces over f16 / bf16 of at least this many bytes: opt-in, lossy by
+  // design; nothing is allocated for it (it moves through the direct inbox)
+  s->arMxfp8MinBytes = ar_mxfp8_of(*s, param_int("AR_MXFP8_THRESHOLD", 0), n, false, s->dRegionBytes > 0);
   return ncclSuccess;
+}
+
+size_t ar_mxfp8_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool inbox) {
+  return (size_t)ar_mxfp8_min(threshold, inbox, (s.algoAllowed & kAllowDirect) != 0, anyNet, nRanks);
 }
 
 size_t sum_fp32_ring_of(const CommSetup& s, int level) {
@@ -473,6 +480,7 @@ ncclResult_t setup_mesh(int rank, const std::vector<PeerId>& peers, CommSetup* s
     if (!s->p2pOff) s->p2pOff = kP2pOffNet;  // p2p FIFOs need every peer's memory mapped too
     s->p2pLLMaxBytes = 0;
     s->sumFp32 = 0;
+    s->arMxfp8MinBytes = 0;
     s->nChannels = std::max(1, std::min(s->nChannels, (int)param_int("NET_NCHANNELS", 8)));
     VINFO("rank %d: inter-node ring through the net proxy, %d channels", rank, s->nChannels);
   }

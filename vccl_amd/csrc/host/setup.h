@@ -92,6 +92,11 @@ struct CommSetup {
   // default 0 = off; not part of what vcclCommSetup reports either).  What
   // takes effect follows the level in force (sum_fp32_ring_of).
   int64_t sumFp32RingBytes = 0;
+  // Smallest ncclSum all-reduce over f16 / bf16 that travels in the MXFP8 wire format on the staged direct path
+  // (VCCL_AR_MXFP8_THRESHOLD / vcclCommSetArMxfp8Threshold, bytes, plan.h ar_mxfp8_min; default 0 = off: no plan
+  // and no result changes; not part of what vcclCommSetup reports either).  Calls also need the peers' inboxes
+  // mapped (launch.h ar_mxfp8_min_of).
+  size_t arMxfp8MinBytes = 0;
 };
 enum { kP2pOn = 0, kP2pOffEnv = 1, kP2pOffRanks = 2, kP2pOffNet = 3 };
 
@@ -130,6 +135,10 @@ int sum_fp32_of(const CommSetup& s, int level, int nRanks, bool anyNet, bool inb
 // The comm's wide-ring threshold as it takes effect at `level` (the level in
 // force, sum_fp32_of's or launch.h sum_fp32_level's): plan.h sum_fp32_ring_min.
 size_t sum_fp32_ring_of(const CommSetup& s, int level);
+
+// CommSetup::arMxfp8MinBytes for a VCCL_AR_MXFP8_THRESHOLD of `threshold`, likewise (setup_local;
+// vcclCommSetArMxfp8Threshold).
+size_t ar_mxfp8_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool inbox);
 
 // A comm's VCCL_REG_THRESHOLD of `threshold` as it takes effect (plan.h
 // reg_max; inbox: every peer's inbox and direct flags are mapped).

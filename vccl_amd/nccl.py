@@ -74,6 +74,7 @@ EXPORTED = [
     "vcclCommSetRegRootedThreshold",
     # fp32-accumulated sums for f16 / bf16 / fp8: the engine's entry point and the comm's live knob
     "vcclReduceCopyWide", "vcclCommSetSumFp32", "vcclCommSetSumFp32RingThreshold",
+    "vcclMxfp8Pack", "vcclMxfp8Unpack", "vcclCommSetArMxfp8Threshold", "vcclCommArMxfp8Stats",
     # out of scope, exported so libnccl-linked binaries load: WARN + ncclInvalidUsage
     "ncclGroupSimulateEnd",
     # memory / registration / scalable init (what a libnccl caller such as
@@ -173,6 +174,10 @@ def lib() -> ctypes.CDLL:
                                c_size, vp],
         "vcclCommSetSumFp32": [vp, c_int, ctypes.POINTER(c_int)],
         "vcclCommSetSumFp32RingThreshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
+        "vcclMxfp8Pack": [vp, c_int, c_size, vp, vp],
+        "vcclMxfp8Unpack": [vp, c_int, c_size, vp, vp],
+        "vcclCommSetArMxfp8Threshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
+        "vcclCommArMxfp8Stats": [vp, ctypes.POINTER(u64)],
         "vcclHostToDevRedOp": [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(u64)],
         "vcclKernelTypeOf": [c_int, c_int],
         "vcclBootstrapAllGather": [ctypes.POINTER(ncclUniqueId), c_int, c_int, vp, c_size],
@@ -819,6 +824,25 @@ def reduce_copy_wide(dev_op: int, dtype: int, red_arg: int, srcs, dsts, n_elts: 
           "vcclReduceCopyWide")
 
 
+MXFP8_TILE_ELTS, MXFP8_TILE_BYTES = 512, 528
+
+
+def mxfp8_wire_bytes(count: int) -> int:
+    """Bytes of the wire tiles holding `count` elements (whole 528-byte tiles of 512 elements)."""
+    return (count + MXFP8_TILE_ELTS - 1) // MXFP8_TILE_ELTS * MXFP8_TILE_BYTES
+
+
+def mxfp8_pack(src: int, dtype: int, count: int, wire: int, stream: int = 0) -> None:
+    """vcclMxfp8Pack on raw device pointers: `count` f16 / bf16 / f32 elements at `src` into MXFP8 wire tiles at
+    the 16-byte-aligned `wire` (mxfp8_wire_bytes(count) bytes)."""
+    check(lib().vcclMxfp8Pack(src, dtype, count, wire, stream), "vcclMxfp8Pack")
+
+
+def mxfp8_unpack(wire: int, dtype: int, count: int, dst: int, stream: int = 0) -> None:
+    """vcclMxfp8Unpack: the wire tiles at `wire` decoded into `count` elements of `dtype` at `dst`."""
+    check(lib().vcclMxfp8Unpack(wire, dtype, count, dst, stream), "vcclMxfp8Unpack")
+
+
 class Comm:
     """Owning wrapper over ncclComm_t."""
 
@@ -1108,6 +1132,21 @@ class Comm:
         check(lib().vcclCommSetSumFp32RingThreshold(self.handle, int(nbytes), ctypes.byref(eff)),
               "vcclCommSetSumFp32RingThreshold")
         return int(eff.value)
+
+    def set_ar_mxfp8_threshold(self, nbytes: int) -> int:
+        """vcclCommSetArMxfp8Threshold: later ncclSum all-reduces over f16 / bf16 of at least `nbytes` bytes travel
+        in the MXFP8 wire format on the staged direct path (VCCL_AR_MXFP8_THRESHOLD; 0: off; lossy by design).
+        Returns the threshold in force (0 where the staged direct path cannot run)."""
+        eff = ctypes.c_int64(0)
+        check(lib().vcclCommSetArMxfp8Threshold(self.handle, int(nbytes), ctypes.byref(eff)),
+              "vcclCommSetArMxfp8Threshold")
+        return int(eff.value)
+
+    def ar_mxfp8_stats(self) -> int:
+        """vcclCommArMxfp8Stats: the all-reduce calls this comm launched on the MXFP8 kernel."""
+        n = ctypes.c_uint64(0)
+        check(lib().vcclCommArMxfp8Stats(self.handle, ctypes.byref(n)), "vcclCommArMxfp8Stats")
+        return int(n.value)
 
     def debug_set_epochs(self, ll_epoch: int, direct_epoch: int):
         """vcclCommDebugSetEpochs: overwrite the LL / direct call epochs (wrap tests)."""
