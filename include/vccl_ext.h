@@ -388,6 +388,33 @@ ncclResult_t vcclCommSetSumFp32RingThreshold(ncclComm_t comm, int64_t bytes, int
  *                    launched on the MXFP8 kernel. */
 ncclResult_t vcclCommSetArMxfp8Threshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
 ncclResult_t vcclCommArMxfp8Stats(ncclComm_t comm, uint64_t* launches);
+/* The same wire format for the one-hop direct reduce-scatter and all-gather
+ * (opt-in: VCCL_RSAG_MXFP8_THRESHOLD=<bytes> at init, default 0 = off: nothing
+ * allocated, no plan and no result changed; independent of
+ * VCCL_AR_MXFP8_THRESHOLD, which means the all-reduce only; DESIGN.md section
+ * 4.20).  An ncclReduceScatter with ncclSum, or an ncclAllGather, over
+ * ncclFloat16 / ncclBfloat16 with count c > 0 per rank and nRanks * c * 2 of at
+ * least that many bytes moves 33/32 bytes per element and hop instead of 2:
+ *   reduce-scatter, rank p: out[j] = narrow(D(E(x_0[p c ..)))[j] + ... +
+ *                           D(E(x_{n-1}[p c ..)))[j]), every + a binary32 add in
+ *                           ascending rank order, one narrowing;
+ *   all-gather, every rank: out[r c + j] = narrow(D(E(x_r))[j]), r = its own
+ *                           rank included;
+ * E / D as vcclMxfp8Pack / vcclMxfp8Unpack, blocks of 32 cut by the index j
+ * within one rank's block.  LOSSY by design; the bits are a pure function of
+ * the inputs, in place or not, at any buffer alignment; a block holding a NaN
+ * or an infinity decodes to NaN; narrowing a decoded f16 value near 65504 may
+ * round it up to infinity.  Such a call takes the staged direct launch at every
+ * size (vcclCommCollAlgo says vcclAlgoDirect), never negotiates zero-copy, is a
+ * bin of its own in a group and wins over VCCL_SUM_FP32.  ncclAvg, PreMulSum,
+ * other ops and types and every other collective are unchanged.  Untimed over
+ * xGMI.
+ *   vcclCommSetRsAgMxfp8Threshold  the same for later calls; the rules and
+ *                    *effective of vcclCommSetArMxfp8Threshold.
+ *   vcclCommRsAgMxfp8Stats  the reduce-scatter and the all-gather calls this
+ *                    comm has launched on the two MXFP8 kernels. */
+ncclResult_t vcclCommSetRsAgMxfp8Threshold(ncclComm_t comm, int64_t bytes, int64_t* effective);
+ncclResult_t vcclCommRsAgMxfp8Stats(ncclComm_t comm, uint64_t* reduceScatters, uint64_t* allGathers);
 /* Zero-copy direct all-reduce / reduce-scatter / all-gather over
  * ncclCommRegister'ed buffers (opt-in: VCCL_REG_THRESHOLD=<bytes> at init,
  * default 0 = off).

@@ -23,6 +23,8 @@
 #include "vccl_device.h"
 #include "vccl_ext.h"
 
+#include "../vccl_amd/csrc/host/plan.h"  // the MXFP8 reduce-scatter / all-gather planner: internal, linked in directly
+
 static int g_fail = 0;
 #define EXPECT(c)                                                  \
   do {                                                             \
@@ -553,6 +555,42 @@ int main() {
       EXPECT(vcclCommSetArMxfp8Threshold(nullptr, bytes, &eff64) == ncclInvalidArgument && eff64 == 7);
     EXPECT(vcclCommSetArMxfp8Threshold(nullptr, 4096, nullptr) == ncclInvalidArgument);
     EXPECT(vcclCommArMxfp8Stats(nullptr, &launches) == ncclInvalidArgument && launches == 7);
+    // ... and the reduce-scatter / all-gather's switch and counters
+    uint64_t nRs = 7, nAg = 7;
+    for (int64_t bytes : {(int64_t)0, (int64_t)1, (int64_t)-1, INT64_MAX})
+      EXPECT(vcclCommSetRsAgMxfp8Threshold(nullptr, bytes, &eff64) == ncclInvalidArgument && eff64 == 7);
+    EXPECT(vcclCommSetRsAgMxfp8Threshold(nullptr, 4096, nullptr) == ncclInvalidArgument);
+    EXPECT(vcclCommRsAgMxfp8Stats(nullptr, &nRs, &nAg) == ncclInvalidArgument && nRs == 7 && nAg == 7);
+    EXPECT(vcclCommRsAgMxfp8Stats(nullptr, nullptr, nullptr) == ncclInvalidArgument);
+    // their eligibility rule and launch geometry (host/plan.h, linked in beside the library: they have no export)
+    // on random arguments, against the rule restated and the geometry's invariants
+    std::mt19937_64 mrng(20);
+    for (int trial = 0; trial < 20000; trial++) {
+      auto any = [&](std::initializer_list<int64_t> l) { return l.begin()[mrng() % l.size()]; };
+      const int coll = (int)(mrng() % 6), devOp = (int)any({0, 1, 2, 3, 5, 7, 8, 15}), dt = (int)(mrng() % 13);
+      const int n = (int)any({0, 1, 2, 3, 8, 9});
+      const size_t count = (size_t)any({0, 1, 7, 4096, 1000003});
+      const uint64_t eff = (uint64_t)any({0, 1, 15, 65536, 1ll << 40});
+      const int op = vccl::rsag_mxfp8_op(eff, coll, devOp, (ncclDataType_t)dt, count, n);
+      const bool ok = eff > 0 && count > 0 && n >= 1 && (dt == ncclFloat16 || dt == ncclBfloat16) &&
+                      (uint64_t)count * 2 * (uint64_t)n >= eff;
+      EXPECT(op == (ok && coll == 1 && devOp == 0 ? 7 : ok && coll == 2 && devOp == 15 ? 8 : devOp));
+      const int64_t cnt = any({0, 1, 511, 512, 513, 4099, 1000003, 1ll << 33}) + (int64_t)(mrng() % 3);
+      const int64_t region = any({0, 527, 528, 8448, 33024, 4 << 20}), force = any({0, 0, 512, 100, 1 << 20});
+      const int minC = (int)any({1, 4, 32}), maxC = (int)any({1, 32, 64}), cap = (int)any({0, 8, 64});
+      vccl::DirectMxPlanOut mp;
+      const ncclResult_t r = vccl::direct_mx_rsag_plan(cnt, region, minC, maxC, cap, force, &mp);
+      EXPECT(r == ncclSuccess || r == ncclInvalidArgument || r == ncclInternalError);
+      if (r != ncclSuccess) continue;
+      const int64_t regionTiles = region / 528, blkTiles = mp.blkElts / 512;
+      EXPECT(cnt >= 1 && regionTiles >= 1 && mp.chunkElts >= 1 && mp.chunkElts <= regionTiles * 512);
+      EXPECT((int64_t)mp.nChunks * mp.chunkElts >= cnt && (int64_t)(mp.nChunks - 1) * mp.chunkElts < cnt);
+      EXPECT(mp.nChunks == 1 || mp.chunkElts % 512 == 0);
+      EXPECT(mp.blkElts % 512 == 0 && blkTiles >= 1 && (force == 0 || mp.blkElts == force));
+      EXPECT(mp.shardTiles == (mp.chunkElts + 511) / 512 && mp.shardTiles * 528 <= region);
+      EXPECT(mp.nBlocks >= 1 && mp.nBlocks <= vccl::kDirectMaxBlocks && (int64_t)mp.nBlocks * blkTiles >= mp.shardTiles &&
+             (int64_t)(mp.nBlocks - 1) * blkTiles < mp.shardTiles);
+    }
     alignas(16) char buf[1056] = {};
     for (int dt = 0; dt < (int)ncclNumTypes; dt++) {
       const bool has = dt == ncclFloat16 || dt == ncclBfloat16 || dt == ncclFloat32;

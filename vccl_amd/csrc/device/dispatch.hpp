@@ -48,9 +48,14 @@ __host__ __device__ inline bool is_wide_op(int devOp) { return devOp == OP_SUM_W
 // The MXFP8 all-reduce (direct_mx.hpp): one more op code of the library's own, given at enqueue
 // to an eligible ncclSum all-reduce over f16 / bf16 and refused by kernel_type_of like the wide ones.
 enum : int { OP_SUM_MXFP8 = 7 };
-__host__ __device__ inline bool is_mx_op(int devOp) { return devOp == OP_SUM_MXFP8; }
+// ... and the reduce-scatter / all-gather in the format: an eligible ncclSum reduce-scatter carries
+// OP_SUM_MXFP8 too (the collective tells them apart), an eligible all-gather over f16 / bf16 OP_COPY_MXFP8 in place
+// of OP_COPY: its kernel decodes elements, so it is typed, unlike the byte copy.
+enum : int { OP_COPY_MXFP8 = 8 };
+__host__ __device__ inline bool is_mx_op(int devOp) { return devOp == OP_SUM_MXFP8 || devOp == OP_COPY_MXFP8; }
 __host__ __device__ inline int native_op_of(int devOp) {
   if (devOp == OP_SUM_WIDE || devOp == OP_SUM_MXFP8) return OP_SUM;
+  if (devOp == OP_COPY_MXFP8) return OP_COPY;
   return devOp == OP_PREMULSUM_WIDE ? (int)OP_PREMULSUM : devOp;
 }
 // The wide counterpart of (devOp, type), or -1: Sum / PreMulSum over f16, bf16, e4m3, e5m2.

@@ -52,6 +52,26 @@ hipError_t direct_launch_mx<VCCL_KT>(const DirectBatch& b, hipStream_t stream, h
   using T = typename KTypeOf<VCCL_KT>::T;
   return launch_k(k_direct_allreduce_mx<T>, dim3(b.w.nBlocks), dim3(kDirectThreads), stream, stop, b);
 }
+
+// the one-hop reduce-scatter and all-gather in the format
+template <typename T>
+__global__ __launch_bounds__(kDirectThreads) void k_direct_reducescatter_mx(DirectBatch b) {
+  direct_batch_mx_rsag<T, false>(b);
+}
+template <typename T>
+__global__ __launch_bounds__(kDirectThreads) void k_direct_allgather_mx(DirectBatch b) {
+  direct_batch_mx_rsag<T, true>(b);
+}
+template <>
+hipError_t direct_launch_mx_rs<VCCL_KT>(const DirectBatch& b, hipStream_t stream, hipEvent_t stop) {
+  using T = typename KTypeOf<VCCL_KT>::T;
+  return launch_k(k_direct_reducescatter_mx<T>, dim3(b.w.nBlocks), dim3(kDirectThreads), stream, stop, b);
+}
+template <>
+hipError_t direct_launch_mx_ag<VCCL_KT>(const DirectBatch& b, hipStream_t stream, hipEvent_t stop) {
+  using T = typename KTypeOf<VCCL_KT>::T;
+  return launch_k(k_direct_allgather_mx<T>, dim3(b.w.nBlocks), dim3(kDirectThreads), stream, stop, b);
+}
 #endif
 
 }  // namespace vccl

@@ -93,6 +93,13 @@ hipError_t direct_launch_bias(int devOp, const DirectBiasBatch& b, hipStream_t s
 // object of its own per kernel type (mx_kernels.hip).
 template <int K>
 hipError_t direct_launch_mx(const DirectBatch& b, hipStream_t stream, hipEvent_t stop);
+// The one-hop direct reduce-scatter (OP_SUM_MXFP8) and all-gather (OP_COPY_MXFP8) with the MXFP8 wire format
+// (direct_mx.hpp; K_F16 or K_BF16): the batch and the grid of direct_launch, the geometry in wire
+// tiles of one rank's block (host/plan.cc direct_mx_rsag_plan).  In the same objects as direct_launch_mx.
+template <int K>
+hipError_t direct_launch_mx_rs(const DirectBatch& b, hipStream_t stream, hipEvent_t stop);
+template <int K>
+hipError_t direct_launch_mx_ag(const DirectBatch& b, hipStream_t stream, hipEvent_t stop);
 
 // Zero-copy direct all-reduce / reduce-scatter / all-gather over registered
 // buffers, with the staged kernel of the same collective as its in-kernel

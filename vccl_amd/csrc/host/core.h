@@ -190,7 +190,9 @@ struct ncclComm : vccl::CommSetup {
   std::vector<CapOrder> caps;         // most recently used first
   uint64_t fusedLaunches = 0;         // group launches that carried > 1 collective
   uint64_t arMxfp8Launches = 0;       // all-reduce calls launched on the MXFP8 direct kernel (vcclCommArMxfp8Stats)
-  int ringWave = 0;                   // SIMPLE ring launches take the per-wave hand-off (VCCL_RING_WAVE)
+  uint64_t rsMxfp8Launches = 0;       // reduce-scatter / all-gather calls launched on the MXFP8 direct kernels
+  uint64_t agMxfp8Launches = 0;       // (vcclCommRsAgMxfp8Stats)
+  int ringWave = 0;                  // SIMPLE ring launches take the per-wave hand-off (VCCL_RING_WAVE)
   uint64_t waveLaunches = 0;          // ring launches that ran the per-wave kernel
   // ncclAllToAll(v) on this comm (vcclCommA2aStats / vcclCommA2aStatsEx): LL
   // and direct launches, and the sends + recvs (self block included) that went

@@ -115,7 +115,12 @@ static ncclResult_t enqueue_check_impl(int coll, const char* name, const void* s
     // VCCL_AR_MXFP8_THRESHOLD: the MXFP8 op code for an eligible all-reduce (it wins over the wide sum: it
     // accumulates in binary32 anyway); else VCCL_SUM_FP32: the wide op code, or unchanged
     t.devOp = ar_mxfp8_op(ar_mxfp8_min_of(comm), coll, t.devOp, dt, count, acc != nullptr);
+    // VCCL_RSAG_MXFP8_THRESHOLD: the same op code for an eligible reduce-scatter, by its own switch
+    t.devOp = rsag_mxfp8_op(rsag_mxfp8_min_of(comm), coll, t.devOp, dt, count, comm->nRanks);
     if (t.devOp != kSumMxOp) t.devOp = sum_fp32_op(sum_fp32_level(comm), coll, t.devOp, dt);
+  } else {
+    // ... and the all-gather's mark: its kernel is typed, unlike the byte copy (OP_COPY otherwise)
+    t.devOp = rsag_mxfp8_op(rsag_mxfp8_min_of(comm), coll, t.devOp, dt, count, comm->nRanks);
   }
   if (*(volatile int*)comm->errorFlag) {
     const ncclResult_t e = error_word_result(comm);

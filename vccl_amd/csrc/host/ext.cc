@@ -96,6 +96,12 @@ VCCL_EXPORT ncclResult_t vcclCommCollAlgo(ncclComm_t comm, int coll, size_t coun
     *algo = public_algo(kAlgoDirect);
     return ncclSuccess;
   }
+  // VCCL_RSAG_MXFP8_THRESHOLD: so does an eligible sum reduce-scatter or all-gather
+  if (is_mx_devop(rsag_mxfp8_op(rsag_mxfp8_min_of(comm), coll, coll == kAllGather ? (int)OP_COPY : (int)OP_SUM,
+                                datatype, count, comm->nRanks))) {
+    *algo = public_algo(kAlgoDirect);
+    return ncclSuccess;
+  }
   *algo = public_algo(wide ? sum_fp32_algo(level, pol, coll, type_size(datatype), (int64_t)count)
                            : select_algo(pol, coll, type_size(datatype), (int64_t)count));
   return ncclSuccess;
@@ -134,7 +140,7 @@ VCCL_EXPORT ncclResult_t vcclRingChunkOf(size_t count, ncclDataType_t datatype, 
 static ncclResult_t group_plan_export(int nCalls, const int* colls, const size_t* counts, const int* datatypes,
                                       const int* ops, int nRanks, int nChannels, const PlanGeometry& geo,
                                       const AlgoPolicy* pol, int* algos, int* order, int* planOf, int64_t* cbd,
-                                      int sumFp32 = 0, uint64_t arMxfp8Min = 0) {
+                                      int sumFp32 = 0, uint64_t arMxfp8Min = 0, uint64_t rsagMxfp8Min = 0) {
   if (nCalls < 1 || !colls || !counts || !datatypes || !ops || !order || !planOf || !cbd || nRanks < 1 ||
       nChannels < 1 || nChannels > kMaxChannels || geo.stepBytes < 4096 || geo.nThreads < 64 ||
       geo.ll128StepBytes < 1920 * 16 || geo.ll128Threads < 64)
@@ -150,7 +156,8 @@ static ncclResult_t group_plan_export(int nCalls, const int* colls, const size_t
     const int kt = kernel_type_of_call(c, devOp, dt);
     if (kt < 0) return ncclInvalidArgument;
     int op = ar_mxfp8_op(arMxfp8Min, c, devOp, dt, counts[i], false);  // as enqueue gives the op codes
-    if (op != kSumMxOp) op = sum_fp32_op(sumFp32, c, devOp, dt);
+    op = rsag_mxfp8_op(rsagMxfp8Min, c, c == kAllGather ? (int)OP_COPY : op, dt, counts[i], nRanks);
+    if (!is_mx_devop(op)) op = sum_fp32_op(sumFp32, c, devOp, dt);
     g.push_back(group_task_of(c, counts[i], dt, op, kt));
   }
   GroupPlanOut p;
@@ -203,7 +210,8 @@ VCCL_EXPORT ncclResult_t vcclCommGroupAlgos(ncclComm_t comm, int nCalls, const i
   const PlanGeometry geo{comm->stepBytes, comm->nThreads, ll128 ? comm->ll128StepBytes : kDefaultLL128.stepBytes,
                          ll128 ? comm->ll128Threads : kDefaultLL128.nThreads};
   return group_plan_export(nCalls, colls, counts, datatypes, ops, comm->nRanks, comm->nChannels, geo, &pol, algos,
-                           order.data(), planOf.data(), cbd.data(), sum_fp32_level(comm), ar_mxfp8_min_of(comm));
+                           order.data(), planOf.data(), cbd.data(), sum_fp32_level(comm), ar_mxfp8_min_of(comm),
+                           rsag_mxfp8_min_of(comm));
 }
 
 // A comm's VCCL_P2P_LL_THRESHOLD as it takes effect.
@@ -544,6 +552,25 @@ VCCL_EXPORT ncclResult_t vcclCommArMxfp8Stats(ncclComm_t comm, uint64_t* launche
   NCCLCHECK(comm_check(comm, "vcclCommArMxfp8Stats"));
   if (!launches) return ncclInvalidArgument;
   *launches = comm->arMxfp8Launches;
+  return ncclSuccess;
+}
+
+// The same format for later ncclSum reduce-scatters and all-gathers over f16 / bf16 whose bucket (nRanks * count * 2)
+// reaches `bytes` (as VCCL_RSAG_MXFP8_THRESHOLD at init; 0: off): every rank must call it alike, outside a group.
+VCCL_EXPORT ncclResult_t vcclCommSetRsAgMxfp8Threshold(ncclComm_t comm, int64_t bytes, int64_t* effective) {
+  NCCLCHECK(comm_check(comm, "vcclCommSetRsAgMxfp8Threshold"));
+  if (bytes < 0) return ncclInvalidArgument;
+  comm->rsagMxfp8MinBytes = ar_mxfp8_of(*comm, bytes, comm->nRanks, comm->dPeers == nullptr, comm->dPeers != nullptr);
+  if (effective) *effective = (int64_t)comm->rsagMxfp8MinBytes;
+  return ncclSuccess;
+}
+
+// Reduce-scatter / all-gather calls this comm launched on the MXFP8 direct kernels.
+VCCL_EXPORT ncclResult_t vcclCommRsAgMxfp8Stats(ncclComm_t comm, uint64_t* reduceScatters, uint64_t* allGathers) {
+  NCCLCHECK(comm_check(comm, "vcclCommRsAgMxfp8Stats"));
+  if (!reduceScatters || !allGathers) return ncclInvalidArgument;
+  *reduceScatters = comm->rsMxfp8Launches;
+  *allGathers = comm->agMxfp8Launches;
   return ncclSuccess;
 }
 

@@ -33,7 +33,8 @@ static_assert((int)OP_SUM == (int)vcclDevSum && (int)OP_PROD == (int)vcclDevProd
                   (int)OP_MINMAX == (int)vcclDevMinMax && (int)OP_PREMULSUM == (int)vcclDevPreMulSum &&
                   (int)OP_SUMPOSTDIV == (int)vcclDevSumPostDiv,
               "OP_* and vcclDevRedOp_t are one enumeration");
-static_assert((int)OP_SUM_MXFP8 == kSumMxOp, "plan.h names the MXFP8 op code without the kernel headers");
+static_assert((int)OP_SUM_MXFP8 == kSumMxOp && (int)OP_COPY_MXFP8 == kCopyMxOp && (int)OP_COPY == kCopyOp,
+              "plan.h names the MXFP8 op codes without the kernel headers");
 static_assert((int)OP_SUM_WIDE == kSumWideOp && (int)OP_PREMULSUM_WIDE == kPreMulSumWideOp,
               "the wide op codes of plan.h are dispatch.hpp's");
 
@@ -449,10 +450,18 @@ static ncclResult_t direct_work_of(const Task& t, DirectWork* out, int* ktOut, i
     if (t.coll == kReduce) w.cbd = rs_cbd(t, kProtoSimple);
   } else if (is_mx_op(t.devOp)) {
     // the MXFP8 all-reduce: whole wire tiles (plan.cc direct_mx_plan); it folds in rank order, no partition
-    if (t.coll != kAllReduce || (t.datatype != ncclFloat16 && t.datatype != ncclBfloat16)) return ncclInternalError;
+    // ... the reduce-scatter (OP_SUM_MXFP8) and the all-gather (OP_COPY_MXFP8) in the format: wire tiles of one
+    // rank's block (direct_mx_rsag_plan), the count in elements for the all-gather too (its kernel is typed)
+    const bool rsag = t.coll == kReduceScatter || t.coll == kAllGather;
+    if ((t.coll != kAllReduce && !rsag) || (t.datatype != ncclFloat16 && t.datatype != ncclBfloat16) ||
+        (t.devOp == OP_COPY_MXFP8) != (t.coll == kAllGather))
+      return ncclInternalError;
     DirectMxPlanOut mp;
-    if (direct_mx_plan(n, count, comm->dRegionBytes, comm->minCTAs, comm->maxCTAs, comm->directMaxBlocks, blkForce,
-                       &mp) != ncclSuccess)
+    if (rsag) w.count = (uint64_t)t.count;
+    if ((rsag ? direct_mx_rsag_plan((int64_t)t.count, comm->dRegionBytes, comm->minCTAs, comm->maxCTAs,
+                                    comm->directMaxBlocks, blkForce, &mp)
+              : direct_mx_plan(n, count, comm->dRegionBytes, comm->minCTAs, comm->maxCTAs, comm->directMaxBlocks,
+                               blkForce, &mp)) != ncclSuccess)
       return ncclInternalError;
     w.chunkElts = mp.chunkElts;
     w.nChunks = mp.nChunks;
@@ -536,10 +545,18 @@ static ncclResult_t launch_direct(const Task* ts, int nTasks, hipEvent_t stop) {
   b.nParts = nTasks;
   if (t.acc && t.coll != kAllReduce) return ncclInternalError;
   hipError_t e;
-  if (is_mx_op(devOp)) {  // the MXFP8 all-reduce: its own kernel, over the two 16-bit float types
+  if (is_mx_op(devOp)) {  // the MXFP8 kernels, one per collective, over the two 16-bit float types
     if (t.acc) return ncclInternalError;
-    e = kt == K_F16 ? direct_launch_mx<K_F16>(b, t.stream, stop) : direct_launch_mx<K_BF16>(b, t.stream, stop);
-    if (e == hipSuccess) t.comm->arMxfp8Launches += (uint64_t)nTasks;
+    if (t.coll == kReduceScatter) {
+      e = kt == K_F16 ? direct_launch_mx_rs<K_F16>(b, t.stream, stop) : direct_launch_mx_rs<K_BF16>(b, t.stream, stop);
+      if (e == hipSuccess) t.comm->rsMxfp8Launches += (uint64_t)nTasks;
+    } else if (t.coll == kAllGather) {
+      e = kt == K_F16 ? direct_launch_mx_ag<K_F16>(b, t.stream, stop) : direct_launch_mx_ag<K_BF16>(b, t.stream, stop);
+      if (e == hipSuccess) t.comm->agMxfp8Launches += (uint64_t)nTasks;
+    } else {
+      e = kt == K_F16 ? direct_launch_mx<K_F16>(b, t.stream, stop) : direct_launch_mx<K_BF16>(b, t.stream, stop);
+      if (e == hipSuccess) t.comm->arMxfp8Launches += (uint64_t)nTasks;
+    }
   } else {
     e = by_kernel_type(kt, [&]<int K>() {
       return t.acc ? direct_launch_bias<K>(devOp, bb, t.stream, stop)
@@ -660,7 +677,7 @@ static ncclResult_t launch_direct_reg_rooted(const Task& t, hipEvent_t stop) {
 static int choose_algo(const Task& t) {
   // the wide sums: the staged direct path, at level 2 the one-hop LL kernel where select_algo answers LL, the
   // wide ring from the comm's VCCL_SUM_FP32_RING_THRESHOLD up
-  if (is_mx_op(t.devOp)) return kAlgoDirect;  // the MXFP8 all-reduce: the staged direct launch at every size
+  if (is_mx_op(t.devOp)) return kAlgoDirect;  // an MXFP8 call: the staged direct launch at every size
   if (is_wide_op(t.devOp)) {
     const int a =
         sum_fp32_algo(sum_fp32_level(t.comm), policy_of(t.comm), t.coll, type_size(t.datatype), (int64_t)t.count);
@@ -678,7 +695,7 @@ static int reg_algo_or(const Task& t, int algo) {
   // level 1 of the wide sums keeps to the staged path: such calls do not negotiate
   // ... and a wide call with a bias at any level, whose bias must enter the staged kernel's binary32 fold
   if (is_wide_op(t.devOp) && (sum_fp32_level(t.comm) < 2 || t.acc)) return algo;
-  if (is_mx_op(t.devOp)) return algo;  // the MXFP8 all-reduce never negotiates
+  if (is_mx_op(t.devOp)) return algo;  // an MXFP8 call never negotiates
   return reg_task_eligible(t) ? kAlgoDirectReg : reg_rooted_task_eligible(t) ? kAlgoDirectRegRooted : algo;
 }
 // The paths whose kernels fold a bias themselves; behind every other one each bias call of the run gets its
@@ -741,7 +758,7 @@ ncclResult_t launch_task(const Task& t) {
 // Same comm, collective, kernel type and op (the caller compares the paths).
 static bool fusable(const Task& a, const Task& b) {
   if (a.comm != b.comm || a.coll != b.coll || (a.acc != nullptr) != (b.acc != nullptr)) return false;
-  if (is_copy_coll(a.coll)) return true;  // byte copies: any type
+  if (is_copy_coll(a.coll) && !is_mx_op(a.devOp) && !is_mx_op(b.devOp)) return true;  // byte copies: any type
   return a.datatype == b.datatype && a.devOp == b.devOp && a.arg == b.arg && a.argPtr == b.argPtr;
 }
 static int max_parts(int algo) {

@@ -68,6 +68,10 @@ inline bool sum_fp32_on(const ncclComm* c) { return c->sumFp32 != 0 && c->dPeers
 inline int sum_fp32_level(const ncclComm* c) { return sum_fp32_on(c) ? c->sumFp32 : 0; }
 // VCCL_AR_MXFP8_THRESHOLD / vcclCommSetArMxfp8Threshold as the comm's calls take it (0: off).
 inline uint64_t ar_mxfp8_min_of(const ncclComm* c) { return c->dPeers != nullptr ? (uint64_t)c->arMxfp8MinBytes : 0; }
+// VCCL_RSAG_MXFP8_THRESHOLD / vcclCommSetRsAgMxfp8Threshold, likewise.
+inline uint64_t rsag_mxfp8_min_of(const ncclComm* c) {
+  return c->dPeers != nullptr ? (uint64_t)c->rsagMxfp8MinBytes : 0;
+}
 // The one place that reads a comm into the planner's thresholds.
 AlgoPolicy policy_of(const ncclComm* c);
 // The kernel element type of a call (K_U8 for the byte copies), -1: no kernel.

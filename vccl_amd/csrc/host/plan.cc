@@ -345,6 +345,33 @@ ncclResult_t direct_mx_plan(int nRanks, int64_t count, int64_t regionBytes, int 
   if (out->shardTiles > regionTiles || out->nBlocks < 1 || out->nBlocks > kDirectMaxBlocks) return ncclInternalError;
   return ncclSuccess;
 }
+int rsag_mxfp8_op(uint64_t effective, int coll, int devOp, ncclDataType_t datatype, size_t count, int nRanks) {
+  if (effective == 0 || count == 0 || nRanks < 1) return devOp;
+  if (datatype != ncclFloat16 && datatype != ncclBfloat16) return devOp;
+  if ((uint64_t)count * 2 * (uint64_t)nRanks < effective) return devOp;
+  if (coll == kReduceScatter && devOp == OP_SUM) return kSumMxOp;
+  return coll == kAllGather && devOp == kCopyOp ? kCopyMxOp : devOp;
+}
+ncclResult_t direct_mx_rsag_plan(int64_t count, int64_t regionBytes, int minCTAs, int maxCTAs, int directMaxBlocks,
+                                 int64_t blkForce, DirectMxPlanOut* out) {
+  const int64_t regionTiles = regionBytes / kMxTileBytes;
+  if (count < 1 || regionTiles < 1) return ncclInvalidArgument;
+  out->chunkElts = std::min<int64_t>(count, regionTiles * kMxTileElts);
+  const int64_t nChunks = (count + out->chunkElts - 1) / out->chunkElts;
+  if (nChunks > INT32_MAX) return ncclInvalidArgument;
+  out->nChunks = (int)nChunks;
+  out->shardTiles = (out->chunkElts + kMxTileElts - 1) / kMxTileElts;  // the largest chunk's tiles
+  const int64_t blk = direct_blk_elts(out->shardTiles * kMxTileElts, 1, minCTAs, maxCTAs, directMaxBlocks);
+  out->blkElts = (blk + kMxTileElts - 1) / kMxTileElts * kMxTileElts;
+  if (blkForce > 0) {
+    if (blkForce < out->blkElts || blkForce % kMxTileElts) return ncclInternalError;
+    out->blkElts = blkForce;
+  }
+  const int64_t blkTiles = out->blkElts / kMxTileElts;
+  out->nBlocks = (int)((out->shardTiles + blkTiles - 1) / blkTiles);
+  if (out->shardTiles > regionTiles || out->nBlocks < 1 || out->nBlocks > kDirectMaxBlocks) return ncclInternalError;
+  return ncclSuccess;
+}
 uint64_t ll_rooted_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks) {
   if (threshold <= 0 || llSlotBytes <= 0 || !llAllowed || anyNet || nRanks > kOrderMaxRanks) return 0;
   return (uint64_t)std::min(threshold, llSlotBytes);
@@ -384,11 +411,12 @@ int proto_of_algo(int algo) {
 // oracle/vccl_sched.py (plan_schedule).
 // group_task_of: all-gather / broadcast are int8 copies (enqueue.cc:2400-2404), keyed as such.
 GroupTask group_task_of(int coll, size_t count, ncclDataType_t datatype, int devOp, int kernelType, bool bias) {
-  const bool ag = is_copy_coll(coll);
+  // ... except the MXFP8 all-gather (kCopyMxOp): a typed kernel, keyed by its op and type
+  const bool ag = is_copy_coll(coll) && devOp != kCopyMxOp;
   const CallSize sz = call_size(coll, count, datatype);
   const int key = (coll * 16 + (ag ? (int)OP_SUM : devOp)) * 32 + (bias ? kBiasKey : 0);
   return GroupTask{coll, sz.count, sz.eltSize, key + (ag ? (int)ncclInt8 : (int)datatype), key + kernelType,
-                   !ag && (is_wide_sum_op(devOp) || devOp == kSumMxOp), false, bias, !ag && devOp == kSumMxOp};
+                   !ag && (is_wide_sum_op(devOp) || is_mx_devop(devOp)), false, bias, !ag && is_mx_devop(devOp)};
 }
 void sum_fp32_group_rule(std::vector<GroupTask>& g, int level, const AlgoPolicy& pol) {
   if (g.size() != 1 || !g[0].wide || g[0].mx) return;

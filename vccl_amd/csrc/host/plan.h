@@ -152,6 +152,24 @@ struct DirectMxPlanOut {
 };
 ncclResult_t direct_mx_plan(int nRanks, int64_t count, int64_t regionBytes, int minCTAs, int maxCTAs,
                             int directMaxBlocks, int64_t blkForce, DirectMxPlanOut* out);
+// The same format for the one-hop direct reduce-scatter and all-gather (VCCL_RSAG_MXFP8_THRESHOLD /
+// vcclCommSetRsAgMxfp8Threshold); the threshold takes effect as ar_mxfp8_min says, on its own
+// variable.  The device op a call runs with: kSumMxOp for an ncclReduceScatter whose devOp is OP_SUM, kCopyMxOp
+// (device/dispatch.hpp OP_COPY_MXFP8) for an ncclAllGather (devOp OP_COPY), over f16 / bf16 with count > 0 (the
+// per-rank count) and nRanks * count * 2 >= `effective` (> 0: the whole bucket, reg_eligible's size convention);
+// devOp unchanged for every other call.  Asked BEFORE sum_fp32_op; such a call takes the staged direct launch at
+// every size, never negotiates zero-copy, and is a bin of its own in a group (group_task_of keys the all-gather
+// by this op and its type instead of the byte copy's).
+constexpr int kCopyMxOp = 8, kCopyOp = 15;  // OP_COPY_MXFP8 / OP_COPY, tied to dispatch.hpp in launch.cc
+inline bool is_mx_devop(int devOp) { return devOp == kSumMxOp || devOp == kCopyMxOp; }
+int rsag_mxfp8_op(uint64_t effective, int coll, int devOp, ncclDataType_t datatype, size_t count, int nRanks);
+// Launch geometry of one such call, in wire tiles (device/direct_mx.hpp): a region holds floor(regionBytes /
+// kMxTileBytes) tiles; a chunk is a range of ONE rank's block of `count` elements, chunkElts = min(count,
+// regionTiles * kMxTileElts), so every chunk but the last is whole tiles; the largest chunk (shardTiles tiles) is
+// cut into nBlocks blocks of blkElts elements (whole tiles) by direct_blk_elts on its wire bytes.  blkForce as in
+// direct_mx_plan.  ncclInvalidArgument when a region holds no tile.
+ncclResult_t direct_mx_rsag_plan(int64_t count, int64_t regionBytes, int minCTAs, int maxCTAs, int directMaxBlocks,
+                                 int64_t blkForce, DirectMxPlanOut* out);
 int proto_of_algo(int algo);
 
 struct GroupTask {
@@ -162,7 +180,7 @@ struct GroupTask {
   bool wide = false;       // a wide op code: the staged direct path whatever the aggregate's size
   bool wideRing = false;   // ... a group's only collective that sum_fp32_algo sends to the wide ring
   bool bias = false;       // ncclAllReduceWithBias: a bin (and a device function) of its own, never the wide ring
-  bool mx = false;         // the MXFP8 all-reduce (kSumMxOp): `wide` too, and sum_fp32_group_rule leaves it alone
+  bool mx = false;         // an MXFP8 call (kSumMxOp / kCopyMxOp): `wide` too, and sum_fp32_group_rule leaves it alone
 };
 // A call as the group planner takes it.  kernelType: dispatch.hpp
 // kernel_type_of (K_U8 for a byte copy), passed in so no kernel header is

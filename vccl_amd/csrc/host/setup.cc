@@ -403,6 +403,8 @@ ncclResult_t setup_local(int n, int minCTAs, int maxCTAs, CommSetup* s, SetupSiz
   // the MXFP8 wire format for ncclSum all-reduces over f16 / bf16 of at least this many bytes: opt-in, lossy by
   // design; nothing is allocated for it (it moves through the direct inbox)
   s->arMxfp8MinBytes = ar_mxfp8_of(*s, param_int("AR_MXFP8_THRESHOLD", 0), n, false, s->dRegionBytes > 0);
+  // ... and, on a switch of its own, for ncclSum reduce-scatters and all-gathers over f16 / bf16
+  s->rsagMxfp8MinBytes = ar_mxfp8_of(*s, param_int("RSAG_MXFP8_THRESHOLD", 0), n, false, s->dRegionBytes > 0);
   return ncclSuccess;
 }
 
@@ -481,6 +483,7 @@ ncclResult_t setup_mesh(int rank, const std::vector<PeerId>& peers, CommSetup* s
     s->p2pLLMaxBytes = 0;
     s->sumFp32 = 0;
     s->arMxfp8MinBytes = 0;
+    s->rsagMxfp8MinBytes = 0;
     s->nChannels = std::max(1, std::min(s->nChannels, (int)param_int("NET_NCHANNELS", 8)));
     VINFO("rank %d: inter-node ring through the net proxy, %d channels", rank, s->nChannels);
   }

@@ -97,6 +97,10 @@ struct CommSetup {
   // and no result changes; not part of what vcclCommSetup reports either).  Calls also need the peers' inboxes
   // mapped (launch.h ar_mxfp8_min_of).
   size_t arMxfp8MinBytes = 0;
+  // ... and the smallest ncclSum reduce-scatter / all-gather over f16 / bf16 (nRanks * count * 2 bytes) that does
+  // (VCCL_RSAG_MXFP8_THRESHOLD / vcclCommSetRsAgMxfp8Threshold, plan.h rsag_mxfp8_op; default 0 =
+  // off; independent of the all-reduce's switch; not part of what vcclCommSetup reports).
+  size_t rsagMxfp8MinBytes = 0;
 };
 enum { kP2pOn = 0, kP2pOffEnv = 1, kP2pOffRanks = 2, kP2pOffNet = 3 };
 
@@ -137,7 +141,7 @@ int sum_fp32_of(const CommSetup& s, int level, int nRanks, bool anyNet, bool inb
 size_t sum_fp32_ring_of(const CommSetup& s, int level);
 
 // CommSetup::arMxfp8MinBytes for a VCCL_AR_MXFP8_THRESHOLD of `threshold`, likewise (setup_local;
-// vcclCommSetArMxfp8Threshold).
+// vcclCommSetArMxfp8Threshold); CommSetup::rsagMxfp8MinBytes for a VCCL_RSAG_MXFP8_THRESHOLD by the same rule.
 size_t ar_mxfp8_of(const CommSetup& s, int64_t threshold, int nRanks, bool anyNet, bool inbox);
 
 // A comm's VCCL_REG_THRESHOLD of `threshold` as it takes effect (plan.h

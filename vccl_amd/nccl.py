@@ -75,6 +75,7 @@ EXPORTED = [
     # fp32-accumulated sums for f16 / bf16 / fp8: the engine's entry point and the comm's live knob
     "vcclReduceCopyWide", "vcclCommSetSumFp32", "vcclCommSetSumFp32RingThreshold",
     "vcclMxfp8Pack", "vcclMxfp8Unpack", "vcclCommSetArMxfp8Threshold", "vcclCommArMxfp8Stats",
+    "vcclCommSetRsAgMxfp8Threshold", "vcclCommRsAgMxfp8Stats",
     # out of scope, exported so libnccl-linked binaries load: WARN + ncclInvalidUsage
     "ncclGroupSimulateEnd",
     # memory / registration / scalable init (what a libnccl caller such as
@@ -178,6 +179,8 @@ def lib() -> ctypes.CDLL:
         "vcclMxfp8Unpack": [vp, c_int, c_size, vp, vp],
         "vcclCommSetArMxfp8Threshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
         "vcclCommArMxfp8Stats": [vp, ctypes.POINTER(u64)],
+        "vcclCommSetRsAgMxfp8Threshold": [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
+        "vcclCommRsAgMxfp8Stats": [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)],
         "vcclHostToDevRedOp": [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(u64)],
         "vcclKernelTypeOf": [c_int, c_int],
         "vcclBootstrapAllGather": [ctypes.POINTER(ncclUniqueId), c_int, c_int, vp, c_size],
@@ -1147,6 +1150,21 @@ class Comm:
         n = ctypes.c_uint64(0)
         check(lib().vcclCommArMxfp8Stats(self.handle, ctypes.byref(n)), "vcclCommArMxfp8Stats")
         return int(n.value)
+
+    def set_rsag_mxfp8_threshold(self, nbytes: int) -> int:
+        """vcclCommSetRsAgMxfp8Threshold: later ncclSum reduce-scatters and all-gathers over f16 / bf16 whose bucket
+        (nranks * count * 2) reaches `nbytes` bytes travel in the MXFP8 wire format on the staged direct path
+        (VCCL_RSAG_MXFP8_THRESHOLD; 0: off; lossy by design).  Returns the threshold in force."""
+        eff = ctypes.c_int64(0)
+        check(lib().vcclCommSetRsAgMxfp8Threshold(self.handle, int(nbytes), ctypes.byref(eff)),
+              "vcclCommSetRsAgMxfp8Threshold")
+        return int(eff.value)
+
+    def rsag_mxfp8_stats(self):
+        """vcclCommRsAgMxfp8Stats: (reduce-scatter, all-gather) calls this comm launched on the MXFP8 kernels."""
+        rs, ag = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(lib().vcclCommRsAgMxfp8Stats(self.handle, ctypes.byref(rs), ctypes.byref(ag)), "vcclCommRsAgMxfp8Stats")
+        return int(rs.value), int(ag.value)
 
     def debug_set_epochs(self, ll_epoch: int, direct_epoch: int):
         """vcclCommDebugSetEpochs: overwrite the LL / direct call epochs (wrap tests)."""
