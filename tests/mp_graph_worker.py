@@ -274,7 +274,7 @@ def main():
     g = torch.cuda.CUDAGraph()
     # An eager call on ANOTHER stream right before the capture: the capture
     # must not wait on (or overwrite) the comm's eager ordering event, which
-    # was recorded outside it (launch.cc stream_order / stream_mark).
+    # was recorded outside it (order.cc stream_order / stream_mark).
     eager_x = torch.arange(4099, device="cuda", dtype=torch.float32) + rank
     eager_y = torch.empty_like(eager_x)
     comm.all_reduce(eager_x.data_ptr(), eager_y.data_ptr(), 4099, nccl.ncclFloat32, nccl.ncclSum,

@@ -44,7 +44,7 @@ def rs_bound(xs, p, c, dt):
 
 
 def three_chunk_count(n):
-    """A per-rank count that moves through the inbox in three chunks (host/plan.cc direct_mx_rsag_plan)."""
+    """A per-rank count that moves through the inbox in three chunks (host/plan.cc direct_mx_plan, one shard)."""
     region = (max(int(os.environ["VCCL_DIRECT_CHUNK_BYTES"]), 64 << 10) + n - 1) // n // 256 * 256 + 256
     return 2 * (region // 528 * 512) + 1031
 

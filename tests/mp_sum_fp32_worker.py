@@ -32,7 +32,7 @@ def native_fold(dt, xs, scale=1.0):  # the inputs folded in the given order, one
 
 
 def three_chunk_count(coll, n, esz):
-    """A count that moves through the inbox in three chunks (host/setup.cc's region, host/launch.cc direct_work_of)."""
+    """A count that moves through the inbox in three chunks (host/setup.cc's region, host/plan.cc direct_plan)."""
     region = (max(int(os.environ["VCCL_DIRECT_CHUNK_BYTES"]), 64 << 10) + n - 1) // n // 256 * 256 + 256
     relts, align = (region - 16) // esz, 16 // esz
     return 2 * (relts * n // (n * align) * (n * align) if coll == AR else relts // align * align) + 1031

@@ -20,8 +20,9 @@ MIN_BLK_BYTES = 16 << 10
 
 
 def _geometry(count, n, esz, max_blocks, chunk_bytes):
-    """host/launch.cc launch_direct: chunk, block length (fixed per launch),
-    block count, inbox region bytes."""
+    """A restatement, not attached to the library, of the all-reduce's staged
+    geometry (host/plan.cc direct_plan, which also applies the CTA bounds):
+    chunk, block length (fixed per launch), block count, inbox region bytes."""
     align = max(1, 16 // esz)
     region = (chunk_bytes + n - 1) // n // 256 * 256 + 256
     chunk = _ring.direct_chunk_elts(count, n, esz, chunk_bytes)

@@ -23,7 +23,7 @@
 #include "vccl_device.h"
 #include "vccl_ext.h"
 
-#include "../vccl_amd/csrc/host/plan.h"  // the MXFP8 reduce-scatter / all-gather planner: internal, linked in directly
+#include "../vccl_amd/csrc/host/plan.h"  // the direct planners (direct_plan, direct_mx_plan): internal, linked in directly
 
 static int g_fail = 0;
 #define EXPECT(c)                                                  \
@@ -452,7 +452,7 @@ int main() {
   // the direct all-to-all limit (vcclDirectA2aMax) and one call's three-way
   // split (vcclDirectA2aPlan) on random byte matrices, limits, bounds and
   // invalid arguments
-  long directA2a = 0;
+  long directA2a = 0, mxPlans = 0, directPlans = 0, directPlansOk = 0;
   for (int trial = 0; trial < 20000; trial++) {
     if (rng() % 4 == 0) setenv("VCCL_DIRECT_A2A_THRESHOLD", junk[rng() % 11], 1);
     else if (rng() % 2) setenv("VCCL_DIRECT_A2A_THRESHOLD", "98304", 1);
@@ -578,19 +578,83 @@ int main() {
       const int64_t cnt = any({0, 1, 511, 512, 513, 4099, 1000003, 1ll << 33}) + (int64_t)(mrng() % 3);
       const int64_t region = any({0, 527, 528, 8448, 33024, 4 << 20}), force = any({0, 0, 512, 100, 1 << 20});
       const int minC = (int)any({1, 4, 32}), maxC = (int)any({1, 32, 64}), cap = (int)any({0, 8, 64});
-      vccl::DirectMxPlanOut mp;
-      const ncclResult_t r = vccl::direct_mx_rsag_plan(cnt, region, minC, maxC, cap, force, &mp);
+      // one planner, two forms: one shard (a rank's block of the reduce-scatter / all-gather), n shards (the all-reduce)
+      const int64_t sh = any({1, 1, 2, 3, 8});
+      vccl::DirectPlanOut mp;
+      const ncclResult_t r = vccl::direct_mx_plan((int)sh, cnt, region, minC, maxC, cap, force, &mp);
       EXPECT(r == ncclSuccess || r == ncclInvalidArgument || r == ncclInternalError);
       if (r != ncclSuccess) continue;
-      const int64_t regionTiles = region / 528, blkTiles = mp.blkElts / 512;
-      EXPECT(cnt >= 1 && regionTiles >= 1 && mp.chunkElts >= 1 && mp.chunkElts <= regionTiles * 512);
+      const int64_t regionTiles = region / 528, blkTiles = mp.blkElts / 512, shardTiles = mp.shardElts / 512;
+      EXPECT(cnt >= 1 && regionTiles >= 1 && mp.chunkElts >= 1 && mp.chunkElts <= regionTiles * 512 * sh);
       EXPECT((int64_t)mp.nChunks * mp.chunkElts >= cnt && (int64_t)(mp.nChunks - 1) * mp.chunkElts < cnt);
-      EXPECT(mp.nChunks == 1 || mp.chunkElts % 512 == 0);
+      EXPECT(mp.nChunks == 1 || mp.chunkElts % (512 * sh) == 0);
       EXPECT(mp.blkElts % 512 == 0 && blkTiles >= 1 && (force == 0 || mp.blkElts == force));
-      EXPECT(mp.shardTiles == (mp.chunkElts + 511) / 512 && mp.shardTiles * 528 <= region);
-      EXPECT(mp.nBlocks >= 1 && mp.nBlocks <= vccl::kDirectMaxBlocks && (int64_t)mp.nBlocks * blkTiles >= mp.shardTiles &&
-             (int64_t)(mp.nBlocks - 1) * blkTiles < mp.shardTiles);
+      EXPECT(mp.shardElts % 512 == 0 && shardTiles == ((mp.chunkElts + 511) / 512 + sh - 1) / sh && shardTiles * 528 <= region);
+      EXPECT(mp.nBlocks >= 1 && mp.nBlocks <= vccl::kDirectMaxBlocks && (int64_t)mp.nBlocks * blkTiles >= shardTiles &&
+             (int64_t)(mp.nBlocks - 1) * blkTiles < shardTiles);
+      mxPlans++;
     }
+    // the staged direct geometry (plan.h direct_plan, all five collectives) on random arguments, against the
+    // formulas restated — the all-reduce rounds the region's elements to n x 16 bytes at once, the reduce-scatter /
+    // all-gather to 16 bytes, the rooted pair to 16 bytes before the shard count — and the geometry's invariants
+    for (int trial = 0; trial < 24000; trial++) {
+      auto any = [&](std::initializer_list<int64_t> l) { return l.begin()[mrng() % l.size()]; };
+      const int coll = (int)(mrng() % 5), n = (int)any({2, 3, 5, 8, 9});
+      const int64_t esz = any({1, 2, 4, 8}), align = std::max<int64_t>(1, 16 / esz);
+      const int64_t cnt = std::max<int64_t>(1, any({1, 5, 4099, 786433, 1 << 28, 1 << 20}) + (int64_t)(mrng() % 5) - 2);
+      const int64_t region = any({16, 32, 272, 33024, (2 << 20) + 256, (2 << 20) + 256, 4 << 20, 64 << 20});
+      const int minC = (int)any({1, 4, 32}), maxC = (int)any({1, 32, 128});
+      const int cap = (int)any({64, 8, 16, 64});  // as a comm stores it: VCCL_DIRECT_MAX_BLOCKS' default, or lowered
+      // the expected geometry
+      const int64_t regionElts = (region - 16) / esz;
+      const int64_t nSh = coll == 0 || coll == 4 ? n : coll == 3 ? n - 1 : 1;
+      const int64_t chunkMax = coll == 0   ? regionElts * n / (n * align) * (n * align)
+                               : coll <= 2 ? regionElts / align * align
+                                           : regionElts / align * align * nSh;
+      const int64_t chunk = std::min(cnt, chunkMax);
+      const int64_t shard = coll == 1 || coll == 2 ? chunk : ((chunk + nSh - 1) / nSh + align - 1) / align * align;
+      int64_t blk = 0, nb = 0;
+      if (chunk >= 1) {  // direct_blk_elts: >= 16 KiB blocks within the CTA bounds, the co-residency caps last
+        nb = (shard + (16 << 10) / esz - 1) / ((16 << 10) / esz);
+        nb = std::max<int64_t>(std::min<int64_t>(nb, maxC), minC);
+        nb = std::max<int64_t>(1, std::min<int64_t>({nb, (int64_t)cap, (int64_t)vccl::kDirectMaxBlocks}));
+        blk = ((shard + nb - 1) / nb + align - 1) / align * align;
+      }
+      // the force: absent half the time, aligned and large, too small, misaligned (where 16 bytes hold more than one element)
+      const int fk = (int)(mrng() % 6);
+      const int64_t force = fk <= 2 || chunk < 1 ? 0
+                            : fk == 3 ? blk + align * (int64_t)(mrng() % 4)
+                            : fk == 4 ? blk - align : blk + 1;
+      bool ok = chunk >= 1;  // a region that holds no unit is refused
+      if (ok && force > 0) {
+        ok = force >= blk && force % align == 0;
+        blk = force;
+      }
+      if (ok) nb = (shard + blk - 1) / blk;
+      ok = ok && shard * esz <= region && nb >= 1 && nb <= vccl::kDirectMaxBlocks;
+      vccl::DirectPlanOut dp;
+      const ncclResult_t r = vccl::direct_plan(coll, n, cnt, esz, region, minC, maxC, cap, force, &dp);
+      EXPECT(r == (ok ? ncclSuccess : ncclInternalError));
+      directPlans++;
+      if (r != ncclSuccess) continue;
+      directPlansOk++;
+      EXPECT(dp.chunkElts == chunk && dp.shardElts == shard && dp.blkElts == blk && dp.nBlocks == nb);
+      EXPECT(dp.nChunks == (cnt + chunk - 1) / chunk);
+      // chunks cover the count exactly once; the shards of a chunk cover it, each within a region
+      EXPECT((int64_t)dp.nChunks * dp.chunkElts >= cnt && (int64_t)(dp.nChunks - 1) * dp.chunkElts < cnt);
+      EXPECT(dp.shardElts * nSh >= dp.chunkElts && dp.shardElts * esz <= region);
+      EXPECT(dp.blkElts * esz % 16 == 0 && (force == 0 || dp.blkElts == force));
+      EXPECT((int64_t)(dp.nBlocks - 1) * dp.blkElts < dp.shardElts && dp.shardElts <= (int64_t)dp.nBlocks * dp.blkElts);
+      EXPECT(dp.nBlocks >= 1 && dp.nBlocks <= vccl::kDirectMaxBlocks);
+      if (coll >= 3) {  // the rooted pair: direct_rooted_plan's chunking, which the step lists run on
+        vccl::DirectRootedPlanOut rp;
+        EXPECT(vccl::direct_rooted_plan(coll, n, 0, 0, cnt, esz, region, -1, &rp) == ncclSuccess);
+        EXPECT(rp.chunkElts == dp.chunkElts && rp.nChunks == dp.nChunks && (int64_t)rp.owner.size() == nSh);
+      }
+    }
+    EXPECT(directPlansOk * 2 >= directPlans && directPlans >= 20000);
+    EXPECT(vccl::direct_plan(5, 2, 1, 1, 1 << 20, 1, 1, 64, 0, nullptr) == ncclInvalidArgument);
+    EXPECT(vccl::direct_plan(0, 2, 0, 1, 1 << 20, 1, 1, 64, 0, nullptr) == ncclInvalidArgument);
     alignas(16) char buf[1056] = {};
     for (int dt = 0; dt < (int)ncclNumTypes; dt++) {
       const bool has = dt == ncclFloat16 || dt == ncclBfloat16 || dt == ncclFloat32;
@@ -775,6 +839,8 @@ int main() {
   printf("host_api_check: %ld registration table operations, thresholds and zero-copy plans\n", regOps);
   printf("host_api_check: %ld all-to-all limits and plans\n", a2a);
   printf("host_api_check: %ld direct all-to-all limits and plans\n", directA2a);
+  printf("host_api_check: %ld direct geometries (%ld refused), %ld MXFP8 geometries\n", directPlans,
+         directPlans - directPlansOk, mxPlans);
   printf("host_api_check: %ld rooted selections and layouts\n", rooted);
   printf("host_api_check: %ld rooted direct selections and plans\n", directRooted);
   printf("host_api_check: %ld p2p plans\n", p2pPlans);

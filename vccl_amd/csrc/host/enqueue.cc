@@ -12,7 +12,7 @@
 // ncclAllToAll(v) is an internal group of them — or, on a comm that opted into
 // the one-hop LL or direct all-to-all (VCCL_LL_A2A_THRESHOLD,
 // VCCL_DIRECT_A2A_THRESHOLD), one task of its own whose small pairs take one LL
-// launch and whose mid-size pairs one direct launch (launch.cc launch_comm_p2p).
+// launch and whose mid-size pairs one direct launch (launch_p2p.cc launch_comm_p2p).
 // This file holds the nccl* entry points, their pnccl* aliases and the group
 // handling; the vccl* extension exports live in ext.cc.
 #include <algorithm>

@@ -263,7 +263,7 @@ VCCL_EXPORT ncclResult_t vcclP2pPlan(int rank, int nRanks, int nCalls, const int
                        gCap, maxWorks, cap, nItems, nWgs, items);
 }
 
-// The sends and recvs of this comm planned so far, by kind (launch.cc launch_p2p).
+// The sends and recvs of this comm planned so far, by kind (launch_p2p.cc launch_p2p).
 VCCL_EXPORT ncclResult_t vcclCommP2pStats(ncclComm_t comm, unsigned long long* llMessages,
                                           unsigned long long* fifoMessages) {
   NCCLCHECK(comm_check(comm, "vcclCommP2pStats"));

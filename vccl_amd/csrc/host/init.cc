@@ -190,7 +190,7 @@ static ncclResult_t create_flags_and_events(ncclComm* c) {
   HIPCHECK(hipHostMalloc((void**)&c->errorFlag, sizeof(int), hipHostMallocMapped));
   *c->abortFlag = 0;
   *c->errorFlag = 0;
-  // Ordering events (stream_order / stream_mark): only ever waited on by
+  // Ordering events (order.cc stream_order / stream_mark): only ever waited on by
   // other streams of this device, never by the host.  VCCL_EVENT_FENCE: 0 =
   // HIP's default system-scope release when the event is recorded, 1 =
   // device-scope release (hipEventReleaseToDevice), 2 = no system fence
@@ -536,7 +536,7 @@ ncclResult_t comm_init_rank(ncclComm_t* out, int nranks, const ncclUniqueId* id,
 
 // Wait for THIS comm's launches only — its ordering event, which every eager
 // launch of the comm records (bound to the kernel's completion, or a marker
-// behind it; launch.cc stream_mark), and the launches of one comm are
+// behind it; order.cc stream_mark), and the launches of one comm are
 // serialised through it, so the last one done means all done.  The
 // reference's commReclaim likewise waits on the comm's own strong stream
 // (src/init.cc:2079-2111), never the whole device: a hipDeviceSynchronize

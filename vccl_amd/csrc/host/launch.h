@@ -1,6 +1,6 @@
-// What launch.cc offers the API file (enqueue.cc) and the extension exports
-// (ext.cc): a checked call as a Task, its launch alone or as part of a group,
-// and the path queries.
+// What launch.cc and launch_p2p.cc offer the API file (enqueue.cc) and the
+// extension exports (ext.cc): a checked call as a Task, its launch alone or as
+// part of a group, and the path queries.
 #pragma once
 #include <vector>
 
@@ -56,7 +56,7 @@ struct Task {
   int skip;
   // ncclAllReduceWithBias: the bias, count elements, folded in last (nullptr: none).  Such a call is a bin of its
   // own in a group and fuses with bias calls only; the LL and direct launches carry it in their bias kernels, every
-  // other path is followed by one two-source reduce-copy recv = op(recv, acc) (launch.cc launch_bias_tail).
+  // other path is followed by one two-source reduce-copy recv = op(recv, acc) (launch.cc launch_path).
   const void* acc;
 };
 
@@ -84,6 +84,13 @@ ncclResult_t launch_task(const Task& t);
 ncclResult_t launch_group(std::vector<Task>& tasks);
 // Why `comm` cannot send or receive (WARN + ncclInvalidUsage), else ncclSuccess.
 ncclResult_t p2p_usable(const ncclComm* comm, const char* api);
+// One comm's sends, recvs and all-to-all tasks of a group, in call order (launch_p2p.cc).
+ncclResult_t launch_comm_p2p(const std::vector<Task>& mine);
+// The LL launches' 8-byte lines of a payload, and the bounded grid for that many lines (launch.cc).
+inline int64_t ll_lines_of(int64_t bytes) { return (bytes + 7) / 8; }
+int ll_grid(const ncclComm* comm, int64_t lines);
+// A launcher's hipError_t as the call's result: "<family> kernel launch failed: ..." + ncclUnhandledCudaError.
+ncclResult_t launch_result(hipError_t e, const char* family);
 
 }  // namespace vccl
 #pragma GCC visibility pop

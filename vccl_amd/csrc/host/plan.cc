@@ -324,26 +324,64 @@ int ar_mxfp8_op(uint64_t effective, int coll, int devOp, ncclDataType_t datatype
   if (datatype != ncclFloat16 && datatype != ncclBfloat16) return devOp;
   return (uint64_t)count * 2 >= effective ? kSumMxOp : devOp;
 }
-ncclResult_t direct_mx_plan(int nRanks, int64_t count, int64_t regionBytes, int minCTAs, int maxCTAs,
-                            int directMaxBlocks, int64_t blkForce, DirectMxPlanOut* out) {
-  const int64_t n = nRanks, regionTiles = regionBytes / kMxTileBytes;
-  if (n < 2 || n > kDirectMaxRanks || count < 1 || regionTiles < 1) return ncclInvalidArgument;
+ncclResult_t direct_cut_blocks(int64_t shardElts, int64_t eltSize, int64_t unit, int minCTAs, int maxCTAs,
+                               int directMaxBlocks, int64_t blkForce, int64_t* blkElts, int* nBlocks) {
+  if (shardElts < 1 || eltSize < 1 || unit < 1) return ncclInternalError;
+  // blocks of >= 16 KiB within the CTA bounds, then the co-residency caps (direct_blk_elts), in whole units
+  int64_t blk = (direct_blk_elts(shardElts, eltSize, minCTAs, maxCTAs, directMaxBlocks) + unit - 1) / unit * unit;
+  if (blkForce > 0) {
+    if (blkForce < blk || blkForce % unit) return ncclInternalError;
+    blk = blkForce;
+  }
+  const int64_t nb = (shardElts + blk - 1) / blk;
+  if (nb < 1 || nb > kDirectMaxBlocks) return ncclInternalError;
+  *blkElts = blk;
+  *nBlocks = (int)nb;
+  return ncclSuccess;
+}
+// The rooted chunk: nShards shards of whole 16-byte units, one per region (0 when a region holds no unit).
+static int64_t direct_rooted_chunk(int64_t count, int64_t esz, int64_t regionBytes, int nShards) {
+  const int64_t eltAlign = std::max<int64_t>(1, 16 / esz);
+  const int64_t regionElts = (regionBytes - 16) / esz / eltAlign * eltAlign;  // whole 16-byte units
+  return regionElts < eltAlign || nShards < 1 ? 0 : std::min<int64_t>(count, regionElts * nShards);
+}
+ncclResult_t direct_plan(int coll, int nRanks, int64_t count, int64_t eltSize, int64_t regionBytes, int minCTAs,
+                         int maxCTAs, int directMaxBlocks, int64_t blkForce, DirectPlanOut* out) {
+  const int64_t n = nRanks, esz = eltSize;
+  if (coll < kAllReduce || coll > kReduce || n < 1 || count < 1 || esz < 1) return ncclInvalidArgument;
+  const int64_t eltAlign = std::max<int64_t>(1, 16 / esz), regionElts = (regionBytes - 16) / esz;
+  if (coll == kBroadcast || coll == kReduce) {
+    const int nShards = direct_rooted_shards(coll == kReduce, nRanks);
+    out->chunkElts = direct_rooted_chunk(count, esz, regionBytes, nShards);
+    out->shardElts = out->chunkElts > 0 ? direct_shard_elts(out->chunkElts, nShards, eltAlign) : 0;
+  } else if (coll == kAllReduce) {
+    // as many elements as fit one shard per inbox region, a multiple of n x 16 bytes
+    out->chunkElts = std::min<int64_t>(count, regionElts * n / (n * eltAlign) * (n * eltAlign));
+    out->shardElts = out->chunkElts > 0 ? direct_shard_elts(out->chunkElts, nRanks, eltAlign) : 0;
+  } else {
+    // a chunk is a range of ONE rank's block that fits a region; it is cut into blocks directly
+    out->chunkElts = out->shardElts = std::min<int64_t>(count, regionElts / eltAlign * eltAlign);
+  }
+  if (out->chunkElts < 1) return ncclInternalError;  // a region that holds no unit
+  out->nChunks = (int)((count + out->chunkElts - 1) / out->chunkElts);
+  const ncclResult_t r = direct_cut_blocks(out->shardElts, esz, eltAlign, minCTAs, maxCTAs, directMaxBlocks, blkForce,
+                                           &out->blkElts, &out->nBlocks);
+  return r != ncclSuccess ? r : out->shardElts * esz > regionBytes ? ncclInternalError : ncclSuccess;
+}
+ncclResult_t direct_mx_plan(int nShards, int64_t count, int64_t regionBytes, int minCTAs, int maxCTAs,
+                            int directMaxBlocks, int64_t blkForce, DirectPlanOut* out) {
+  const int64_t n = nShards, regionTiles = regionBytes / kMxTileBytes;
+  if (n < 1 || n > kDirectMaxRanks || count < 1 || regionTiles < 1) return ncclInvalidArgument;
   out->chunkElts = std::min<int64_t>(count, regionTiles * n * kMxTileElts);
   const int64_t nChunks = (count + out->chunkElts - 1) / out->chunkElts;
   if (nChunks > INT32_MAX) return ncclInvalidArgument;
   out->nChunks = (int)nChunks;
-  out->shardTiles = ((out->chunkElts + kMxTileElts - 1) / kMxTileElts + n - 1) / n;
-  // blocks of >= 16 KiB of wire bytes (one byte per element, the scale lines aside), in whole tiles
-  const int64_t blk = direct_blk_elts(out->shardTiles * kMxTileElts, 1, minCTAs, maxCTAs, directMaxBlocks);
-  out->blkElts = (blk + kMxTileElts - 1) / kMxTileElts * kMxTileElts;
-  if (blkForce > 0) {
-    if (blkForce < out->blkElts || blkForce % kMxTileElts) return ncclInternalError;
-    out->blkElts = blkForce;
-  }
-  const int64_t blkTiles = out->blkElts / kMxTileElts;
-  out->nBlocks = (int)((out->shardTiles + blkTiles - 1) / blkTiles);
-  if (out->shardTiles > regionTiles || out->nBlocks < 1 || out->nBlocks > kDirectMaxBlocks) return ncclInternalError;
-  return ncclSuccess;
+  const int64_t shardTiles = ((out->chunkElts + kMxTileElts - 1) / kMxTileElts + n - 1) / n;  // of the largest chunk
+  out->shardElts = shardTiles * kMxTileElts;
+  // the wire bytes: one byte per element, the scale lines aside
+  const ncclResult_t r = direct_cut_blocks(out->shardElts, 1, kMxTileElts, minCTAs, maxCTAs, directMaxBlocks,
+                                           blkForce, &out->blkElts, &out->nBlocks);
+  return r != ncclSuccess ? r : shardTiles > regionTiles ? ncclInternalError : ncclSuccess;
 }
 int rsag_mxfp8_op(uint64_t effective, int coll, int devOp, ncclDataType_t datatype, size_t count, int nRanks) {
   if (effective == 0 || count == 0 || nRanks < 1) return devOp;
@@ -351,26 +389,6 @@ int rsag_mxfp8_op(uint64_t effective, int coll, int devOp, ncclDataType_t dataty
   if ((uint64_t)count * 2 * (uint64_t)nRanks < effective) return devOp;
   if (coll == kReduceScatter && devOp == OP_SUM) return kSumMxOp;
   return coll == kAllGather && devOp == kCopyOp ? kCopyMxOp : devOp;
-}
-ncclResult_t direct_mx_rsag_plan(int64_t count, int64_t regionBytes, int minCTAs, int maxCTAs, int directMaxBlocks,
-                                 int64_t blkForce, DirectMxPlanOut* out) {
-  const int64_t regionTiles = regionBytes / kMxTileBytes;
-  if (count < 1 || regionTiles < 1) return ncclInvalidArgument;
-  out->chunkElts = std::min<int64_t>(count, regionTiles * kMxTileElts);
-  const int64_t nChunks = (count + out->chunkElts - 1) / out->chunkElts;
-  if (nChunks > INT32_MAX) return ncclInvalidArgument;
-  out->nChunks = (int)nChunks;
-  out->shardTiles = (out->chunkElts + kMxTileElts - 1) / kMxTileElts;  // the largest chunk's tiles
-  const int64_t blk = direct_blk_elts(out->shardTiles * kMxTileElts, 1, minCTAs, maxCTAs, directMaxBlocks);
-  out->blkElts = (blk + kMxTileElts - 1) / kMxTileElts * kMxTileElts;
-  if (blkForce > 0) {
-    if (blkForce < out->blkElts || blkForce % kMxTileElts) return ncclInternalError;
-    out->blkElts = blkForce;
-  }
-  const int64_t blkTiles = out->blkElts / kMxTileElts;
-  out->nBlocks = (int)((out->shardTiles + blkTiles - 1) / blkTiles);
-  if (out->shardTiles > regionTiles || out->nBlocks < 1 || out->nBlocks > kDirectMaxBlocks) return ncclInternalError;
-  return ncclSuccess;
 }
 uint64_t ll_rooted_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks) {
   if (threshold <= 0 || llSlotBytes <= 0 || !llAllowed || anyNet || nRanks > kOrderMaxRanks) return 0;
@@ -582,11 +600,10 @@ ncclResult_t direct_rooted_plan(int coll, int nRanks, int rank, int root, int64_
   const bool reduce = coll == kReduce;
   const int n = nRanks, nShards = direct_rooted_shards(reduce, n);
   const int64_t esz = eltSize, eltAlign = std::max<int64_t>(1, 16 / esz);
-  const int64_t regionElts = (regionBytes - 16) / esz / eltAlign * eltAlign;  // whole 16-byte units
-  if (regionElts < eltAlign || nShards < 1) return ncclInvalidArgument;
+  if (direct_rooted_chunk(1, esz, regionBytes, nShards) < 1) return ncclInvalidArgument;
   out->owner.clear();
   out->steps.clear();
-  out->chunkElts = std::min<int64_t>(count, regionElts * nShards);
+  out->chunkElts = direct_rooted_chunk(count, esz, regionBytes, nShards);
   const int64_t nChunks = out->chunkElts > 0 ? (count + out->chunkElts - 1) / out->chunkElts : 0;
   if (nChunks > INT32_MAX) return ncclInvalidArgument;
   out->nChunks = (int)nChunks;

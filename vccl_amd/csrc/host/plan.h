@@ -1,6 +1,6 @@
 // The restatement of VCCL's planner (plan.cc): pure integer arithmetic on
-// plain structs — no runtime call, no communicator, no stream.  launch.cc
-// reads a comm into these inputs; the plan exports (ext.cc) and through
+// plain structs — no runtime call, no communicator, no stream.  launch.cc and
+// launch_p2p.cc read a comm into these inputs; the plan exports (ext.cc) and through
 // them the CPU parity tests (oracle/vccl_sched.py) pass explicit ones.
 #pragma once
 #include <algorithm>
@@ -108,10 +108,10 @@ bool sum_fp32_effective(bool on, bool inbox, bool directAllowed, bool anyNet, in
 // included) over f16, bf16, e4m3 or e5m2 on a comm where the opt-in is
 // effective (`level` 1 or 2; 0: off), at level 2 for such a reduce too; devOp
 // unchanged for every other call.  At level 1 a call with a wide op takes the
-// staged direct path at every size (group_plan, launch.cc choose_algo) and
+// staged direct path at every size (group_plan, launch.cc path_of) and
 // never the zero-copy one.  At level 2 a call on its own also takes the other
 // paths where one rank holds all n inputs of an element (sum_fp32_algo below,
-// launch.cc reg_algo_or): the one-hop LL kernels and the zero-copy kernels;
+// launch.cc path_of): the one-hop LL kernels and the zero-copy kernels;
 // inside a group of several collectives it keeps level 1's rule.
 constexpr int kSumWideOp = 5, kPreMulSumWideOp = 6;  // dispatch.hpp OP_SUM_WIDE / OP_PREMULSUM_WIDE (tied in launch.cc)
 inline bool is_wide_sum_op(int devOp) { return devOp == kSumWideOp || devOp == kPreMulSumWideOp; }
@@ -137,21 +137,22 @@ uint64_t ar_mxfp8_min(int64_t threshold, bool inbox, bool directAllowed, bool an
 // whose devOp is OP_SUM (ncclSum alone: ncclAvg and PreMulSum resolve to other codes) over f16 / bf16 and whose
 // count * size reaches `effective` (> 0); devOp unchanged for every other call.  Asked BEFORE sum_fp32_op, so it
 // wins where both apply.  A call with this op takes the staged direct launch at every size (group_plan, launch.cc
-// choose_algo), never negotiates zero-copy, and is a bin of its own in a group through its devOp.
+// path_of), never negotiates zero-copy, and is a bin of its own in a group through its devOp.
 constexpr int kSumMxOp = 7;  // tied to dispatch.hpp in launch.cc
 int ar_mxfp8_op(uint64_t effective, int coll, int devOp, ncclDataType_t datatype, size_t count, bool bias);
-// Launch geometry of one such call, in wire tiles of kMxTileElts elements (device/direct_mx.hpp reads it from
+// Launch geometry of one MXFP8 call, in wire tiles of kMxTileElts elements (device/direct_mx.hpp reads it from
 // DirectWork): a region holds floor(regionBytes / kMxTileBytes) tiles; a chunk is at most that many tiles per
-// shard, n shards, so chunkElts is a multiple of kMxTileElts * n unless the call is one chunk; the shard of the
-// largest chunk (shardTiles tiles) is cut into nBlocks blocks of blkElts elements (whole tiles) by direct_blk_elts
-// on the shard's wire bytes.  blkForce > 0 imposes the block length (a fused batch's common one).
-// ncclInvalidArgument when a region holds no tile.
-struct DirectMxPlanOut {
-  int64_t chunkElts = 0, blkElts = 0, shardTiles = 0;
+// shard.  nShards = n for the all-reduce, whose chunkElts is a multiple of kMxTileElts * n unless the call is one
+// chunk; nShards = 1 for the reduce-scatter / all-gather, whose chunk is a range of ONE rank's block of `count`
+// elements.  The shard of the largest chunk (shardTiles tiles) is cut into nBlocks blocks of blkElts elements by
+// direct_cut_blocks on the shard's wire bytes, in whole tiles; shardElts = shardTiles * kMxTileElts.  blkForce > 0
+// imposes the block length (a fused batch's common one).  ncclInvalidArgument when a region holds no tile.
+struct DirectPlanOut {
+  int64_t chunkElts = 0, shardElts = 0, blkElts = 0;
   int nChunks = 0, nBlocks = 0;
 };
-ncclResult_t direct_mx_plan(int nRanks, int64_t count, int64_t regionBytes, int minCTAs, int maxCTAs,
-                            int directMaxBlocks, int64_t blkForce, DirectMxPlanOut* out);
+ncclResult_t direct_mx_plan(int nShards, int64_t count, int64_t regionBytes, int minCTAs, int maxCTAs,
+                            int directMaxBlocks, int64_t blkForce, DirectPlanOut* out);
 // The same format for the one-hop direct reduce-scatter and all-gather (VCCL_RSAG_MXFP8_THRESHOLD /
 // vcclCommSetRsAgMxfp8Threshold); the threshold takes effect as ar_mxfp8_min says, on its own
 // variable.  The device op a call runs with: kSumMxOp for an ncclReduceScatter whose devOp is OP_SUM, kCopyMxOp
@@ -159,17 +160,10 @@ ncclResult_t direct_mx_plan(int nRanks, int64_t count, int64_t regionBytes, int 
 // per-rank count) and nRanks * count * 2 >= `effective` (> 0: the whole bucket, reg_eligible's size convention);
 // devOp unchanged for every other call.  Asked BEFORE sum_fp32_op; such a call takes the staged direct launch at
 // every size, never negotiates zero-copy, and is a bin of its own in a group (group_task_of keys the all-gather
-// by this op and its type instead of the byte copy's).
+// by this op and its type instead of the byte copy's).  Its geometry is direct_mx_plan's with one shard.
 constexpr int kCopyMxOp = 8, kCopyOp = 15;  // OP_COPY_MXFP8 / OP_COPY, tied to dispatch.hpp in launch.cc
 inline bool is_mx_devop(int devOp) { return devOp == kSumMxOp || devOp == kCopyMxOp; }
 int rsag_mxfp8_op(uint64_t effective, int coll, int devOp, ncclDataType_t datatype, size_t count, int nRanks);
-// Launch geometry of one such call, in wire tiles (device/direct_mx.hpp): a region holds floor(regionBytes /
-// kMxTileBytes) tiles; a chunk is a range of ONE rank's block of `count` elements, chunkElts = min(count,
-// regionTiles * kMxTileElts), so every chunk but the last is whole tiles; the largest chunk (shardTiles tiles) is
-// cut into nBlocks blocks of blkElts elements (whole tiles) by direct_blk_elts on its wire bytes.  blkForce as in
-// direct_mx_plan.  ncclInvalidArgument when a region holds no tile.
-ncclResult_t direct_mx_rsag_plan(int64_t count, int64_t regionBytes, int minCTAs, int maxCTAs, int directMaxBlocks,
-                                 int64_t blkForce, DirectMxPlanOut* out);
 int proto_of_algo(int algo);
 
 struct GroupTask {
@@ -241,7 +235,7 @@ ncclResult_t ll_rooted_plan(int coll, int nRanks, int rank, const std::vector<in
 // direct_reduce_part) as `rank` runs it: the chunk length, the shards of chunk
 // `chunk` and their owners, and the ordered steps of that chunk.  The step
 // order IS the kernel's phase order — the two are kept side by side and name
-// each other; host/launch.cc direct_work_of takes its geometry from here.
+// each other; the launch geometry (chunk, shard, blocks) is direct_plan's below.
 // Lengths and offsets in bytes; a step covers a whole shard (workgroup b moves
 // bytes [b * blk, (b + 1) * blk) of it, so region offsets are 0).
 //   kDStepWait   {phase, peer = from}
@@ -439,7 +433,7 @@ ncclResult_t reg_a2a_plan(int nRanks, int rank, const int64_t* sendBytes, const 
 uint64_t ll_a2a_max(int64_t threshold, int64_t llSlotBytes, bool llAllowed, bool anyNet, int nRanks, bool hasP2p);
 // A comm's VCCL_DIRECT_A2A_THRESHOLD (bytes per ordered pair) as it takes
 // effect: clamped to what one inbox region holds ((regionBytes - 16) rounded
-// down to 16 bytes, the slack launch.cc direct_work_of leaves); 0 without
+// down to 16 bytes, the slack direct_plan leaves); 0 without
 // mapped inboxes (regionBytes == 0), with Direct excluded by NCCL_ALGO, with a
 // peer behind the net proxy, with fewer than 2 or more than kDirectMaxRanks
 // ranks, or on a comm without point-to-point connections.
@@ -456,7 +450,7 @@ inline int a2a_pair_path(uint64_t llA2aMax, uint64_t directA2aMax, int64_t bytes
   return directA2aMax > 0 && (uint64_t)bytes <= directA2aMax ? kA2aDirect : kA2aFifo;
 }
 // The direct kernels' block length for a shard of `len` elements of `esz`
-// bytes (launch.cc direct_work_of, a2a_plan): nb = ceil(len / 16 KiB) blocks
+// bytes (direct_cut_blocks, a2a_plan): nb = ceil(len / 16 KiB) blocks
 // (one 512-thread x 2-pack hunk each) clamped by maxCTAs / minCTAs, then by the
 // co-residency caps directMaxBlocks and kDirectMaxBlocks LAST, so NCCL_MIN_CTAS
 // cannot push past them; the length is alignUp(ceil(len / nb), 16
@@ -468,6 +462,19 @@ inline int64_t direct_blk_elts(int64_t len, int64_t esz, int minCTAs, int maxCTA
   nb = std::max<int64_t>(1, std::min<int64_t>({nb, (int64_t)directMaxBlocks, (int64_t)kDirectMaxBlocks}));
   return ((len + nb - 1) / nb + eltAlign - 1) / eltAlign * eltAlign;
 }
+// Cut a shard into blocks of whole `unit`s (elements: 16 bytes' worth natively, a wire tile for MXFP8): the
+// natural block is direct_blk_elts'; blkForce > 0 imposes one (a fused batch's common length), refused below the
+// natural block or off the unit; nBlocks = ceil(shardElts / blkElts) in 1 .. kDirectMaxBlocks, else refused.
+ncclResult_t direct_cut_blocks(int64_t shardElts, int64_t eltSize, int64_t unit, int minCTAs, int maxCTAs,
+                               int directMaxBlocks, int64_t blkForce, int64_t* blkElts, int* nBlocks);
+// Launch geometry of one staged direct call (device/direct.hpp reads it from DirectWork); count in elements of
+// eltSize (the byte copies: bytes, 1).  All-reduce: a chunk is floor((regionBytes - 16) / eltSize) * n elements
+// rounded down to n x 16 bytes, its shard direct_shard_elts.  Reduce-scatter / all-gather: a chunk is a range of
+// ONE rank's block, the region's elements rounded down to 16 bytes, and its own shard.  Broadcast / reduce:
+// direct_rooted_plan's chunk, n - 1 / n shards.  shardElts is the largest chunk's, cut by direct_cut_blocks.
+// ncclInternalError when a region holds no unit, the shard exceeds it, or the cut refuses.
+ncclResult_t direct_plan(int coll, int nRanks, int64_t count, int64_t eltSize, int64_t regionBytes, int minCTAs,
+                         int maxCTAs, int directMaxBlocks, int64_t blkForce, DirectPlanOut* out);
 // One ncclAllToAll (uniform) / ncclAllToAllv call as `rank` runs it (device/
 // ll.hpp ll_alltoall, device/direct.hpp direct_alltoall).  Launch rule,
 // identical on every rank: a uniform call of B bytes per pair is one LL launch
